@@ -22,12 +22,19 @@ A step is one full Cut pass (every kernel, token spans out) over the rank's
 shard, inputs already resident in HBM.  `value` = all ranks' runes x K / the
 slowest rank's time for the K timed steps.
 
-After timing, every rank downloads its spans and checks ALL of its shard
-token for token against the oracle (oracle/jieba_oracle.c, the C restatement
-of tokenizer.go) on the host's CPUs; at N = 1 that full-corpus oracle run is
+A plain run stops there: set up, warm up, time the K steps, download the last
+step's spans, print the line.  `--dump-outputs DIR` also writes those spans as
+DIR/<name>.npy (dump_outputs below); the inputs are seeded, so two builds run
+with the same arguments can be compared file for file.
+
+`--full` adds everything else.  Every rank checks ALL of its shard token for
+token against the oracle (oracle/jieba_oracle.c, the C restatement of
+tokenizer.go) on the host's CPUs; at N = 1 that full-corpus oracle run is
 also `cpu_baseline` (threads = the CPUs this process may use).  `roofline` is
 the dominant kernel's, from HIP event pairs around each launch on the launch
-stream (a second pass of the K steps, kernel by kernel).
+stream (a second pass of the K steps, kernel by kernel).  `end_to_end_host`
+and `roofline_latency` (N = 1) are the host-memory paths and k_zh's latency
+probe.  Without --full those keys are null or absent.
 
 Other BASELINE configs: --workload sentence (config 1: jb_cut latency on the
 19-rune sentence of tokenizer_test.go:531), s10k (configs 2/3 with --hmm 0/1),
@@ -257,6 +264,37 @@ def check_shard(results, o, buf, off, hmm, threads):
             "oracle_ties": int(o.ties)}
 
 
+DUMP_SAMPLE_TOKENS = 3_000_000  # starts + ends of the sample as float64: 48 MB, under the 64 MB a dump may take
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, results, suffix=""):
+    """--dump-outputs: what the timed path's last step returned (GpuCutter.results), as
+    float64 .npy files (u32 byte offsets and token counts below 2^53 are exact in it):
+    doc_tok (every document's first token index, whole), doc_start_sum / doc_end_sum
+    (per document, the sum of its tokens' start / end offsets: every token of the
+    output is in one of them), and starts / ends, whole when they fit, else at a fixed
+    seeded sample of token indices (drawn from the token count alone, in index order)."""
+    starts, ends, doc_tok = results
+    os.makedirs(out_dir, exist_ok=True)
+    doc_tok = np.asarray(doc_tok, np.uint64)
+    ntok = len(starts)
+
+    def doc_sums(x):
+        cs = np.zeros(ntok + 1, np.uint64)
+        np.cumsum(x, dtype=np.uint64, out=cs[1:])
+        return (cs[doc_tok[1:]] - cs[doc_tok[:-1]]).astype(np.float64)
+
+    pick = None
+    if ntok > DUMP_SAMPLE_TOKENS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).integers(0, ntok, DUMP_SAMPLE_TOKENS))
+    for name, a in (("doc_tok", doc_tok.astype(np.float64)),
+                    ("doc_start_sum", doc_sums(starts)), ("doc_end_sum", doc_sums(ends)),
+                    ("starts", (starts if pick is None else starts[pick]).astype(np.float64)),
+                    ("ends", (ends if pick is None else ends[pick]).astype(np.float64))):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def job_sums(dist, agg_dev, vals, op="sum"):
     """Element-wise sum (or max) of a list of floats over ranks."""
     if dist is None:
@@ -357,15 +395,18 @@ def run(args, world, rank, dist, agg_dev, make_cutter, open_oracle, log=print):
     results = cutter.results()
     ties = cutter.ties()
     ntok = int(len(results[0]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, results, "" if world == 1 else f"_rank{rank}")
 
-    kprof, prof_ms = ({}, None) if args.no_profile else cutter.profile(args.steps)
+    full = args.full  # everything past the headline figure is --full's
+    kprof, prof_ms = cutter.profile(args.steps) if full and not args.no_profile else ({}, None)
     kernels = {k: {"avg_ms": ms / n, "launches": int(n)} for k, (ms, n) in kprof.items() if n}
 
     # ---- parity: this rank's whole shard against the oracle ----------------
     ncpu, nproc, quota = effective_cpus()
     par = None
     o = None
-    if not args.no_parity:
+    if full and not args.no_parity:
         o = open_oracle()
         import oracle as O
         O.set_viterbi_backptr(args.workload.startswith("long"))  # path copy is O(m^2) on a 1M-rune run
@@ -457,6 +498,7 @@ def run(args, world, rank, dist, agg_dev, make_cutter, open_oracle, log=print):
         "kernels_ms": {k: round(v["avg_ms"], 4) for k, v in kernels.items()},
         "ms_per_step_kernel_by_kernel": round(prof_ms, 4) if prof_ms else None,
         "gen_s": round(gen_s, 2),
+        "full": bool(args.full),
         "workload_key": wkey,
     }
     return line, (sbuf, soff, cutter)
@@ -519,23 +561,32 @@ def end_to_end(tk, buf, off, hmm, nrunes, reps=3):
 
 def sentence_latency(tk, o, n):
     """Config 1: Cut(sentence, hmm=true) through jb_cut (host string in, spans out,
-    the same call a Go caller makes); the oracle on one core beside it."""
+    the same call a Go caller makes); with an oracle `o` (--full), the oracle on one
+    core beside it.  Returns (latencies, oracle latencies or None, the last call's
+    (starts, ends, doc_tok))."""
     import ctypes as C
     import jiebahip as J
-    import oracle as O
     t = SENTENCE.encode("utf-8")
     sp = J.jb_spans()
     L = J.lib()
-    assert tk.Cut(SENTENCE, True) == o.cut(SENTENCE, True)
+    if o is not None:
+        assert tk.Cut(SENTENCE, True) == o.cut(SENTENCE, True)
     for _ in range(50):
         J._check(L.jb_cut(tk.h, t, len(t), 1, C.byref(sp)))
         L.jb_spans_free(C.byref(sp))
     lat = np.empty(n)
+    last = None
     for i in range(n):
         a = time.perf_counter_ns()
         J._check(L.jb_cut(tk.h, t, len(t), 1, C.byref(sp)))
         lat[i] = time.perf_counter_ns() - a
+        if i == n - 1:
+            k = int(sp.ntokens)
+            last = (np.array(sp.start[:k], np.uint64), np.array(sp.end[:k], np.uint64), np.array([0, k], np.uint64))
         L.jb_spans_free(C.byref(sp))
+    if o is None:
+        return lat, None, last
+    import oracle as O
     ol = O.lib()
     s = np.zeros(64, np.uint32)
     e = np.zeros(64, np.uint32)
@@ -739,13 +790,20 @@ def parse_args(argv=None):
     ap.add_argument("--dict-kind", choices=["prefix", "txt"], default="prefix",
                     help="prefix: NewJiebaTokenizer semantics (prefix_dictionary.gob, size 60,101,967) as in the "
                          "reference's own benchmarks; txt: NewTokenizer(dict.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the oracle "
+                         "check of every token (parity, cpu_baseline), the kernel-by-kernel pass (kernels_ms, "
+                         "roofline), the host-memory paths (end_to_end_host) and the roofline_latency probe; "
+                         "the --no-* options below drop single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/<name>.npy (float64; see dump_outputs)")
     ap.add_argument("--cpu1-sample-mib", type=float, default=96.0,
-                    help="one-thread oracle sample (docs, N = 1); 0: skip")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check (and cpu_baseline)")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+                    help="--full: one-thread oracle sample (docs, N = 1); 0: skip")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle check (and cpu_baseline)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip end_to_end_host")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the kernel-by-kernel pass")
     ap.add_argument("--sentence-iters", type=int, default=5000)
-    ap.add_argument("--no-latency", action="store_true", help="skip the roofline_latency probe")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the roofline_latency probe")
     ap.add_argument("--latency-probe", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -797,8 +855,9 @@ def main(argv=None):
         return O.Oracle.from_files(dpath, epath, kind, size_override)
 
     if args.workload == "sentence":
-        o = open_oracle()
-        lat, olat = sentence_latency(tk, o, args.sentence_iters)
+        lat, olat, last = sentence_latency(tk, open_oracle() if args.full else None, args.sentence_iters)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
         med = float(np.median(lat))
         line = {"metric": METRIC, "value": round(19 / (med * 1e-9), 1), "unit": "chars/s", "n_gpus": 1,
                 "steps": args.sentence_iters, "warmup": 50, "ms_per_step": round(med * 1e-6, 5),
@@ -812,10 +871,11 @@ def main(argv=None):
                 "latency_ns": {"median": med, "p10": float(np.percentile(lat, 10)),
                                "p99": float(np.percentile(lat, 99)), "mean": float(lat.mean())},
                 "reference_ns_per_op": {"value": REF_SENTENCE_NS, "hardware": "i5-9400 (tokenizer_test.go:610)"},
-                "cpu_baseline": {"value": round(19 / (float(np.median(olat)) * 1e-9), 1), "unit": "chars/s",
-                                 "cores": 1, "kind": "port", "latency_ns_median": float(np.median(olat)),
-                                 "sample": f"{args.sentence_iters} calls of or_cut (oracle/jieba_oracle.c) on the "
-                                           "same sentence, ctypes call overhead included", "cpu_model": cpu_model()},
+                "cpu_baseline": None if olat is None else {
+                    "value": round(19 / (float(np.median(olat)) * 1e-9), 1), "unit": "chars/s",
+                    "cores": 1, "kind": "port", "latency_ns_median": float(np.median(olat)),
+                    "sample": f"{args.sentence_iters} calls of or_cut (oracle/jieba_oracle.c) on the "
+                              "same sentence, ctypes call overhead included", "cpu_model": cpu_model()},
                 "roofline": None}
         print(json.dumps(line), flush=True)
         backend.close()
@@ -834,9 +894,9 @@ def main(argv=None):
             line["data"] = "TEST (JB_BENCH_SHARE_GPU, ranks share a GPU): not a scaling measurement; " + line["data"]
         if backend.name != "gpu":
             line["data"] = f"TEST BACKEND {backend.name}: not a measurement"
-        if world == 1 and not args.no_e2e:
+        if args.full and world == 1 and not args.no_e2e:
             line["end_to_end_host"] = end_to_end(tk, sbuf, soff, args.hmm, line["config"]["corpus_chars"])
-        if world == 1 and args.workload == "docs" and not args.no_latency:
+        if args.full and world == 1 and args.workload == "docs" and not args.no_latency:
             line["roofline_latency"] = roofline_latency()
         line["loaded"] = J.loaded_runtime() if backend.name == "gpu" else None
         print(json.dumps(line), flush=True)

@@ -335,7 +335,7 @@ def test_bench_two_ranks_on_the_gpu(tmp_path):
     env = dict(os.environ, JB_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--corpus-mib", "32",
-                        "--steps", "2", "--warmup", "1", "--no-e2e", "--no-latency", "--no-profile",
+                        "--steps", "2", "--warmup", "1", "--full", "--no-e2e", "--no-latency", "--no-profile",
                         "--cpu1-sample-mib", "0"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

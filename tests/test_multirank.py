@@ -32,7 +32,8 @@ def _worker(rank, world, port, dict_path, emit_path, corpus_mib, corrupt_rank, o
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     args = types.SimpleNamespace(workload="docs", corpus_mib=corpus_mib, nwords=20_000, hmm=1, steps=3, warmup=1,
-                                 no_profile=True, no_parity=False, cpu1_sample_mib=0, dict_kind="txt")
+                                 full=True, no_profile=True, no_parity=False, cpu1_sample_mib=0, dict_kind="txt",
+                                 dump_outputs=None)
     seen = {}
 
     def make_cutter(buf, off, hmm):
@@ -141,8 +142,8 @@ def test_bench_two_ranks_gloo(syn_small, corrupt_rank):
 
 def _bench_cmd(*extra):
     return [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "docs", "--corpus-mib", "0.75",
-            "--nwords", "20000", "--steps", "3", "--warmup", "1", "--no-profile", "--no-e2e", "--no-latency",
-            "--cpu1-sample-mib", "0", "--dict-kind", "txt", *extra]
+            "--nwords", "20000", "--steps", "3", "--warmup", "1", "--full", "--no-profile", "--no-e2e",
+            "--no-latency", "--cpu1-sample-mib", "0", "--dict-kind", "txt", *extra]
 
 
 def _bench_env(**kw):
@@ -178,6 +179,57 @@ def test_bench_launcher_two_ranks(corrupt_rank):
     pr = line["config"]["ranks"]["per_rank"]
     assert [r["rank"] for r in pr] == [0, 1] and sum(r["shard_bytes"] for r in pr) == line["config"]["corpus_bytes"]
     assert [r["bit_exact"] for r in pr] == [True, corrupt_rank != 1]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """Without --full the line has the headline figure and none of the other legs, and
+    --dump-outputs writes the last step's spans as float64 arrays that two runs with
+    the same arguments reproduce and that are the oracle's tokens (stand-in backend)."""
+    import json
+    import oracle as O
+    import synth
+    cmd = [a for a in _bench_cmd("--gpus", "1") if a != "--full"]
+    dumps = []
+    for name in ("a", "b"):
+        d = str(tmp_path / name)
+        p = subprocess.run(cmd + ["--dump-outputs", d], env=_bench_env(), capture_output=True, text=True,
+                           timeout=300, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["full"] is False and line["parity"] is None and line["cpu_baseline"] is None
+        assert line["roofline"] is None and not line["kernels_ms"]
+        assert "end_to_end_host" not in line and "roofline_latency" not in line
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["doc_end_sum", "doc_start_sum", "doc_tok", "ends", "starts"] == sorted(b)
+    assert all(a[k].dtype == np.float64 and np.array_equal(a[k], b[k]) for k in a)
+    s = synth.Synth(nwords=20_000)
+    dp, ep = s.write_files(str(tmp_path))
+    buf, off, _ = s.corpus_parallel(synth.KIND_DOCS, 0, target_bytes=int(0.75 * (1 << 20)), threads=2)
+    ws, we, wd = O.Oracle.from_files(dp, ep, 0).cut_batch(buf, off, True, nthreads=2)
+    assert np.array_equal(a["starts"], ws) and np.array_equal(a["ends"], we) and np.array_equal(a["doc_tok"], wd)
+    assert a["doc_start_sum"].sum() == ws.sum(dtype=np.uint64) and a["doc_end_sum"].sum() == we.sum(dtype=np.uint64)
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path):
+    """Past DUMP_SAMPLE_TOKENS tokens, starts / ends are a fixed seeded sample (the same
+    indices for the same token count) and the per-document sums still cover every token."""
+    import bench
+    n = bench.DUMP_SAMPLE_TOKENS + 12_345
+    starts = np.arange(n, dtype=np.uint32) * np.uint32(3)
+    ends = starts + np.uint32(3)
+    doc_tok = np.array([0, 0, 5, n - 7, n, n], np.uint64)  # empty documents first, inside and last
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), (starts, ends, doc_tok))
+    a, b = ({f[:-4]: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)} for name in ("a", "b"))
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert len(a["starts"]) == bench.DUMP_SAMPLE_TOKENS and np.array_equal(a["ends"], a["starts"] + 3)
+    assert np.all(np.diff(a["starts"]) >= 0) and a["starts"].max() <= 3 * (n - 1) and np.all(a["starts"] % 3 == 0)
+    assert sum(v.nbytes for v in a.values()) <= 64_000_000
+    want = [0, 3 * sum(range(5)), 3 * sum(range(5, n - 7)), 3 * sum(range(n - 7, n)), 0]
+    assert a["doc_start_sum"].tolist() == want and a["doc_end_sum"][2] == want[2] + 3 * (n - 12)
+    assert np.array_equal(a["doc_tok"], doc_tok)
 
 
 def test_roofline_charges_the_output_format():

@@ -9,7 +9,7 @@
 #   abw:W:V1,...      the same on workload W (sentence, s10k, long-oov, ...)
 #   req:V             one PMC pass of L1->L2 read requests and L1 accesses per kernel (V = lib or a variant)
 #   pmc               every PMC pass of the headline (tools/final_profile.sh: summary, stats, bench line)
-#   bench             the default bench line
+#   bench             the default bench line with every leg (bench.py --full)
 #   cfg               the other BASELINE configs (tools/configs.sh)
 #   smoke             __graft_entry__.smoke()
 #   roundend          tools/round_end.sh (smoke, final profile, configs, sentence stats)
@@ -53,7 +53,7 @@ for step in "$@"; do
       IFS=, read -ra vs <<< "${rest#*:}"
       for r in $(seq 1 ${REPS:-2}); do
         for v in lib "${vs[@]}"; do
-          JB_LIB=$(libof "$v") timeout -k 10 300 python bench.py --workload "$w" --no-e2e --no-parity ${BENCH_ARGS:-} \
+          JB_LIB=$(libof "$v") timeout -k 10 300 python bench.py --full --workload "$w" --no-e2e --no-parity ${BENCH_ARGS:-} \
             > "$OUT/abw_${w}_$v.$r.json" 2> "$OUT/abw_${w}_$v.$r.err" || fail "$step" "$OUT/abw_${w}_$v.$r.err"
           python -c "import json; d=json.load(open('$OUT/abw_${w}_$v.$r.json')); print('$w', '$v', d['ms_per_step'], {k: round(x, 4) for k, x in (d.get('kernels_ms') or {}).items()})"
         done
@@ -78,7 +78,7 @@ EOF
     pmc)
       TAG=$RUN/fp bash tools/final_profile.sh || fail "$step" /dev/null ;;
     bench)
-      timeout -k 10 500 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || fail "$step" "$OUT/bench.err"
+      timeout -k 10 500 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || fail "$step" "$OUT/bench.err"
       head -c 1500 "$OUT/bench.json"; echo ;;
     cfg)
       TAG=$RUN/cfg bash tools/configs.sh || fail "$step" /dev/null ;;
@@ -116,7 +116,7 @@ EOF
       for r in $(seq 1 ${REPS:-2}); do
         for e in "" "$kv"; do
           tag=$( [ -z "$e" ] && echo default || echo "${e//=/_}" )
-          env $e timeout -k 10 300 python bench.py --workload "$w" --no-e2e --no-parity ${BENCH_ARGS:-} \
+          env $e timeout -k 10 300 python bench.py --full --workload "$w" --no-e2e --no-parity ${BENCH_ARGS:-} \
             > "$OUT/envab_${w}_$tag.$r.json" 2> "$OUT/envab_${w}_$tag.$r.err" || fail "$step" "$OUT/envab_${w}_$tag.$r.err"
           python -c "import json; d=json.load(open('$OUT/envab_${w}_$tag.$r.json')); print('$w', '$tag', d['ms_per_step'], {k: round(x, 4) for k, x in (d.get('kernels_ms') or {}).items()})"
         done
