@@ -169,6 +169,45 @@ int jb_cut_device_into(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, cons
                        uint32_t ndocs, int hmm, void *stream, uint32_t *d_start, uint32_t *d_end, uint64_t cap,
                        uint64_t *d_doc_tok, uint64_t *d_ntok);
 
+/* ---- search mode (jieba's cut_for_search; the reference has only Cut) ------
+ * The spans of Cut(doc, hmm), expanded.  For each token T = [s, e) of Cut's result, in
+ * order, the output holds, all of them byte ranges of the input inside T's document:
+ *  - T alone when T's first rune is not Han (a token of a non-Han block);
+ *  - for a Han token whose n runes start at bytes p_0 < ... < p_{n-1}, p_n = e:
+ *      n > 2: [p_i, p_{i+2}) for i = 0 .. n-2, ascending, where E(i, 2);
+ *      n > 3: then [p_i, p_{i+3}) for i = 0 .. n-3, ascending, where E(i, 3);
+ *      then T.
+ *    E(i, L): buildDag (tokenizer.go:462-497) has the edge of L runes from rune i, that is
+ *    termFreq[r_i] is found and not 0 (:468-471), every prefix r_i..r_{i+k}, k < L-1, is
+ *    found (:476-478), and termFreq[r_i..r_{i+L-1}] > 0 (:479).
+ * Tokens made by the HMM expand like dictionary tokens.  ntokens / *d_ntok and doc_tok
+ * describe the expanded list; a token gives at most as many spans as it has bytes, so a
+ * batch of n bytes has at most n spans.  Errors (JB_EPANIC included) are those of the plain
+ * call.  jb_last_stats keeps reporting the plain counts (tokens = Cut's tokens).
+ * Two deliberate differences from Python jieba's cut_for_search:
+ *  - a gram that buildDag cannot see is not emitted: one whose first rune has frequency
+ *    0, or (JB_DICT_TXT) one with a prefix that is not in the dictionary.  Cut could
+ *    never produce that word either;
+ *  - non-Han tokens are never expanded: the trie holds only all-Han keys, and the
+ *    reference never consults the dictionary for non-Han blocks. */
+
+/* jb_cut in search mode: one document. */
+int jb_cut_search(jb_ctx *ctx, const uint8_t *text, size_t len, int hmm, jb_spans *out);
+/* jb_cut_batch in search mode (arguments and ownership as jb_cut_batch). */
+int jb_cut_batch_search(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm,
+                        jb_spans *out);
+/* jb_cut_device in search mode (arguments, limits, alignment and lifetime as jb_cut_device):
+ * *d_start / *d_end / *d_doc_tok / *d_ntok are the expanded spans, their per-document
+ * offsets and their count, in ctx-owned device memory until the next call on this ctx. */
+int jb_cut_device_search(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uint64_t *d_doc_off,
+                         uint32_t ndocs, int hmm, void *stream, uint32_t **d_start, uint32_t **d_end,
+                         uint64_t **d_doc_tok, uint64_t **d_ntok);
+/* jb_cut_device_into in search mode: the expanded spans into caller-owned device arrays of
+ * cap >= nbytes u32 entries, d_doc_tok ndocs+1 u64 and *d_ntok the expanded count. */
+int jb_cut_device_search_into(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uint64_t *d_doc_off,
+                              uint32_t ndocs, int hmm, void *stream, uint32_t *d_start, uint32_t *d_end,
+                              uint64_t cap, uint64_t *d_doc_tok, uint64_t *d_ntok);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

@@ -128,6 +128,10 @@ struct Device {
     DevImage dim{};
     // workspace
     Work w{};
+    // search mode (jb_cut_*_search): the expanded spans and the pass's workspace, allocated by the
+    // first search call and again whenever the workspace grows (ensure_search)
+    SearchOut srch{};
+    uint64_t srch_gen = 0;  // work_gen they were sized for
     uint8_t* text = nullptr;   // staging for host batches (padded)
     uint64_t* doc_off = nullptr;
     uint64_t text_cap = 0;
@@ -220,10 +224,13 @@ struct Device {
     struct GraphKey {
         const void* text; uint64_t nbytes; const void* doc_off; uint32_t ndocs; bool hmm;
         uint64_t work_gen; hipStream_t stream; const void* out_s; const void* out_e; const void* out_d;
+        // search mode: the pass's outputs (all null for a plain run)
+        bool search; const void* so_s; const void* so_e; const void* so_d; const void* so_n;
         bool operator==(const GraphKey& o) const {
             return text == o.text && nbytes == o.nbytes && doc_off == o.doc_off && ndocs == o.ndocs &&
                    hmm == o.hmm && work_gen == o.work_gen && stream == o.stream && out_s == o.out_s &&
-                   out_e == o.out_e && out_d == o.out_d;
+                   out_e == o.out_e && out_d == o.out_d && search == o.search && so_s == o.so_s &&
+                   so_e == o.so_e && so_d == o.so_d && so_n == o.so_n;
         }
     } gkey{};
     hipGraphExec_t gexec = nullptr;  // captured for gkey (null until the key repeats)
@@ -232,6 +239,17 @@ struct Device {
     // launch that failed part way.  Pipelines leave it all zeros (k_docbits, k_nonzh).
     bool docbits_dirty = true;
     uint64_t gkey_gen = 0;
+    // the same for search mode, so that plain and search calls on the same buffers each keep
+    // their captured graph
+    GraphKey gkey_s{};
+    hipGraphExec_t gexec_s = nullptr;
+    uint64_t gkey_gen_s = 0;
+    void drop_graphs() {
+        if (gexec) (void)hipGraphExecDestroy(gexec);
+        if (gexec_s) (void)hipGraphExecDestroy(gexec_s);
+        gexec = gexec_s = nullptr;
+        gkey_gen = gkey_gen_s = 0;
+    }
 };
 
 void dfree(void* p) {
@@ -578,9 +596,7 @@ static int install_image(Device* d, ImageBufs* b, const Image& img) {
     for (double w : img.wtab)
         if (std::isnan(w) || w == HUGE_VAL) d->dim.plainw = 0u;  // (a dictionary size <= 0)
     // a captured pipeline holds the old image pointers in its kernel arguments
-    if (d->gexec) (void)hipGraphExecDestroy(d->gexec);
-    d->gexec = nullptr;
-    d->gkey_gen = 0;
+    d->drop_graphs();
     return JB_OK;
 }
 
@@ -599,8 +615,7 @@ static int ensure_work(Device* d, uint64_t nbytes, uint32_t ndocs) {
     const uint64_t nb = std::max<uint64_t>(std::max(nbytes, w.cap_bytes), 4096);
     const uint32_t ndc = std::max(std::max(ndocs, w.cap_docs), 1024u);
     free_work(&w);
-    if (d->gexec) (void)hipGraphExecDestroy(d->gexec);
-    d->gexec = nullptr;
+    d->drop_graphs();
     d->work_gen++;
     const uint64_t nwords = (nb + 31) / 32 + 8;
     const uint64_t ntiles = (nb + kTileBytes - 1) / kTileBytes + 1;
@@ -642,6 +657,30 @@ static int ensure_work(Device* d, uint64_t nbytes, uint32_t ndocs) {
     w.cap_bytes = nb;
     w.cap_docs = ndc;
     d->docbits_dirty = true;
+    return JB_OK;
+}
+
+static void free_search(Device* d) {
+    SearchOut& so = d->srch;
+    dfree(so.start); dfree(so.end); dfree(so.doc_tok); dfree(so.off); dfree(so.tile); dfree(so.sup);
+    so = SearchOut{};
+}
+
+// The search pass's buffers, sized like the workspace's spans (after ensure_work).  A context
+// that never cuts in search mode never gets here.
+static int ensure_search(Device* d) {
+    SearchOut& so = d->srch;
+    if (so.off && d->srch_gen == d->work_gen) return JB_OK;
+    free_search(d);
+    const uint64_t nb = d->w.cap_bytes, ntt = srch_tiles(nb);
+    HIPCHK(hipMalloc(&so.start, (nb + 4) * 4));
+    HIPCHK(hipMalloc(&so.end, (nb + 4) * 4));
+    HIPCHK(hipMalloc(&so.doc_tok, ((uint64_t)d->w.cap_docs + 2) * 8));
+    HIPCHK(hipMalloc(&so.off, (nb + 4) * 4));
+    HIPCHK(hipMalloc(&so.tile, (ntt + 1) * sizeof(uint2)));
+    HIPCHK(hipMalloc(&so.sup, (ntt / 256 + 2) * sizeof(uint2)));
+    so.ntok = reinterpret_cast<uint64_t*>(d->w.counters + CNT_NSRCH);
+    d->srch_gen = d->work_gen;
     return JB_OK;
 }
 
@@ -769,19 +808,23 @@ static int init_launch_cfg(Device* d) {
 }
 
 static int launch_pipeline_(Device* d, const Work& w, const uint8_t* d_text, uint64_t nbytes,
-                            const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask);
+                            const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask,
+                            const SearchOut* so);
 static int launch_pipeline(Device* d, const Work& w, const uint8_t* d_text, uint64_t nbytes,
-                           const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask) {
+                           const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask,
+                           const SearchOut* so) {
     if (d->docbits_dirty) {  // the whole bitmap, once (see Device::docbits_dirty)
         HIPCHK(run_zero(w.docbits, w.bits_stride * 4, s));
         d->docbits_dirty = false;
     }
-    const int rc = launch_pipeline_(d, w, d_text, nbytes, d_doc_off, ndocs, hmm, s, mask);
+    const int rc = launch_pipeline_(d, w, d_text, nbytes, d_doc_off, ndocs, hmm, s, mask, so);
     if (rc) d->docbits_dirty = true;
     return rc;
 }
+// so != nullptr: search mode, the search pass (run_search) follows the pipeline's kernels
 static int launch_pipeline_(Device* d, const Work& w, const uint8_t* d_text, uint64_t nbytes,
-                            const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask) {
+                            const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask,
+                            const SearchOut* so) {
     static const bool dbg = getenv("JB_DEBUG") != nullptr;
     const LaunchCfg& lc = d->lc;
     d->last_nbytes = nbytes;
@@ -793,40 +836,48 @@ static int launch_pipeline_(Device* d, const Work& w, const uint8_t* d_text, uin
         fprintf(stderr, "[jb] nbytes=%llu ndocs=%u zh_waves=%u/%u wide=%d zh_group=%u\n", (unsigned long long)nbytes,
                 ndocs, lc.zh_waves, lc.zh_waves_wide, lc.zh_wide, lc.zh_group ? lc.zh_group : zh_group_for(nbytes));
     static const bool use_graph = env_int("JB_GRAPH", 1) != 0;
+    auto run = [&](KernelTimer* tm) {  // the pipeline's kernels, then search mode's
+        hipError_t e = run_pipeline(d->dim, w, d_text, nbytes, d_doc_off, ndocs, hmm, lc, s, tm, mask);
+        if (e == hipSuccess && so) e = run_search(d->dim, w, *so, d_text, nbytes, ndocs, s, tm);
+        return e;
+    };
     if (use_graph && !d->profile && lc.diag == 0 && s != nullptr && !mask) {
-        const Device::GraphKey key{d_text, nbytes, d_doc_off, ndocs, hmm, d->work_gen, s, w.tok_start, w.tok_end, w.doc_tok};
-        const bool repeat = d->gkey_gen != 0 && key == d->gkey;
+        const Device::GraphKey key{d_text, nbytes, d_doc_off, ndocs, hmm, d->work_gen, s, w.tok_start, w.tok_end,
+                                   w.doc_tok, so != nullptr, so ? so->start : nullptr, so ? so->end : nullptr,
+                                   so ? (const void*)so->doc_tok : nullptr, so ? (const void*)so->ntok : nullptr};
+        // (each mode has its own slot)
+        Device::GraphKey& gkey = so ? d->gkey_s : d->gkey;
+        hipGraphExec_t& gexec = so ? d->gexec_s : d->gexec;
+        uint64_t& gkey_gen = so ? d->gkey_gen_s : d->gkey_gen;
+        const bool repeat = gkey_gen != 0 && key == gkey;
         if (!repeat) {  // first call with this key: run directly, capture if it comes again
-            if (d->gexec) (void)hipGraphExecDestroy(d->gexec);
-            d->gexec = nullptr;
-            d->gkey = key;
-            d->gkey_gen = 1;
-            const hipError_t e = run_pipeline(d->dim, w, d_text, nbytes, d_doc_off, ndocs, hmm, lc, s, nullptr);
+            if (gexec) (void)hipGraphExecDestroy(gexec);
+            gexec = nullptr;
+            gkey = key;
+            gkey_gen = 1;
+            const hipError_t e = run(nullptr);
             if (e != hipSuccess) return fail(JB_EDEVICE, "pipeline launch: %s", hipGetErrorString(e));
             return JB_OK;
         }
-        if (!d->gexec) {
-            if (d->gexec) (void)hipGraphExecDestroy(d->gexec);
-            d->gexec = nullptr;
+        if (!gexec) {
             hipGraph_t g = nullptr;
             HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            const hipError_t ec = run_pipeline(d->dim, w, d_text, nbytes, d_doc_off, ndocs, hmm, lc, s, nullptr);
+            const hipError_t ec = run(nullptr);
             const hipError_t ee = hipStreamEndCapture(s, &g);
             if (ec != hipSuccess) return fail(JB_EDEVICE, "pipeline capture: %s", hipGetErrorString(ec));
             if (ee != hipSuccess) return fail(JB_EDEVICE, "pipeline capture end: %s", hipGetErrorString(ee));
-            const hipError_t ei = hipGraphInstantiate(&d->gexec, g, nullptr, nullptr, 0);
+            const hipError_t ei = hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0);
             (void)hipGraphDestroy(g);
             if (ei != hipSuccess) {
-                d->gexec = nullptr;
+                gexec = nullptr;
                 return fail(JB_EDEVICE, "pipeline graph instantiate: %s", hipGetErrorString(ei));
             }
         }
-        const hipError_t el = hipGraphLaunch(d->gexec, s);
+        const hipError_t el = hipGraphLaunch(gexec, s);
         if (el != hipSuccess) return fail(JB_EDEVICE, "pipeline graph launch: %s", hipGetErrorString(el));
         return JB_OK;
     }
-    const hipError_t e = run_pipeline(d->dim, w, d_text, nbytes, d_doc_off, ndocs, hmm, lc, s,
-                                      d->profile ? &d->timer : nullptr, mask);
+    const hipError_t e = run(d->profile ? &d->timer : nullptr);
     if (e != hipSuccess) return fail(JB_EDEVICE, "pipeline launch: %s", hipGetErrorString(e));
     if ((lc.diag & 0x100u) && d->w.dbg) {  // diagnostic: per-wave clocks of k_zh (STAMPS builds)
         const uint32_t nwv = std::min<uint32_t>(std::max(lc.zh_waves, lc.zh_waves_wide), 16384u);
@@ -920,10 +971,11 @@ static int launch_pipeline_(Device* d, const Work& w, const uint8_t* d_text, uin
 // for the previous one (on whatever stream it ran) before it starts.  `w` is the
 // device's workspace, or a copy with caller-owned outputs (jb_cut_device_into).
 static int launch(Device* d, const Work& w, const uint8_t* d_text, uint64_t nbytes, const uint64_t* d_doc_off,
-                  uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask = nullptr) {
+                  uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask = nullptr,
+                  const SearchOut* so = nullptr) {
     if (!d->ws_done) HIPCHK(hipEventCreateWithFlags(&d->ws_done, hipEventDisableTiming));
     else HIPCHK(hipStreamWaitEvent(s, d->ws_done, 0));  // (free on the stream that recorded it)
-    int rc = launch_pipeline(d, w, d_text, nbytes, d_doc_off, ndocs, hmm, s, mask);
+    int rc = launch_pipeline(d, w, d_text, nbytes, d_doc_off, ndocs, hmm, s, mask, so);
     if (rc) return rc;
     HIPCHK(hipEventRecord(d->ws_done, s));
     d->ws_stream = s;
@@ -1044,9 +1096,9 @@ extern "C" void jb_close(jb_ctx* ctx) {
         // wait for its completion event before freeing anything (the caller's stream may be
         // gone by now, the event is ours)
         if (d->ws_done) (void)hipEventSynchronize(d->ws_done);
-        if (d->gexec) (void)hipGraphExecDestroy(d->gexec);
-        d->gexec = nullptr;
+        d->drop_graphs();
         free_work(&d->w);
+        free_search(d.get());
         dfree(d->text); dfree(d->doc_off);
         free_image_bufs(&d->ib);
         if (d->ws_done) (void)hipEventDestroy(d->ws_done);
@@ -1596,8 +1648,10 @@ static bool host_pinned(const void* p, uint64_t n) {
 // staged into pinned memory and copied up on cstream while piece k's kernels run on
 // `stream` and piece k-1's spans (or final mask words) come back on dstream, then are
 // widened to u64 batch offsets into `out` by kCopyThreads host threads.
+// search: search mode (jb_cut_batch_search).  Such a range always takes the pipeline, and its spans come
+// back unpacked: they overlap, and k_span_pack's gap coding wants ascending disjoint spans.
 static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, uint32_t d0, uint32_t d1, bool hmm,
-                     SpanBuf* out, const MaskDst* mask) {
+                     SpanBuf* out, const MaskDst* mask, bool search = false) {
     if (d0 >= d1) return JB_OK;
     const uint64_t r0 = doc_off[d0], rbytes = doc_off[d1] - r0;
     const uint32_t ndr = d1 - d0;
@@ -1607,7 +1661,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
     int rc;
     // (small batches: k_small on its own stream and buffers, coalesced across callers, without
     // the device lock that the pipeline below holds)
-    if (d->lc.small_max && rbytes <= d->lc.small_max && ndr <= kSmallDocs) {
+    if (!search && d->lc.small_max && rbytes <= d->lc.small_max && ndr <= kSmallDocs) {
         if (!mask) return cut_small(d, text, doc_off + d0, ndr, hmm, out);
         SpanBuf tmp;
         if ((rc = cut_small(d, text, doc_off + d0, ndr, hmm, &tmp))) {
@@ -1653,7 +1707,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         (rc = grow_pinned(&d->h_misc, &d->h_misc_cap, slots)) ||
         (rc = grow_mapped(&d->h_pcnt, &d->d_pcnt, &d->h_pcnt_cap, (uint64_t)np * kSnapWords)) ||
         (!pinned_in && (rc = grow_pinned(&d->h_text, &d->h_text_cap, dev_bytes))) ||
-        (rc = ensure_work(d, maxb, maxd)))
+        (rc = ensure_work(d, maxb, maxd)) || (search && (rc = ensure_search(d))))
         return rc;
     for (auto* v : {&d->ev_h2d, &d->ev_comp, &d->ev_d2h})
         while (v->size() < np) {
@@ -1661,7 +1715,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
             HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             v->push_back(e);
         }
-    const bool pack = !mask && d->span_pack;
+    const bool pack = !mask && !search && d->span_pack;
     const uint32_t side_cap = pack_side_cap(maxb);
     if (!mask) {
         for (auto& o : d->outs) {
@@ -1691,7 +1745,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         (void)hipStreamSynchronize(d->dstream);
         return code;
     };
-    std::vector<uint32_t> ntok(np, 0);
+    std::vector<uint32_t> ntok(np, 0);  // spans each piece returns (search mode: the expanded count)
     std::vector<std::pair<uint64_t, uint64_t>> words(np);  // mask words each piece copies back
     static const bool tdbg2 = env_int("JB_DEBUG", 0) >= 2;  // per-piece event clocks
     std::vector<hipEvent_t> tev;  // t0, then per piece: H2D done, kernels done, results back
@@ -1751,18 +1805,25 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         HIPCHK(hipStreamWaitEvent(d->stream, d->ev_h2d[k], 0));
         Work w = d->w;
         MaskOut mo{nullptr, nullptr, 0};
+        SearchOut so = d->srch;
         if (mask) {
             mo = MaskOut{d->d_mask, d->d_mask + nw, rsh + (pb - r0)};
         } else {
             if (k >= (size_t)Device::kSets) HIPCHK(hipStreamWaitEvent(d->stream, d->ev_d2h[k - Device::kSets], 0));
             const Device::OutSet& o = d->outs[k % Device::kSets];
-            w.tok_start = o.ts;
-            w.tok_end = o.te;
-            w.doc_tok = o.dt;
+            if (search) {  // the plain spans stay in the workspace, the expanded ones go to the output set
+                so.start = o.ts;
+                so.end = o.te;
+                so.doc_tok = o.dt;
+            } else {
+                w.tok_start = o.ts;
+                w.tok_end = o.te;
+                w.doc_tok = o.dt;
+            }
         }
         int r;
         if ((r = launch(d, w, d->text + p.off, len, d->doc_off + p.slot, p.d1 - p.d0, hmm, d->stream,
-                        mask ? &mo : nullptr)))
+                        mask ? &mo : nullptr, search ? &so : nullptr)))
             return r;
         d->last_nbytes = len;
         if (pack) {  // the spans packed for the trip back: 4 B per token (k_span_pack)
@@ -1788,7 +1849,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         if (c[CNT_ERR]) return fail(JB_EPANIC, "a Han block has no DAG path (the reference panics in cutDAG)");
         if (c[CNT_NTOK] != c[CNT_NTOKE])
             return fail(JB_EDEVICE, "internal: %u token starts vs %u ends", c[CNT_NTOK], c[CNT_NTOKE]);
-        const uint32_t nt = ntok[k] = c[CNT_NTOK];
+        const uint32_t nt = ntok[k] = search ? c[CNT_NSRCH] : c[CNT_NTOK];
         HIPCHK(hipStreamWaitEvent(d->dstream, d->ev_comp[k], 0));
         if (!mask) {
             Device::OutSet& o = d->outs[k % Device::kSets];
@@ -1838,7 +1899,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         const uint32_t nt = ntok[k];
         {
             const volatile uint32_t* c = d->h_pcnt + k * kSnapWords;
-            acc.tokens += nt;
+            acc.tokens += c[CNT_NTOK];  // (the Cut tokens, in search mode too)
             acc.long_blocks += c[CNT_NLONG];
             acc.viterbi_ties += c[CNT_TIES];
             acc.blocks += (uint64_t)c[CNT_CLEAR] | (uint64_t)c[CNT_CLEAR + 1] << 32;
@@ -2134,7 +2195,7 @@ struct Units {
 // cuts, exclusive inside jb_add_word).
 static int cut_sharded(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
                        std::vector<SpanBuf>* sbp, const MaskDst* mask = nullptr,
-                       std::vector<uint32_t>* unit_doc = nullptr) {
+                       std::vector<uint32_t>* unit_doc = nullptr, bool search = false) {
     if (ndocs && !text && doc_off[ndocs] > doc_off[0]) return fail(JB_EINVAL, "null text");
     for (uint32_t k = 0; k < ndocs; k++)
         if (doc_off[k + 1] < doc_off[k]) return fail(JB_EINVAL, "doc_off not monotonic at %u", k);
@@ -2207,7 +2268,7 @@ static int cut_sharded(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off
     auto work = [&](size_t k) {
         const uint32_t u0 = split ? un.dev[k] : (k == 0 ? 0u : ndocs), u1 = split ? un.dev[k + 1] : ndocs;
         if (u0 < u1) {
-            rcs[k] = cut_range(ctx->devs[k].get(), text, uoff, u0, u1, hmm != 0, &sb[k], mask);
+            rcs[k] = cut_range(ctx->devs[k].get(), text, uoff, u0, u1, hmm != 0, &sb[k], mask, search);
             if (rcs[k]) errs[k] = g_err;
         }
     };
@@ -2239,14 +2300,14 @@ static void fill_doc_tok(const std::vector<SpanBuf>& sb, uint32_t ndocs, uint64_
 
 // jb_cut_batch with ctx->lock already held by the caller.
 static int cut_batch_locked(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                            jb_spans* out) {
+                            jb_spans* out, bool search = false) {
     const size_t nd = ctx->devs.size();
     std::vector<SpanBuf> sb(nd);
     auto release_all = [&] {
         for (auto& b : sb) b.release();
     };
     std::vector<uint32_t> unit_doc;
-    int rc = cut_sharded(ctx, text, doc_off, ndocs, hmm, &sb, nullptr, &unit_doc);
+    int rc = cut_sharded(ctx, text, doc_off, ndocs, hmm, &sb, nullptr, &unit_doc, search);
     if (rc) {
         release_all();
         return rc;
@@ -2290,6 +2351,14 @@ extern "C" int jb_cut_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* do
     memset(out, 0, sizeof *out);
     std::shared_lock<std::shared_mutex> rl(ctx->lock);
     return cut_batch_locked(ctx, text, doc_off, ndocs, hmm, out);
+}
+
+extern "C" int jb_cut_batch_search(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                                   jb_spans* out) {
+    if (!ctx || !out || (!doc_off && ndocs)) return fail(JB_EINVAL, "jb_cut_batch_search: null argument");
+    memset(out, 0, sizeof *out);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    return cut_batch_locked(ctx, text, doc_off, ndocs, hmm, out, true);
 }
 
 extern "C" int jb_cut_batch_into(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs,
@@ -2452,6 +2521,12 @@ extern "C" int jb_cut(jb_ctx* ctx, const uint8_t* text, size_t len, int hmm, jb_
     return jb_cut_batch(ctx, text ? text : empty, off, 1, hmm, out);
 }
 
+extern "C" int jb_cut_search(jb_ctx* ctx, const uint8_t* text, size_t len, int hmm, jb_spans* out) {
+    const uint64_t off[2] = {0, (uint64_t)len};
+    static const uint8_t empty[1] = {0};
+    return jb_cut_batch_search(ctx, text ? text : empty, off, 1, hmm, out);
+}
+
 extern "C" void jb_spans_free(jb_spans* s) {
     if (!s) return;
     free(s->start);
@@ -2462,7 +2537,8 @@ extern "C" void jb_spans_free(jb_spans* s) {
 
 static int cut_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint64_t* d_doc_off,
                       uint32_t ndocs, int hmm, void* stream, uint32_t* o_start, uint32_t* o_end, uint64_t* o_doc_tok,
-                      uint64_t* o_ntok, uint32_t** d_start, uint32_t** d_end, uint64_t** d_doc_tok, uint64_t** d_ntok) {
+                      uint64_t* o_ntok, uint32_t** d_start, uint32_t** d_end, uint64_t** d_doc_tok, uint64_t** d_ntok,
+                      bool search = false) {
     if (!ctx || (!d_text && nbytes) || !d_doc_off) return fail(JB_EINVAL, "jb_cut_device: null argument");
     if (nbytes >= (1ull << 31)) return fail(JB_ELIMIT, "device batch of %llu bytes (limit 2 GiB)",
                                             (unsigned long long)nbytes);
@@ -2478,6 +2554,22 @@ static int cut_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const
     int rc;
     if ((rc = ensure_work(d, nbytes, ndocs))) return rc;
     const hipStream_t s = (hipStream_t)stream;
+    if (search) {  // the plain spans in the workspace, the expanded ones in the search buffers or the caller's arrays
+        if ((rc = ensure_search(d))) return rc;
+        SearchOut so = d->srch;
+        if (o_start) {
+            so.start = o_start;
+            so.end = o_end;
+            so.doc_tok = o_doc_tok;
+            so.ntok = o_ntok;
+        }
+        if ((rc = launch(d, d->w, d_text, nbytes, d_doc_off, ndocs, hmm != 0, s, nullptr, &so))) return rc;
+        if (d_start) *d_start = so.start;
+        if (d_end) *d_end = so.end;
+        if (d_doc_tok) *d_doc_tok = so.doc_tok;
+        if (d_ntok) *d_ntok = so.ntok;
+        return JB_OK;
+    }
     if (o_start) {  // caller-owned outputs: the pipeline writes its spans and offsets there
         Work w = d->w;
         w.tok_start = o_start;
@@ -2511,6 +2603,24 @@ extern "C" int jb_cut_device_into(jb_ctx* ctx, const uint8_t* d_text, uint64_t n
                                   "has up to n tokens)", (unsigned long long)cap, (unsigned long long)nbytes);
     return cut_device(ctx, d_text, nbytes, d_doc_off, ndocs, hmm, stream, d_start, d_end, d_doc_tok, d_ntok, nullptr,
                       nullptr, nullptr, nullptr);
+}
+
+extern "C" int jb_cut_device_search(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint64_t* d_doc_off,
+                                    uint32_t ndocs, int hmm, void* stream, uint32_t** d_start, uint32_t** d_end,
+                                    uint64_t** d_doc_tok, uint64_t** d_ntok) {
+    return cut_device(ctx, d_text, nbytes, d_doc_off, ndocs, hmm, stream, nullptr, nullptr, nullptr, nullptr, d_start,
+                      d_end, d_doc_tok, d_ntok, true);
+}
+
+extern "C" int jb_cut_device_search_into(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes,
+                                         const uint64_t* d_doc_off, uint32_t ndocs, int hmm, void* stream,
+                                         uint32_t* d_start, uint32_t* d_end, uint64_t cap, uint64_t* d_doc_tok,
+                                         uint64_t* d_ntok) {
+    if (!d_start || !d_end || !d_doc_tok || !d_ntok) return fail(JB_EINVAL, "jb_cut_device_search_into: null output");
+    if (cap < nbytes) return fail(JB_EINVAL, "jb_cut_device_search_into: cap %llu < nbytes %llu (a batch of n bytes "
+                                  "has up to n search-mode spans)", (unsigned long long)cap, (unsigned long long)nbytes);
+    return cut_device(ctx, d_text, nbytes, d_doc_off, ndocs, hmm, stream, d_start, d_end, d_doc_tok, d_ntok, nullptr,
+                      nullptr, nullptr, nullptr, true);
 }
 
 // ---------------------------------------------------------------------------

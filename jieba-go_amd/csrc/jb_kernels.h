@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "jb_common.h"
 
 namespace jb {
@@ -33,6 +35,7 @@ struct DevImage {
 
 // Device counters (u32 slots unless noted)
 enum {
+    CNT_NSRCH = 0,  // u64 at u32 slots 0-1: spans of the search-mode expansion (run_search; 0 after a plain run)
     CNT_NTOK = 2,   // token starts
     CNT_NTOKE = 3,  // token ends (== CNT_NTOK when consistent)
     CNT_ERR = 4,    // bit 0: a zh block reached a tail index -1 (the reference panics); bit 1: a k_long
@@ -115,7 +118,7 @@ struct Work {
 enum KernelId {
     K_DOCBITS = 0, K_MARK_WALK, K_ZH, K_NONZH,
     K_TOK_COUNT, K_SCAN_TOK, K_TOK_WRITE, K_DOC_TOK, K_LONG_SPEC, K_LONG_DP, K_LONG_SEG, K_LONG_PATH, K_LONG_TAIL, K_MASK_MERGE,
-    K_LONG_PBITS, K_LONG, K_TOK1,
+    K_LONG_PBITS, K_LONG, K_TOK1, K_SRCH_COUNT, K_SRCH_SCAN, K_SRCH_WRITE, K_SRCH_DOC,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -180,6 +183,28 @@ struct MaskOut {
 hipError_t run_pipeline(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes,
                         const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, const LaunchCfg& lc,
                         hipStream_t stream, KernelTimer* timer, const MaskOut* mask = nullptr);
+
+// Search mode (jb_cut_*_search): the spans of a finished run_pipeline, expanded.  Every Han token
+// of three or more runes is preceded by the dictionary words of two runes inside it, then (four
+// or more runes) those of three runes, each in text order; every other token stays as it is.
+// Token tile = kSrchTile consecutive tokens, one workgroup each.
+constexpr uint32_t kSrchPer = 16;                  // tokens per thread
+constexpr uint32_t kSrchTile = 256u * kSrchPer;    // tokens per workgroup
+inline uint64_t srch_tiles(uint64_t nbytes) { return std::max<uint64_t>(1u, (nbytes + kSrchTile - 1u) / kSrchTile); }
+struct SearchOut {
+    uint32_t* start;    // expanded spans (at least nbytes entries: a token gives at most as many spans as it has bytes)
+    uint32_t* end;
+    uint64_t* doc_tok;  // ndocs + 1: document d's spans are [doc_tok[d], doc_tok[d+1])
+    uint64_t* ntok;     // the expanded count (also left in the counters, CNT_NSRCH)
+    // workspace
+    uint32_t* off;      // per plain token: its span count (k_srch_count), then its first span (k_srch_write)
+    uint2* tile;        // per token tile: (spans, 0); srch_tiles(nbytes) entries
+    uint2* sup;         // per 256 token tiles: their sum (k_sup)
+};
+// Enqueue the search pass on `stream`, after run_pipeline's kernels for the same batch (w.tok_start /
+// w.tok_end / w.doc_tok hold its plain spans, w.erec its DAG records).
+hipError_t run_search(const DevImage& im, const Work& w, const SearchOut& so, const uint8_t* d_text, uint64_t nbytes,
+                      uint32_t ndocs, hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

@@ -41,7 +41,8 @@ namespace jb {
 
 const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_nonzh", "k_tok_count", "k_scan_tok",
                                          "k_tok_write", "k_doc_tok", "k_long_spec", "k_long_dp", "k_long_seg", "k_long_path",
-                                         "k_long_tail", "k_mask_merge", "k_long_pbits", "k_long", "k_tok1"};
+                                         "k_long_tail", "k_mask_merge", "k_long_pbits", "k_long", "k_tok1", "k_srch_count",
+                                         "k_srch_scan", "k_srch_write", "k_srch_doc"};
 
 // newJiebaHMM literals (tokenizer.go:629-652)
 #define START_B (-0.26268660809250016)
@@ -5909,6 +5910,274 @@ hipError_t run_pipeline(const DevImage& im, const Work& w, const uint8_t* d_text
     else
         JB_TIMED(K_DOC_TOK, hipLaunchKernelGGL(k_doc_tok<16>, dim3((16u * (ndocs + 1) + 255) / 256), dim3(256), 0,
                                                stream, d_doc_off, ndocs, w.tok_start, w.counters, w.doc_tok));
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Search mode (jieba's cut_for_search on this reference's DAG): a pass over the
+// spans of a finished run.  For a Han token of n runes at bytes p_0 < ... < p_n:
+// n > 2: [p_i, p_i+2) for every i with a 2-rune edge in buildDag's DAG of the
+// token, ascending; n > 3: then [p_i, p_i+3) likewise; then the token.  Every
+// other token is copied.  An edge of rune i is read from its record erec[p_i / 3]
+// (k_mark_walk: bit L-1 of the mask = an edge of L runes; the record was built on
+// the whole Han run, so the caller keeps only grams that end inside the token); a
+// zero record (overflowed, or DevImage::plainw == 0) is answered by two trie steps
+// with dp_walk_rune's rules.  Nearly every token takes the fast form (srch_masks): no 4-byte rune
+// near it, so its runes and records sit at fixed strides and all its loads are issued at once.
+// Three launches, no waits between workgroups: k_srch_count (spans per token and
+// per tile of kSrchTile tokens), k_sup over the tile sums, k_srch_write (the tile's
+// prefix as k_tok's write pass finds it, pf_load / pf_sum; the spans); then
+// k_srch_doc maps doc_tok through the offsets.
+// Thread t of a tile owns tokens j * 256 + t (j < kSrchPer): every load and
+// store of the token arrays is coalesced, and the scan runs over (j, t) in that order.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kSrchNone = 0xFFFFFFFFu;
+// the byte after the Han rune at p, or kSrchNone when no whole rune starts at p inside [.., e)
+__device__ __forceinline__ uint32_t srch_next(const uint8_t* __restrict__ text, uint32_t p, uint32_t e) {
+    if (p >= e) return kSrchNone;  // (also p == kSrchNone)
+    const uint32_t q = p + (text[p] >= 0xF0u ? 4u : 3u);
+    return q <= e ? q : kSrchNone;
+}
+__device__ __forceinline__ uint32_t srch_rune(const uint8_t* __restrict__ text, uint32_t p) {  // valid UTF-8, 3 or 4 bytes
+    const uint32_t x = ld4(text, p), b0 = x & 0xFFu;
+    const uint32_t r3 = ((b0 & 0x0Fu) << 12) | (((x >> 8) & 0x3Fu) << 6) | ((x >> 16) & 0x3Fu);
+    const uint32_t r4 = ((b0 & 0x07u) << 18) | (((x >> 8) & 0x3Fu) << 12) | (((x >> 16) & 0x3Fu) << 6) | (x >> 24);
+    return b0 >= 0xF0u ? r4 : r3;
+}
+// bit 0: E(i, 2), bit 1: E(i, 3) for the rune at a, whose next two runes start at b and (third
+// == true) at c, all inside the token.  rc: the rune's record.
+__device__ __forceinline__ uint32_t srch_edges(const uint8_t* __restrict__ text, const DevImage& im, uint64_t rc,
+                                               uint32_t a, uint32_t b, uint32_t c, bool third) {
+    if (rc) return (uint32_t)(rc >> 1) & 3u;
+    const uint32_t r0 = srch_rune(text, a), r1 = srch_rune(text, b);
+    if (r0 >= 0x110000u || r1 >= 0x110000u) return 0u;  // (not in a Han token)
+    const uint32_t id = rune_code(im, r0);
+    const uint64_t cc = im.cells[id];
+    if (jb_cell_check(cc) != JB_CHECK_ROOT || jb_cell_fc(cc) == JB_FC_ZERO || !jb_cell_hc(cc)) return 0u;
+    const uint32_t t1 = dat_slot(im, cc, r1);
+    const uint64_t c1 = im.cells[t1];
+    if (!dat_hit(c1, id)) return 0u;
+    uint32_t m = jb_cell_fc(c1) == JB_FC_POS ? 1u : 0u;
+    if (third && jb_cell_hc(c1)) {
+        const uint32_t r2 = srch_rune(text, c);
+        if (r2 < 0x110000u) {
+            const uint32_t t2 = dat_slot(im, c1, r2);
+            const uint64_t c2 = im.cells[t2];
+            if (dat_hit(c2, t1) && jb_cell_fc(c2) == JB_FC_POS) m |= 2u;
+        }
+    }
+    return m;
+}
+// Does a token of at least nine bytes (three runes) whose first four bytes are x start with a Han rune?
+__device__ __forceinline__ bool srch_han(uint32_t x) {
+    uint32_t w;
+    return (x & 0x80u) != 0u && han_rune(x, 4u, &w) != 0u;
+}
+// The fast form.  A token whose tiles hold no 4-byte Han rune (tile4) has rune i at s + 3 i and its
+// records at consecutive slots, so no load waits for another: the edges of its runes as two masks,
+// bit i of m2 = E(i, 2) (i <= n - 2), bit i of m3 = E(i, 3) (n > 3, i <= n - 3).  han: the token starts
+// with a Han rune (the caller's load; only then may a zero record be walked).  False: the token has more
+// than kSrchFastN runes or may hold a 4-byte rune, and takes the general form (srch_grams).
+constexpr uint32_t kSrchFastN = 32;
+__device__ __forceinline__ bool srch_masks(const uint8_t* __restrict__ text, const DevImage& im,
+                                           const uint64_t* __restrict__ erec, const uint32_t* __restrict__ tile4,
+                                           uint32_t s, uint32_t e, bool han, uint32_t& m2, uint32_t& m3) {
+    const uint32_t n = (e - s) / 3u;
+    if (n * 3u != e - s || n > kSrchFastN) return false;
+    const bool all3 = (tile4[s / kTileBytes] | tile4[(e - 1u) / kTileBytes]) == 0u;
+    const uint64_t* const rp = erec + s / 3u;
+    uint32_t a2 = 0, a3 = 0;
+    for (uint32_t i = 0; i + 1u < n; i += 4u) {  // runes i .. i+3 of 0 .. n-2
+        uint64_t r[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) r[k] = rp[i + k];  // (slots past the last rune are read and dropped)
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            const uint32_t q = i + k, a = s + 3u * q;
+            if (q + 1u < n) {
+                uint32_t m = (uint32_t)(r[k] >> 1) & 3u;
+                if (r[k] == 0ull) m = han && all3 ? srch_edges(text, im, 0ull, a, a + 3u, a + 6u, q + 2u < n) : 0u;
+                a2 |= (m & 1u) << q;
+                a3 |= (m >> 1) << q;
+            }
+        }
+    }
+    m2 = a2;
+    m3 = n > 3u ? a3 & ((1u << (n - 2u)) - 1u) : 0u;
+    return all3;
+}
+// The grams of one length (L = 2, 3) or both (L = 0) of the Han token [s, e), in text order:
+// f(L, from, to).  A token of n runes has 2-grams when n > 2 and 3-grams when n > 3.
+template <uint32_t L, class F>
+__device__ __forceinline__ void srch_grams(const uint8_t* __restrict__ text, const DevImage& im,
+                                           const uint64_t* __restrict__ erec, uint32_t s, uint32_t e, F&& f) {
+    uint32_t a = s, b = srch_next(text, a, e), c = srch_next(text, b, e), d = srch_next(text, c, e);
+    if (c == kSrchNone || c >= e) return;  // n <= 2
+    const bool n3 = d != kSrchNone && d < e;  // n > 3
+    if (L == 3u && !n3) return;
+    while (c != kSrchNone) {  // the rune at a has a next rune [b, c)
+        const uint32_t m = srch_edges(text, im, erec[a / 3u], a, b, c, d != kSrchNone);
+        if (L != 3u && (m & 1u)) f(2u, a, c);
+        if (L != 2u && n3 && (m & 2u) && d != kSrchNone) f(3u, a, d);
+        a = b;
+        b = c;
+        c = d;
+        d = srch_next(text, d, e);
+    }
+}
+
+// (96 SGPRs at most: the image's pointers would otherwise cost the eighth wave per SIMD)
+#define JB_SRCH_ATTR __attribute__((amdgpu_num_sgpr(96)))
+__global__ __launch_bounds__(256) JB_SRCH_ATTR void k_srch_count(const uint8_t* __restrict__ text, DevImage im,
+                                                    const uint64_t* __restrict__ erec,
+                                                    const uint32_t* __restrict__ ts, const uint32_t* __restrict__ te,
+                                                    const uint32_t* __restrict__ counters, uint32_t* __restrict__ off,
+                                                    uint2* __restrict__ tile, const uint32_t* __restrict__ tile4) {
+    __shared__ uint32_t lds[8];
+    const uint32_t n = counters[CNT_NTOK], i0 = blockIdx.x * kSrchTile + threadIdx.x;
+    uint32_t sum = 0;
+    if (blockIdx.x * kSrchTile < n) {
+        uint32_t s1 = 0, e1 = 0;  // the next token's span, loaded one trip ahead
+        if (i0 < n) {
+            s1 = ts[i0];
+            e1 = te[i0];
+        }
+        for (uint32_t j = 0; j < kSrchPer; j++) {
+            const uint32_t i = i0 + j * 256u;
+            if (i >= n) break;
+            const uint32_t s = s1, e = e1;
+            if (j + 1u < kSrchPer && i + 256u < n) {
+                s1 = ts[i + 256u];
+                e1 = te[i + 256u];
+            }
+            uint32_t cnt = 1u;
+            if (e - s >= 9u) {
+                const bool han = srch_han(ld4(text, s));
+                uint32_t m2, m3;
+                const bool fast = srch_masks(text, im, erec, tile4, s, e, han, m2, m3);
+                if (han && fast) cnt += __popc(m2) + __popc(m3);
+                else if (han) srch_grams<0u>(text, im, erec, s, e, [&](uint32_t, uint32_t, uint32_t) { cnt++; });
+            }
+            off[i] = cnt;
+            sum += cnt;
+        }
+    }
+    const uint2 t = pf_sum(PrefixLoads{sum, 0u}, lds);
+    if (threadIdx.x == 0) tile[blockIdx.x] = make_uint2(t.x, 0u);  // (0 for the tiles past the last token)
+}
+
+__global__ __launch_bounds__(256) JB_SRCH_ATTR void k_srch_write(const uint8_t* __restrict__ text, DevImage im,
+                                                    const uint64_t* __restrict__ erec,
+                                                    const uint32_t* __restrict__ ts, const uint32_t* __restrict__ te,
+                                                    uint32_t* __restrict__ counters, uint32_t* __restrict__ off,
+                                                    const uint2* __restrict__ tile, const uint2* __restrict__ sup,
+                                                    uint32_t* __restrict__ os, uint32_t* __restrict__ oe,
+                                                    uint64_t* ontok, const uint32_t* __restrict__ tile4) {
+    __shared__ uint32_t lds[8];
+    __shared__ uint32_t s_tot[kSrchPer * 4u], s_pre[kSrchPer * 4u];
+    static_assert(kSrchPer * 4u == 64u, "the (row, wave) totals are scanned by one wave");
+    const uint32_t n = counters[CNT_NTOK], t0 = blockIdx.x * kSrchTile, i0 = t0 + threadIdx.x;
+    if (t0 >= n && blockIdx.x != 0u) return;  // (the whole workgroup)
+    const PrefixLoads pl = pf_load(tile, sup, blockIdx.x);
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    uint32_t c[kSrchPer], x[kSrchPer];
+#pragma unroll
+    for (uint32_t j = 0; j < kSrchPer; j++) c[j] = i0 + j * 256u < n ? off[i0 + j * 256u] : 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < kSrchPer; j++) {
+        x[j] = wave_incl_scan(c[j]);
+        if (lane == 63u) s_tot[j * 4u + wid] = x[j];
+    }
+    const uint2 tb = pf_sum(pl, lds);  // (its barriers also publish s_tot)
+    if (threadIdx.x < 64u) {
+        const uint32_t v = s_tot[threadIdx.x];
+        s_pre[threadIdx.x] = wave_incl_scan(v) - v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t j = 0; j < kSrchPer; j++)
+        if (i0 + j * 256u < n) off[i0 + j * 256u] = tb.x + s_pre[j * 4u + wid] + x[j] - c[j];
+    if (threadIdx.x == 0 && t0 + kSrchTile >= n) {  // the last tile: the expanded count
+        const uint64_t tot = (uint64_t)tb.x + s_pre[63] + s_tot[63];
+        *reinterpret_cast<uint64_t*>(counters + CNT_NSRCH) = tot;
+        *ontok = tot;
+    }
+    uint32_t s1 = 0, e1 = 0, k1 = 0;  // the next token's span and offset, loaded one trip ahead
+    if (i0 < n) {
+        s1 = ts[i0];
+        e1 = te[i0];
+        k1 = off[i0];  // (this thread's own store)
+    }
+    for (uint32_t j = 0; j < kSrchPer; j++) {
+        const uint32_t i = i0 + j * 256u;
+        if (i >= n) break;
+        const uint32_t s = s1, e = e1;
+        uint32_t k = k1;
+        if (j + 1u < kSrchPer && i + 256u < n) {
+            s1 = ts[i + 256u];
+            e1 = te[i + 256u];
+            k1 = off[i + 256u];
+        }
+        bool han = false, fast = false;
+        uint32_t m2 = 0, m3 = 0;
+        if (e - s >= 9u) {
+            han = srch_han(ld4(text, s));
+            fast = srch_masks(text, im, erec, tile4, s, e, han, m2, m3);
+        }
+        if (han && fast) {
+            for (; m2; m2 &= m2 - 1u, k++) {
+                const uint32_t a = s + 3u * (uint32_t)__builtin_ctz(m2);
+                os[k] = a;
+                oe[k] = a + 6u;
+            }
+            for (; m3; m3 &= m3 - 1u, k++) {
+                const uint32_t a = s + 3u * (uint32_t)__builtin_ctz(m3);
+                os[k] = a;
+                oe[k] = a + 9u;
+            }
+        } else if (han) {
+            srch_grams<2u>(text, im, erec, s, e, [&](uint32_t, uint32_t a, uint32_t b) {
+                os[k] = a;
+                oe[k] = b;
+                k++;
+            });
+            srch_grams<3u>(text, im, erec, s, e, [&](uint32_t, uint32_t a, uint32_t b) {
+                os[k] = a;
+                oe[k] = b;
+                k++;
+            });
+        }
+        os[k] = s;
+        oe[k] = e;
+    }
+}
+
+// doc_tok of the expanded list: the first span of each document's first token
+__global__ __launch_bounds__(256) void k_srch_doc(const uint64_t* __restrict__ doc_tok, uint32_t ndocs,
+                                                  const uint32_t* __restrict__ counters,
+                                                  const uint32_t* __restrict__ off, uint64_t* __restrict__ out) {
+    const uint32_t d = blockIdx.x * 256u + threadIdx.x;
+    if (d > ndocs) return;
+    const uint64_t t = doc_tok[d];
+    out[d] = t < counters[CNT_NTOK] ? (uint64_t)off[t] : *reinterpret_cast<const uint64_t*>(counters + CNT_NSRCH);
+}
+
+hipError_t run_search(const DevImage& im, const Work& w, const SearchOut& so, const uint8_t* d_text, uint64_t nbytes,
+                      uint32_t ndocs, hipStream_t stream, KernelTimer* timer) {
+    if (nbytes == 0)  // (run_pipeline left the counters and the plain doc_tok all zeros)
+        return run_zero(so.doc_tok, (ndocs + 1) * sizeof(uint64_t), stream, so.ntok, sizeof(uint64_t));
+    const uint32_t ntt = (uint32_t)srch_tiles(nbytes);
+    JB_TIMED(K_SRCH_COUNT, hipLaunchKernelGGL(k_srch_count, dim3(ntt), dim3(256), 0, stream, d_text, im,
+                                              w.erec + kErecPad, w.tok_start, w.tok_end, w.counters, so.off, so.tile,
+                                              w.tile4));
+    if (ntt > 256u)  // (k_srch_write reads the sums of whole groups of 256 tiles only)
+        JB_TIMED(K_SRCH_SCAN, hipLaunchKernelGGL(k_sup, dim3((ntt + 255u) / 256u), dim3(256), 0, stream, so.tile, ntt,
+                                                 so.sup));
+    JB_TIMED(K_SRCH_WRITE, hipLaunchKernelGGL(k_srch_write, dim3(ntt), dim3(256), 0, stream, d_text, im,
+                                              w.erec + kErecPad, w.tok_start, w.tok_end, w.counters, so.off, so.tile,
+                                              so.sup, so.start, so.end, so.ntok, w.tile4));
+    JB_TIMED(K_SRCH_DOC, hipLaunchKernelGGL(k_srch_doc, dim3((ndocs + 1u + 255u) / 256u), dim3(256), 0, stream,
+                                            w.doc_tok, ndocs, w.counters, so.off, so.doc_tok));
     return hipGetLastError();
 }
 

@@ -214,6 +214,34 @@ func (t *Tokenizer) Cut(text string, useHmm bool) []string {
 	return spansToTokens(text, &s, 0)
 }
 
+// CutForSearch is search-engine mode (jieba's cut_for_search; the reference has only Cut):
+// the tokens of Cut, each Han token of three or more runes preceded by the dictionary
+// words of two, then three, runes inside it that buildDag has as edges, in text order
+// (jb_cut_batch_search in jiebahip.h, with its two differences from Python jieba: a gram
+// buildDag cannot see is not emitted, and non-Han tokens are never expanded).  Never
+// returns nil.
+func (t *Tokenizer) CutForSearch(text string, useHmm bool) []string {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	if len(text) == 0 {
+		return []string{}
+	}
+	b := []byte(text)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	off := []uint64{0, uint64(len(b))}
+	var s C.jb_spans
+	if rc := C.jb_cut_batch_search(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+		1, hmm, &s); rc != C.JB_OK {
+		// JB_EPANIC: the reference panics on this input (cutDAG slice with tail -1)
+		panic("jiebahip: " + lastError())
+	}
+	defer C.jb_spans_free(&s)
+	return spansToTokens(text, &s, 0)
+}
+
 // CutParallel (tokenizer.go:81) returns the tokens of Cut in document order.
 // The library splits the work itself: the text goes to the device in pieces cut
 // at Han-run starts (jb_split_points), and over every device of a multi-device

@@ -65,6 +65,16 @@ std::vector<std::string> Tokenizer::Cut(const std::string& text, bool useHmm) {
     return out;
 }
 
+std::vector<std::string> Tokenizer::CutForSearch(const std::string& text, bool useHmm) {
+    jb_spans sp;
+    check(jb_cut_search(ctx_, (const uint8_t*)text.data(), text.size(), useHmm ? 1 : 0, &sp));
+    std::vector<std::string> out;
+    out.reserve(sp.ntokens);
+    for (uint64_t k = 0; k < sp.ntokens; k++) out.push_back(token_at(text, sp.start[k], sp.end[k]));
+    jb_spans_free(&sp);
+    return out;
+}
+
 std::vector<std::string> Tokenizer::CutParallel(const std::string& text, bool hmm, int, bool) {
     return Cut(text, hmm);
 }

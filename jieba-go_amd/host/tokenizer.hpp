@@ -44,6 +44,11 @@ public:
 
     // Cut (tokenizer.go:151)
     std::vector<std::string> Cut(const std::string& text, bool useHmm);
+    // Search-engine mode (jieba's cut_for_search; the reference has only Cut): Cut's tokens,
+    // each Han token of three or more runes preceded by the dictionary words of two, then
+    // three, runes inside it that buildDag has as edges (jb_cut_search in jiebahip.h, with
+    // its two differences from Python jieba).
+    std::vector<std::string> CutForSearch(const std::string& text, bool useHmm);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

@@ -32,6 +32,7 @@ EXPORTS = [
     "jb_profile_reset", "jb_image_build", "jb_image_free", "jb_image_save", "jb_image_dict_info", "jb_image_lookup",
     "jb_image_stats", "jb_image_emit", "jb_go_log", "jb_shard_bounds", "jb_last_stats",
     "jb_suggest_freq", "jb_add_log", "jb_image_log_keys", "jb_device_status", "jb_cut_batch_into32",
+    "jb_cut_search", "jb_cut_batch_search", "jb_cut_device_search", "jb_cut_device_search_into",
 ]
 
 
@@ -91,12 +92,16 @@ def lib():
         L.jb_cut_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.POINTER(jb_spans)]
         L.jb_cut_batch_into.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp, C.c_uint64, vp,
                                         C.POINTER(C.c_uint64)]
+        L.jb_cut_search.argtypes = L.jb_cut.argtypes
+        L.jb_cut_batch_search.argtypes = L.jb_cut_batch.argtypes
         L.jb_spans_free.argtypes = [C.POINTER(jb_spans)]
         L.jb_spans_free.restype = None
         L.jb_cut_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, C.POINTER(vp), C.POINTER(vp),
                                     C.POINTER(vp), C.POINTER(vp)]
         L.jb_cut_device_into.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, vp, vp, C.c_uint64, vp,
                                          vp]
+        L.jb_cut_device_search.argtypes = L.jb_cut_device.argtypes
+        L.jb_cut_device_search_into.argtypes = L.jb_cut_device_into.argtypes
         L.jb_open_image.argtypes = [vp, C.POINTER(jb_config), C.POINTER(vp)]
         L.jb_cut_batch_mask.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.jb_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
@@ -298,10 +303,10 @@ class Tokenizer:
             pass
 
     # -- cutting ---------------------------------------------------------
-    def cut_spans(self, text, hmm):
+    def cut_spans(self, text, hmm, _fn="jb_cut"):
         t = _b(text)
         sp = jb_spans()
-        _check(lib().jb_cut(self.h, t, len(t), int(hmm), C.byref(sp)))
+        _check(getattr(lib(), _fn)(self.h, t, len(t), int(hmm), C.byref(sp)))
         try:
             n = sp.ntokens
             s = np.ctypeslib.as_array(sp.start, (max(n, 1),))[:n].copy()
@@ -315,17 +320,27 @@ class Tokenizer:
         s, e = self.cut_spans(text, useHmm)
         return spans_to_tokens(text, s.tolist(), e.tolist())
 
+    def cut_search_spans(self, text, hmm):
+        """jb_cut_search: the spans of Cut, each Han token of three or more runes preceded by
+        the dictionary words of two, then three, runes inside it (overlapping spans)."""
+        return self.cut_spans(text, hmm, "jb_cut_search")
+
+    def CutForSearch(self, text, useHmm):
+        """Search-engine mode (jieba's cut_for_search on this reference's DAG, jiebahip.h)."""
+        s, e = self.cut_search_spans(text, useHmm)
+        return spans_to_tokens(text, s.tolist(), e.tolist())
+
     def CutParallel(self, text, hmm, numWorkers=1, ordered=True):
         """Tokenizer.CutParallel (tokenizer.go:81): always in text order."""
         return self.Cut(text, hmm)
 
-    def cut_batch(self, buf, doc_off, hmm):
+    def cut_batch(self, buf, doc_off, hmm, _fn="jb_cut_batch"):
         """Host batch -> (starts u64, ends u64, doc_tok u64[ndocs+1])."""
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
         nd = len(doc_off) - 1
         sp = jb_spans()
-        _check(lib().jb_cut_batch(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, int(hmm), C.byref(sp)))
+        _check(getattr(lib(), _fn)(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, int(hmm), C.byref(sp)))
         try:
             n = sp.ntokens
             s = np.ctypeslib.as_array(sp.start, (max(n, 1),))[:n].copy()
@@ -334,6 +349,10 @@ class Tokenizer:
         finally:
             lib().jb_spans_free(C.byref(sp))
         return s, e, d
+
+    def cut_batch_search(self, buf, doc_off, hmm):
+        """jb_cut_batch_search: cut_batch in search mode; doc_tok indexes the expanded spans."""
+        return self.cut_batch(buf, doc_off, hmm, "jb_cut_batch_search")
 
     def cut_batch_into(self, buf, doc_off, hmm, out=None):
         """Host batch into caller-owned arrays (jb_cut_batch_into).  `out` =
@@ -395,17 +414,27 @@ class Tokenizer:
                                        out[1].ctypes.data, len(out[0]), C.byref(n)))
         return out[0][:nw], out[1][:nw], n.value
 
-    def cut_device(self, d_text_ptr, nbytes, d_doc_off_ptr, ndocs, hmm, stream_ptr=0):
+    def cut_device(self, d_text_ptr, nbytes, d_doc_off_ptr, ndocs, hmm, stream_ptr=0, _fn="jb_cut_device"):
         """Device-resident cut; returns device pointers (start, end, doc_tok, ntok)."""
         a, b, c, d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _check(lib().jb_cut_device(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_doc_off_ptr), ndocs,
+        _check(getattr(lib(), _fn)(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_doc_off_ptr), ndocs,
                                    int(hmm), C.c_void_p(stream_ptr), C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return a.value, b.value, c.value, d.value
 
+    def cut_device_search(self, d_text_ptr, nbytes, d_doc_off_ptr, ndocs, hmm, stream_ptr=0):
+        """jb_cut_device_search: cut_device in search mode (the expanded spans)."""
+        return self.cut_device(d_text_ptr, nbytes, d_doc_off_ptr, ndocs, hmm, stream_ptr, "jb_cut_device_search")
+
+    def cut_device_search_into(self, d_text_ptr, nbytes, d_doc_off_ptr, ndocs, hmm, d_start, d_end, cap, d_doc_tok,
+                               d_ntok, stream_ptr=0):
+        """jb_cut_device_search_into: the expanded spans into caller-owned device arrays."""
+        self.cut_device_into(d_text_ptr, nbytes, d_doc_off_ptr, ndocs, hmm, d_start, d_end, cap, d_doc_tok, d_ntok,
+                             stream_ptr, "jb_cut_device_search_into")
+
     def cut_device_into(self, d_text_ptr, nbytes, d_doc_off_ptr, ndocs, hmm, d_start, d_end, cap, d_doc_tok, d_ntok,
-                        stream_ptr=0):
+                        stream_ptr=0, _fn="jb_cut_device_into"):
         """jb_cut_device_into: caller-owned device outputs (raw pointers)."""
-        _check(lib().jb_cut_device_into(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_doc_off_ptr), ndocs,
+        _check(getattr(lib(), _fn)(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_doc_off_ptr), ndocs,
                                         int(hmm), C.c_void_p(stream_ptr), C.c_void_p(d_start), C.c_void_p(d_end),
                                         cap, C.c_void_p(d_doc_tok), C.c_void_p(d_ntok)))
 
