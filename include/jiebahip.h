@@ -208,11 +208,61 @@ int jb_cut_device_search_into(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbyte
                               uint32_t ndocs, int hmm, void *stream, uint32_t *d_start, uint32_t *d_end,
                               uint64_t cap, uint64_t *d_doc_tok, uint64_t *d_ntok);
 
+/* ---- full mode (jieba's cut_all=True; the reference has only Cut) ------------
+ * Every word the dictionary can find in the text, overlapping words included.  There is no
+ * hmm argument: full mode never consults the HMM (the plain pipeline runs with hmm = 0).
+ * For each splitText block of a document, in text order (tokenizer.go:165-210):
+ *  - a non-Han block gives cutNonZh's tokens, exactly as Cut does (the reference never
+ *    consults the dictionary there);
+ *  - a Han block whose n runes start at bytes p_0 < ... < p_{n-1}, p_n = the block's end:
+ *    let D(i) be the set of L such that buildDag (tokenizer.go:462-497) has the edge of L
+ *    runes from rune i (1 is always in D(i): a rune that is absent or has count 0 has that
+ *    edge alone, :468-471), and M(i) = D(i) \ {1}.  For i = 0 .. n-1 in order:
+ *      M(i) not empty: [p_i, p_{i+L}) for each L in M(i), ascending (the one-rune word is
+ *        not emitted);
+ *      M(i) empty: [p_i, p_{i+1}), unless the nearest earlier rune i' < i of this block with
+ *        M(i') not empty has i' + max M(i') > i.  Without such an i' the rune is emitted.
+ *        Only the nearest such rune counts, not any rune whose word covers i (jieba's old_j,
+ *        the end of the last word emitted).
+ *    This is jieba's __cut_all loop restated.
+ * The spans are ordered by start byte, then by end, and overlap.  ntokens / *d_ntok and
+ * doc_tok describe this list; jb_last_stats keeps reporting the plain counts.  JB_EPANIC
+ * cannot arise from the rule itself, but the plain run's errors pass through unchanged.
+ * Three deliberate differences from Python jieba's cut_all:
+ *  - the DAG is this reference's buildDag, with its gate on the first rune (:468-471) and
+ *    its break at an absent prefix (:476-478);
+ *  - non-Han text is cut by cutNonZh, not by jieba's re_skip splitting (and re_eng merging);
+ *  - the Han class is unicode.Han, not [\u4E00-\u9FD5].
+ * Size: a rune gives up to maxlen - 1 spans (maxlen: the longest word, jb_image_info), so a
+ * batch of n bytes can give MORE than n spans.  The host calls always return the complete
+ * list.  The device calls write the spans whose index is below the arrays' capacity and
+ * count the rest: *d_ntok and d_doc_tok always describe the complete list, and
+ * jb_device_status returns JB_ELIMIT when the count exceeded the capacity (the caller then
+ * repeats the call with arrays of *d_ntok entries).  Counts are kept in 64 bits throughout. */
+
+/* jb_cut in full mode: one document. */
+int jb_cut_full(jb_ctx *ctx, const uint8_t *text, size_t len, jb_spans *out);
+/* jb_cut_batch in full mode (arguments and ownership as jb_cut_batch). */
+int jb_cut_batch_full(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, jb_spans *out);
+/* jb_cut_device in full mode (arguments, limits, alignment and lifetime as jb_cut_device).
+ * The ctx-owned *d_start / *d_end hold nbytes entries (capacity nbytes) and may be the arrays
+ * of jb_cut_device_search: either result is valid until the next call on this ctx. */
+int jb_cut_device_full(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uint64_t *d_doc_off,
+                       uint32_t ndocs, void *stream, uint32_t **d_start, uint32_t **d_end, uint64_t **d_doc_tok,
+                       uint64_t **d_ntok);
+/* jb_cut_device_into in full mode: caller-owned device arrays of any capacity `cap` (u32
+ * entries; spans with index >= cap are not written), d_doc_tok ndocs+1 u64, *d_ntok the
+ * count of the complete list. */
+int jb_cut_device_full_into(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uint64_t *d_doc_off,
+                            uint32_t ndocs, void *stream, uint32_t *d_start, uint32_t *d_end, uint64_t cap,
+                            uint64_t *d_doc_tok, uint64_t *d_ntok);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:
- * the spans are not the reference's) or JB_EDEVICE (a long-block phase wait gave up,
- * JB_LONG_WAIT_US: the spans are incomplete).  The device calls themselves return
+ * the spans are not the reference's), JB_EDEVICE (a long-block phase wait gave up,
+ * JB_LONG_WAIT_US: the spans are incomplete) or JB_ELIMIT (full mode: the list is longer
+ * than the arrays' capacity, the spans past it were not written).  The device calls themselves return
  * before their kernels run, so a caller that must know checks here (a host batch,
  * jb_cut_batch*, returns these codes itself). */
 int jb_device_status(jb_ctx *ctx, void *stream);

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <array>
 #include <atomic>
 #include <cmath>
@@ -132,6 +133,11 @@ struct Device {
     // first search call and again whenever the workspace grows (ensure_search)
     SearchOut srch{};
     uint64_t srch_gen = 0;  // work_gen they were sized for
+    // full mode (jb_cut_*_full) shares them (both are valid only until the next call) and adds the
+    // per-tile bases of its 64-bit offsets
+    uint64_t* full_tbase = nullptr;
+    uint64_t full_gen = 0;
+    uint32_t maxlen = 1;  // the image's longest key, runes (full mode's look-back reach)
     uint8_t* text = nullptr;   // staging for host batches (padded)
     uint64_t* doc_off = nullptr;
     uint64_t text_cap = 0;
@@ -224,13 +230,14 @@ struct Device {
     struct GraphKey {
         const void* text; uint64_t nbytes; const void* doc_off; uint32_t ndocs; bool hmm;
         uint64_t work_gen; hipStream_t stream; const void* out_s; const void* out_e; const void* out_d;
-        // search mode: the pass's outputs (all null for a plain run)
-        bool search; const void* so_s; const void* so_e; const void* so_d; const void* so_n;
+        // search and full mode (CutMode): the pass's outputs (all null for a plain run) and, in full
+        // mode, their capacity
+        int mode; const void* so_s; const void* so_e; const void* so_d; const void* so_n; uint64_t so_cap;
         bool operator==(const GraphKey& o) const {
             return text == o.text && nbytes == o.nbytes && doc_off == o.doc_off && ndocs == o.ndocs &&
                    hmm == o.hmm && work_gen == o.work_gen && stream == o.stream && out_s == o.out_s &&
-                   out_e == o.out_e && out_d == o.out_d && search == o.search && so_s == o.so_s &&
-                   so_e == o.so_e && so_d == o.so_d && so_n == o.so_n;
+                   out_e == o.out_e && out_d == o.out_d && mode == o.mode && so_s == o.so_s &&
+                   so_e == o.so_e && so_d == o.so_d && so_n == o.so_n && so_cap == o.so_cap;
         }
     } gkey{};
     hipGraphExec_t gexec = nullptr;  // captured for gkey (null until the key repeats)
@@ -239,16 +246,17 @@ struct Device {
     // launch that failed part way.  Pipelines leave it all zeros (k_docbits, k_nonzh).
     bool docbits_dirty = true;
     uint64_t gkey_gen = 0;
-    // the same for search mode, so that plain and search calls on the same buffers each keep
-    // their captured graph
-    GraphKey gkey_s{};
-    hipGraphExec_t gexec_s = nullptr;
-    uint64_t gkey_gen_s = 0;
+    // the same for search mode and for full mode, so that calls of the three modes on the same
+    // buffers each keep their captured graph
+    GraphKey gkey_s{}, gkey_f{};
+    hipGraphExec_t gexec_s = nullptr, gexec_f = nullptr;
+    uint64_t gkey_gen_s = 0, gkey_gen_f = 0;
     void drop_graphs() {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (gexec_s) (void)hipGraphExecDestroy(gexec_s);
-        gexec = gexec_s = nullptr;
-        gkey_gen = gkey_gen_s = 0;
+        if (gexec_f) (void)hipGraphExecDestroy(gexec_f);
+        gexec = gexec_s = gexec_f = nullptr;
+        gkey_gen = gkey_gen_s = gkey_gen_f = 0;
     }
 };
 
@@ -595,6 +603,7 @@ static int install_image(Device* d, ImageBufs* b, const Image& img) {
     d->dim.plainw = 1u;
     for (double w : img.wtab)
         if (std::isnan(w) || w == HUGE_VAL) d->dim.plainw = 0u;  // (a dictionary size <= 0)
+    d->maxlen = std::max<uint32_t>(img.maxlen, 1u);
     // a captured pipeline holds the old image pointers in its kernel arguments
     d->drop_graphs();
     return JB_OK;
@@ -664,6 +673,8 @@ static void free_search(Device* d) {
     SearchOut& so = d->srch;
     dfree(so.start); dfree(so.end); dfree(so.doc_tok); dfree(so.off); dfree(so.tile); dfree(so.sup);
     so = SearchOut{};
+    dfree(d->full_tbase);
+    d->full_tbase = nullptr;
 }
 
 // The search pass's buffers, sized like the workspace's spans (after ensure_work).  A context
@@ -682,6 +693,36 @@ static int ensure_search(Device* d) {
     so.ntok = reinterpret_cast<uint64_t*>(d->w.counters + CNT_NSRCH);
     d->srch_gen = d->work_gen;
     return JB_OK;
+}
+
+// Which list a cut returns: Cut's tokens, their search-mode expansion (run_search) or the full-mode
+// list (run_full).  Each mode has its own captured graph.
+enum CutMode { kModePlain = 0, kModeSearch = 1, kModeFull = 2 };
+// The outputs of the pass that follows the pipeline's kernels in search and full mode.
+struct PostOut {
+    CutMode mode;
+    SearchOut so;  // kModeSearch
+    FullOut fo;    // kModeFull
+};
+
+// Full mode's buffers: search mode's (the ctx-owned spans, nbytes entries, and the workspace: an
+// 8-byte tile sum either way), and the per-tile bases.
+static int ensure_full(Device* d) {
+    int rc;
+    if ((rc = ensure_search(d))) return rc;
+    if (d->full_tbase && d->full_gen == d->work_gen) return JB_OK;
+    dfree(d->full_tbase);
+    d->full_tbase = nullptr;
+    HIPCHK(hipMalloc(&d->full_tbase, (srch_tiles(d->w.cap_bytes) + 1) * 8));
+    d->full_gen = d->work_gen;
+    return JB_OK;
+}
+static_assert(sizeof(uint2) == sizeof(uint64_t), "full mode keeps 64-bit sums in search mode's tile arrays");
+// The pass's arguments with the ctx-owned outputs (cap = the workspace's bytes).
+static FullOut full_out(const Device* d) {
+    const SearchOut& so = d->srch;
+    return FullOut{so.start, so.end, d->w.cap_bytes, so.doc_tok, so.ntok, so.off,
+                   reinterpret_cast<uint64_t*>(so.tile), reinterpret_cast<uint64_t*>(so.sup), d->full_tbase, d->maxlen};
 }
 
 // grow-only device / pinned buffers (a call never has work in flight on them when it grows them)
@@ -809,22 +850,24 @@ static int init_launch_cfg(Device* d) {
 
 static int launch_pipeline_(Device* d, const Work& w, const uint8_t* d_text, uint64_t nbytes,
                             const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask,
-                            const SearchOut* so);
+                            const PostOut* po);
 static int launch_pipeline(Device* d, const Work& w, const uint8_t* d_text, uint64_t nbytes,
                            const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask,
-                           const SearchOut* so) {
+                           const PostOut* po) {
     if (d->docbits_dirty) {  // the whole bitmap, once (see Device::docbits_dirty)
         HIPCHK(run_zero(w.docbits, w.bits_stride * 4, s));
         d->docbits_dirty = false;
     }
-    const int rc = launch_pipeline_(d, w, d_text, nbytes, d_doc_off, ndocs, hmm, s, mask, so);
+    const int rc = launch_pipeline_(d, w, d_text, nbytes, d_doc_off, ndocs, hmm, s, mask, po);
     if (rc) d->docbits_dirty = true;
     return rc;
 }
-// so != nullptr: search mode, the search pass (run_search) follows the pipeline's kernels
+// po != nullptr: search or full mode, the mode's pass (run_search, run_full) follows the pipeline's kernels
 static int launch_pipeline_(Device* d, const Work& w, const uint8_t* d_text, uint64_t nbytes,
                             const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask,
-                            const SearchOut* so) {
+                            const PostOut* po) {
+    const SearchOut* const so = po && po->mode == kModeSearch ? &po->so : nullptr;
+    const FullOut* const fo = po && po->mode == kModeFull ? &po->fo : nullptr;
     static const bool dbg = getenv("JB_DEBUG") != nullptr;
     const LaunchCfg& lc = d->lc;
     d->last_nbytes = nbytes;
@@ -836,19 +879,23 @@ static int launch_pipeline_(Device* d, const Work& w, const uint8_t* d_text, uin
         fprintf(stderr, "[jb] nbytes=%llu ndocs=%u zh_waves=%u/%u wide=%d zh_group=%u\n", (unsigned long long)nbytes,
                 ndocs, lc.zh_waves, lc.zh_waves_wide, lc.zh_wide, lc.zh_group ? lc.zh_group : zh_group_for(nbytes));
     static const bool use_graph = env_int("JB_GRAPH", 1) != 0;
-    auto run = [&](KernelTimer* tm) {  // the pipeline's kernels, then search mode's
+    auto run = [&](KernelTimer* tm) {  // the pipeline's kernels, then search or full mode's
         hipError_t e = run_pipeline(d->dim, w, d_text, nbytes, d_doc_off, ndocs, hmm, lc, s, tm, mask);
         if (e == hipSuccess && so) e = run_search(d->dim, w, *so, d_text, nbytes, ndocs, s, tm);
+        if (e == hipSuccess && fo) e = run_full(d->dim, w, *fo, d_text, nbytes, ndocs, s, tm);
         return e;
     };
     if (use_graph && !d->profile && lc.diag == 0 && s != nullptr && !mask) {
         const Device::GraphKey key{d_text, nbytes, d_doc_off, ndocs, hmm, d->work_gen, s, w.tok_start, w.tok_end,
-                                   w.doc_tok, so != nullptr, so ? so->start : nullptr, so ? so->end : nullptr,
-                                   so ? (const void*)so->doc_tok : nullptr, so ? (const void*)so->ntok : nullptr};
+                                   w.doc_tok, po ? (int)po->mode : (int)kModePlain,
+                                   so ? so->start : (fo ? fo->start : nullptr), so ? so->end : (fo ? fo->end : nullptr),
+                                   so ? (const void*)so->doc_tok : (fo ? (const void*)fo->doc_tok : nullptr),
+                                   so ? (const void*)so->ntok : (fo ? (const void*)fo->ntok : nullptr),
+                                   fo ? fo->cap : 0ull};
         // (each mode has its own slot)
-        Device::GraphKey& gkey = so ? d->gkey_s : d->gkey;
-        hipGraphExec_t& gexec = so ? d->gexec_s : d->gexec;
-        uint64_t& gkey_gen = so ? d->gkey_gen_s : d->gkey_gen;
+        Device::GraphKey& gkey = so ? d->gkey_s : (fo ? d->gkey_f : d->gkey);
+        hipGraphExec_t& gexec = so ? d->gexec_s : (fo ? d->gexec_f : d->gexec);
+        uint64_t& gkey_gen = so ? d->gkey_gen_s : (fo ? d->gkey_gen_f : d->gkey_gen);
         const bool repeat = gkey_gen != 0 && key == gkey;
         if (!repeat) {  // first call with this key: run directly, capture if it comes again
             if (gexec) (void)hipGraphExecDestroy(gexec);
@@ -972,10 +1019,10 @@ static int launch_pipeline_(Device* d, const Work& w, const uint8_t* d_text, uin
 // device's workspace, or a copy with caller-owned outputs (jb_cut_device_into).
 static int launch(Device* d, const Work& w, const uint8_t* d_text, uint64_t nbytes, const uint64_t* d_doc_off,
                   uint32_t ndocs, bool hmm, hipStream_t s, const MaskOut* mask = nullptr,
-                  const SearchOut* so = nullptr) {
+                  const PostOut* po = nullptr) {
     if (!d->ws_done) HIPCHK(hipEventCreateWithFlags(&d->ws_done, hipEventDisableTiming));
     else HIPCHK(hipStreamWaitEvent(s, d->ws_done, 0));  // (free on the stream that recorded it)
-    int rc = launch_pipeline(d, w, d_text, nbytes, d_doc_off, ndocs, hmm, s, mask, so);
+    int rc = launch_pipeline(d, w, d_text, nbytes, d_doc_off, ndocs, hmm, s, mask, po);
     if (rc) return rc;
     HIPCHK(hipEventRecord(d->ws_done, s));
     d->ws_stream = s;
@@ -1648,10 +1695,14 @@ static bool host_pinned(const void* p, uint64_t n) {
 // staged into pinned memory and copied up on cstream while piece k's kernels run on
 // `stream` and piece k-1's spans (or final mask words) come back on dstream, then are
 // widened to u64 batch offsets into `out` by kCopyThreads host threads.
-// search: search mode (jb_cut_batch_search).  Such a range always takes the pipeline, and its spans come
-// back unpacked: they overlap, and k_span_pack's gap coding wants ascending disjoint spans.
+// mode: search mode (jb_cut_batch_search) or full mode (jb_cut_batch_full).  Such a range always takes the
+// pipeline, and its spans come back unpacked: they overlap, and k_span_pack's gap coding wants ascending
+// disjoint spans.  A full-mode piece may give more spans than its output set holds: it is then run once
+// more with a set of the size it reported, so a piece's kernels start only when the piece before has
+// been collected.
 static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, uint32_t d0, uint32_t d1, bool hmm,
-                     SpanBuf* out, const MaskDst* mask, bool search = false) {
+                     SpanBuf* out, const MaskDst* mask, CutMode mode = kModePlain) {
+    const bool search = mode != kModePlain, full = mode == kModeFull;  // (search: a pass follows the pipeline)
     if (d0 >= d1) return JB_OK;
     const uint64_t r0 = doc_off[d0], rbytes = doc_off[d1] - r0;
     const uint32_t ndr = d1 - d0;
@@ -1707,7 +1758,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         (rc = grow_pinned(&d->h_misc, &d->h_misc_cap, slots)) ||
         (rc = grow_mapped(&d->h_pcnt, &d->d_pcnt, &d->h_pcnt_cap, (uint64_t)np * kSnapWords)) ||
         (!pinned_in && (rc = grow_pinned(&d->h_text, &d->h_text_cap, dev_bytes))) ||
-        (rc = ensure_work(d, maxb, maxd)) || (search && (rc = ensure_search(d))))
+        (rc = ensure_work(d, maxb, maxd)) || (search && (rc = full ? ensure_full(d) : ensure_search(d))))
         return rc;
     for (auto* v : {&d->ev_h2d, &d->ev_comp, &d->ev_d2h})
         while (v->size() < np) {
@@ -1745,7 +1796,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         (void)hipStreamSynchronize(d->dstream);
         return code;
     };
-    std::vector<uint32_t> ntok(np, 0);  // spans each piece returns (search mode: the expanded count)
+    std::vector<uint32_t> ntok(np, 0);  // spans each piece returns (search and full mode: the pass's count)
     std::vector<std::pair<uint64_t, uint64_t>> words(np);  // mask words each piece copies back
     static const bool tdbg2 = env_int("JB_DEBUG", 0) >= 2;  // per-piece event clocks
     std::vector<hipEvent_t> tev;  // t0, then per piece: H2D done, kernels done, results back
@@ -1805,13 +1856,19 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         HIPCHK(hipStreamWaitEvent(d->stream, d->ev_h2d[k], 0));
         Work w = d->w;
         MaskOut mo{nullptr, nullptr, 0};
-        SearchOut so = d->srch;
+        PostOut po{mode, d->srch, full ? full_out(d) : FullOut{}};
+        SearchOut& so = po.so;
         if (mask) {
             mo = MaskOut{d->d_mask, d->d_mask + nw, rsh + (pb - r0)};
         } else {
             if (k >= (size_t)Device::kSets) HIPCHK(hipStreamWaitEvent(d->stream, d->ev_d2h[k - Device::kSets], 0));
             const Device::OutSet& o = d->outs[k % Device::kSets];
-            if (search) {  // the plain spans stay in the workspace, the expanded ones go to the output set
+            if (full) {  // the plain spans stay in the workspace, the mode's list goes to the output set
+                po.fo.start = o.ts;
+                po.fo.end = o.te;
+                po.fo.cap = o.cap_tok;
+                po.fo.doc_tok = o.dt;
+            } else if (search) {
                 so.start = o.ts;
                 so.end = o.te;
                 so.doc_tok = o.dt;
@@ -1823,7 +1880,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         }
         int r;
         if ((r = launch(d, w, d->text + p.off, len, d->doc_off + p.slot, p.d1 - p.d0, hmm, d->stream,
-                        mask ? &mo : nullptr, search ? &so : nullptr)))
+                        mask ? &mo : nullptr, search ? &po : nullptr)))
             return r;
         d->last_nbytes = len;
         if (pack) {  // the spans packed for the trip back: 4 B per token (k_span_pack)
@@ -1840,15 +1897,33 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         tmark(2 + 3 * k, d->stream);
         return JB_OK;
     };
-    auto collect = [&](size_t k) -> int {  // piece k's kernels are done: queue its results' copy back
+    std::function<int(size_t, bool)> collect_;
+    collect_ = [&](size_t k, bool redone) -> int {  // piece k's kernels are done: queue its results' copy back
         const Piece& p = pcs[k];
         HIPCHK(hipEventSynchronize(d->ev_comp[k]));
         const volatile uint32_t* c = d->h_pcnt + k * kSnapWords;
         if (c[CNT_ERR] & 2u) return fail(JB_EDEVICE, "k_long: a phase wait gave up (no progress for JB_LONG_WAIT_US)");
         if (c[CNT_ERR] & 4u) return fail(JB_EDEVICE, "internal: k_span_pack's side list overflowed");
-        if (c[CNT_ERR]) return fail(JB_EPANIC, "a Han block has no DAG path (the reference panics in cutDAG)");
+        if (c[CNT_ERR] & ~8u) return fail(JB_EPANIC, "a Han block has no DAG path (the reference panics in cutDAG)");
         if (c[CNT_NTOK] != c[CNT_NTOKE])
             return fail(JB_EDEVICE, "internal: %u token starts vs %u ends", c[CNT_NTOK], c[CNT_NTOKE]);
+        if (full) {  // (bit 3 of CNT_ERR: the list is longer than the output set)
+            const uint64_t nfull = (uint64_t)c[CNT_NSRCH] | (uint64_t)c[CNT_NSRCH + 1] << 32;
+            if (nfull >= (1ull << 32))
+                return fail(JB_ELIMIT, "a piece of the batch gives %llu full-mode spans (limit 2^32 - 1)",
+                            (unsigned long long)nfull);
+            Device::OutSet& o = d->outs[k % Device::kSets];
+            if (nfull > o.cap_tok) {
+                if (redone) return fail(JB_EDEVICE, "internal: %llu full-mode spans after a run that counted fewer",
+                                        (unsigned long long)nfull);
+                // the launcher waits for this piece's collection, so the stream is idle and the set unused
+                int r;
+                uint64_t ct = o.cap_tok;
+                if ((r = grow_dev(&o.ts, &ct, nfull + 4)) || (r = grow_dev(&o.te, &o.cap_tok, nfull + 4))) return r;
+                if ((r = compute(k))) return r;
+                return collect_(k, true);
+            }
+        }
         const uint32_t nt = ntok[k] = search ? c[CNT_NSRCH] : c[CNT_NTOK];
         HIPCHK(hipStreamWaitEvent(d->dstream, d->ev_comp[k], 0));
         if (!mask) {
@@ -1893,6 +1968,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         tmark(3 + 3 * k, d->dstream);
         return JB_OK;
     };
+    auto collect = [&](size_t k) -> int { return collect_(k, false); };
     auto finish = [&](size_t k) -> int {  // piece k's results have landed: into the caller's arrays
         const Piece& p = pcs[k];
         HIPCHK(hipEventSynchronize(d->ev_d2h[k]));
@@ -2014,6 +2090,7 @@ static int cut_range(Device* d, const uint8_t* text, const uint64_t* doc_off, ui
         for (size_t k = 0; k < np; k++) {
             if (!wait_for(&staged, k + 1)) break;
             if (!mask && k >= (size_t)Device::kSets && !wait_for(&collected, k - Device::kSets + 1)) break;
+            if (full && !wait_for(&collected, k)) break;  // (collect may run piece k - 1 once more)
             const int r = compute(k);
             publish(&launched, k + 1, r);
             if (r) break;
@@ -2195,7 +2272,7 @@ struct Units {
 // cuts, exclusive inside jb_add_word).
 static int cut_sharded(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
                        std::vector<SpanBuf>* sbp, const MaskDst* mask = nullptr,
-                       std::vector<uint32_t>* unit_doc = nullptr, bool search = false) {
+                       std::vector<uint32_t>* unit_doc = nullptr, CutMode mode = kModePlain) {
     if (ndocs && !text && doc_off[ndocs] > doc_off[0]) return fail(JB_EINVAL, "null text");
     for (uint32_t k = 0; k < ndocs; k++)
         if (doc_off[k + 1] < doc_off[k]) return fail(JB_EINVAL, "doc_off not monotonic at %u", k);
@@ -2268,7 +2345,7 @@ static int cut_sharded(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off
     auto work = [&](size_t k) {
         const uint32_t u0 = split ? un.dev[k] : (k == 0 ? 0u : ndocs), u1 = split ? un.dev[k + 1] : ndocs;
         if (u0 < u1) {
-            rcs[k] = cut_range(ctx->devs[k].get(), text, uoff, u0, u1, hmm != 0, &sb[k], mask, search);
+            rcs[k] = cut_range(ctx->devs[k].get(), text, uoff, u0, u1, hmm != 0, &sb[k], mask, mode);
             if (rcs[k]) errs[k] = g_err;
         }
     };
@@ -2300,14 +2377,14 @@ static void fill_doc_tok(const std::vector<SpanBuf>& sb, uint32_t ndocs, uint64_
 
 // jb_cut_batch with ctx->lock already held by the caller.
 static int cut_batch_locked(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                            jb_spans* out, bool search = false) {
+                            jb_spans* out, CutMode mode = kModePlain) {
     const size_t nd = ctx->devs.size();
     std::vector<SpanBuf> sb(nd);
     auto release_all = [&] {
         for (auto& b : sb) b.release();
     };
     std::vector<uint32_t> unit_doc;
-    int rc = cut_sharded(ctx, text, doc_off, ndocs, hmm, &sb, nullptr, &unit_doc, search);
+    int rc = cut_sharded(ctx, text, doc_off, ndocs, hmm, &sb, nullptr, &unit_doc, mode);
     if (rc) {
         release_all();
         return rc;
@@ -2358,7 +2435,15 @@ extern "C" int jb_cut_batch_search(jb_ctx* ctx, const uint8_t* text, const uint6
     if (!ctx || !out || (!doc_off && ndocs)) return fail(JB_EINVAL, "jb_cut_batch_search: null argument");
     memset(out, 0, sizeof *out);
     std::shared_lock<std::shared_mutex> rl(ctx->lock);
-    return cut_batch_locked(ctx, text, doc_off, ndocs, hmm, out, true);
+    return cut_batch_locked(ctx, text, doc_off, ndocs, hmm, out, kModeSearch);
+}
+
+extern "C" int jb_cut_batch_full(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs,
+                                 jb_spans* out) {
+    if (!ctx || !out || (!doc_off && ndocs)) return fail(JB_EINVAL, "jb_cut_batch_full: null argument");
+    memset(out, 0, sizeof *out);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    return cut_batch_locked(ctx, text, doc_off, ndocs, 0, out, kModeFull);
 }
 
 extern "C" int jb_cut_batch_into(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs,
@@ -2527,6 +2612,12 @@ extern "C" int jb_cut_search(jb_ctx* ctx, const uint8_t* text, size_t len, int h
     return jb_cut_batch_search(ctx, text ? text : empty, off, 1, hmm, out);
 }
 
+extern "C" int jb_cut_full(jb_ctx* ctx, const uint8_t* text, size_t len, jb_spans* out) {
+    const uint64_t off[2] = {0, (uint64_t)len};
+    static const uint8_t empty[1] = {0};
+    return jb_cut_batch_full(ctx, text ? text : empty, off, 1, out);
+}
+
 extern "C" void jb_spans_free(jb_spans* s) {
     if (!s) return;
     free(s->start);
@@ -2538,7 +2629,7 @@ extern "C" void jb_spans_free(jb_spans* s) {
 static int cut_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint64_t* d_doc_off,
                       uint32_t ndocs, int hmm, void* stream, uint32_t* o_start, uint32_t* o_end, uint64_t* o_doc_tok,
                       uint64_t* o_ntok, uint32_t** d_start, uint32_t** d_end, uint64_t** d_doc_tok, uint64_t** d_ntok,
-                      bool search = false) {
+                      CutMode mode = kModePlain, uint64_t cap = 0) {
     if (!ctx || (!d_text && nbytes) || !d_doc_off) return fail(JB_EINVAL, "jb_cut_device: null argument");
     if (nbytes >= (1ull << 31)) return fail(JB_ELIMIT, "device batch of %llu bytes (limit 2 GiB)",
                                             (unsigned long long)nbytes);
@@ -2554,16 +2645,36 @@ static int cut_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const
     int rc;
     if ((rc = ensure_work(d, nbytes, ndocs))) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    if (search) {  // the plain spans in the workspace, the expanded ones in the search buffers or the caller's arrays
+    if (mode == kModeFull) {  // the plain spans in the workspace, the list in the search buffers or the caller's arrays
+        if ((rc = ensure_full(d))) return rc;
+        PostOut po{mode, SearchOut{}, full_out(d)};
+        FullOut& fo = po.fo;
+        fo.cap = nbytes;  // (the ctx-owned arrays: nbytes entries, whatever the workspace has grown to)
+        if (o_start) {
+            fo.start = o_start;
+            fo.end = o_end;
+            fo.cap = cap;
+            fo.doc_tok = o_doc_tok;
+            fo.ntok = o_ntok;
+        }
+        if ((rc = launch(d, d->w, d_text, nbytes, d_doc_off, ndocs, false, s, nullptr, &po))) return rc;
+        if (d_start) *d_start = fo.start;
+        if (d_end) *d_end = fo.end;
+        if (d_doc_tok) *d_doc_tok = fo.doc_tok;
+        if (d_ntok) *d_ntok = fo.ntok;
+        return JB_OK;
+    }
+    if (mode == kModeSearch) {  // the plain spans in the workspace, the expanded ones in the search buffers or the caller's arrays
         if ((rc = ensure_search(d))) return rc;
-        SearchOut so = d->srch;
+        PostOut po{mode, d->srch, FullOut{}};
+        SearchOut& so = po.so;
         if (o_start) {
             so.start = o_start;
             so.end = o_end;
             so.doc_tok = o_doc_tok;
             so.ntok = o_ntok;
         }
-        if ((rc = launch(d, d->w, d_text, nbytes, d_doc_off, ndocs, hmm != 0, s, nullptr, &so))) return rc;
+        if ((rc = launch(d, d->w, d_text, nbytes, d_doc_off, ndocs, hmm != 0, s, nullptr, &po))) return rc;
         if (d_start) *d_start = so.start;
         if (d_end) *d_end = so.end;
         if (d_doc_tok) *d_doc_tok = so.doc_tok;
@@ -2609,7 +2720,7 @@ extern "C" int jb_cut_device_search(jb_ctx* ctx, const uint8_t* d_text, uint64_t
                                     uint32_t ndocs, int hmm, void* stream, uint32_t** d_start, uint32_t** d_end,
                                     uint64_t** d_doc_tok, uint64_t** d_ntok) {
     return cut_device(ctx, d_text, nbytes, d_doc_off, ndocs, hmm, stream, nullptr, nullptr, nullptr, nullptr, d_start,
-                      d_end, d_doc_tok, d_ntok, true);
+                      d_end, d_doc_tok, d_ntok, kModeSearch);
 }
 
 extern "C" int jb_cut_device_search_into(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes,
@@ -2620,7 +2731,22 @@ extern "C" int jb_cut_device_search_into(jb_ctx* ctx, const uint8_t* d_text, uin
     if (cap < nbytes) return fail(JB_EINVAL, "jb_cut_device_search_into: cap %llu < nbytes %llu (a batch of n bytes "
                                   "has up to n search-mode spans)", (unsigned long long)cap, (unsigned long long)nbytes);
     return cut_device(ctx, d_text, nbytes, d_doc_off, ndocs, hmm, stream, d_start, d_end, d_doc_tok, d_ntok, nullptr,
-                      nullptr, nullptr, nullptr, true);
+                      nullptr, nullptr, nullptr, kModeSearch);
+}
+
+extern "C" int jb_cut_device_full(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint64_t* d_doc_off,
+                                  uint32_t ndocs, void* stream, uint32_t** d_start, uint32_t** d_end,
+                                  uint64_t** d_doc_tok, uint64_t** d_ntok) {
+    return cut_device(ctx, d_text, nbytes, d_doc_off, ndocs, 0, stream, nullptr, nullptr, nullptr, nullptr, d_start,
+                      d_end, d_doc_tok, d_ntok, kModeFull);
+}
+
+extern "C" int jb_cut_device_full_into(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint64_t* d_doc_off,
+                                       uint32_t ndocs, void* stream, uint32_t* d_start, uint32_t* d_end, uint64_t cap,
+                                       uint64_t* d_doc_tok, uint64_t* d_ntok) {
+    if (!d_start || !d_end || !d_doc_tok || !d_ntok) return fail(JB_EINVAL, "jb_cut_device_full_into: null output");
+    return cut_device(ctx, d_text, nbytes, d_doc_off, ndocs, 0, stream, d_start, d_end, d_doc_tok, d_ntok, nullptr,
+                      nullptr, nullptr, nullptr, kModeFull, cap);
 }
 
 // ---------------------------------------------------------------------------
@@ -2785,7 +2911,8 @@ extern "C" int jb_last_stats(jb_ctx* ctx, jb_stats* out) {
     }
     // (a host batch already returned these from its own call; a device pipeline reports them here)
     if (err & 2u) return fail(JB_EDEVICE, "k_long: a phase wait gave up (no progress for JB_LONG_WAIT_US)");
-    if (err) return fail(JB_EPANIC, "a Han block has no DAG path (the reference panics in cutDAG)");
+    // (bit 3, a full-mode list longer than its arrays, is jb_device_status's to report: the plain counts stand)
+    if (err & ~8u) return fail(JB_EPANIC, "a Han block has no DAG path (the reference panics in cutDAG)");
     return JB_OK;
 }
 
@@ -2801,7 +2928,13 @@ extern "C" int jb_device_status(jb_ctx* ctx, void* stream) {
     uint32_t e = 0;
     HIPCHK(hipMemcpy(&e, d->w.counters + CNT_ERR, sizeof e, hipMemcpyDeviceToHost));
     if (e & 2u) return fail(JB_EDEVICE, "k_long: a phase wait gave up (no progress for JB_LONG_WAIT_US)");
-    if (e) return fail(JB_EPANIC, "a Han block has no DAG path (the reference panics in cutDAG)");
+    if (e & ~8u) return fail(JB_EPANIC, "a Han block has no DAG path (the reference panics in cutDAG)");
+    if (e & 8u) {
+        uint64_t n = 0;
+        HIPCHK(hipMemcpy(&n, d->w.counters + CNT_NSRCH, sizeof n, hipMemcpyDeviceToHost));
+        return fail(JB_ELIMIT, "the full-mode list has %llu spans, more than the output arrays hold: the spans "
+                               "past their capacity were not written", (unsigned long long)n);
+    }
     return JB_OK;
 }
 

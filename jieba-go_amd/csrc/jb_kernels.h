@@ -35,12 +35,14 @@ struct DevImage {
 
 // Device counters (u32 slots unless noted)
 enum {
-    CNT_NSRCH = 0,  // u64 at u32 slots 0-1: spans of the search-mode expansion (run_search; 0 after a plain run)
+    CNT_NSRCH = 0,  // u64 at u32 slots 0-1: spans of the search-mode expansion (run_search) or of the full-mode
+                    // list (run_full); 0 after a plain run
     CNT_NTOK = 2,   // token starts
     CNT_NTOKE = 3,  // token ends (== CNT_NTOK when consistent)
     CNT_ERR = 4,    // bit 0: a zh block reached a tail index -1 (the reference panics); bit 1: a k_long
                     // phase wait gave up (no progress for LaunchCfg::long_wait_ticks); bit 2: k_span_pack's
-                    // side list overflowed (internal)
+                    // side list overflowed (internal); bit 3: run_full's list is longer than the output
+                    // arrays (FullOut::cap): the spans past them were counted and not written
     CNT_WORK = 5,   // k_zh work counter: next group (kZhGroupBytes of text)
     CNT_SIDE = 6,   // k_span_pack: tokens in the side list
     CNT_TOKT = 30,  // k_tok1's tile tickets
@@ -119,6 +121,7 @@ enum KernelId {
     K_DOCBITS = 0, K_MARK_WALK, K_ZH, K_NONZH,
     K_TOK_COUNT, K_SCAN_TOK, K_TOK_WRITE, K_DOC_TOK, K_LONG_SPEC, K_LONG_DP, K_LONG_SEG, K_LONG_PATH, K_LONG_TAIL, K_MASK_MERGE,
     K_LONG_PBITS, K_LONG, K_TOK1, K_SRCH_COUNT, K_SRCH_SCAN, K_SRCH_WRITE, K_SRCH_DOC,
+    K_FULL_COUNT, K_FULL_SCAN, K_FULL_WRITE, K_FULL_DOC,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -205,6 +208,27 @@ struct SearchOut {
 // w.tok_end / w.doc_tok hold its plain spans, w.erec its DAG records).
 hipError_t run_search(const DevImage& im, const Work& w, const SearchOut& so, const uint8_t* d_text, uint64_t nbytes,
                       uint32_t ndocs, hipStream_t stream, KernelTimer* timer);
+
+// Full mode (jb_cut_*_full, jieba's cut_all): the spans of a finished run_pipeline with hmm = 0 replaced,
+// inside every Han block, by each dictionary word of two or more runes (by start, then by length) and by the
+// single runes that no such word accounts for; non-Han tokens are copied.  The list can be longer than
+// the text, so the counts are 64 bits wide and the output arrays have a capacity of their own.
+struct FullOut {
+    uint32_t* start;    // the spans, cap entries: a span whose index is >= cap is not written
+    uint32_t* end;
+    uint64_t cap;
+    uint64_t* doc_tok;  // ndocs + 1, of the complete list
+    uint64_t* ntok;     // the count of the complete list (also left in the counters, CNT_NSRCH)
+    // workspace (SearchOut's, which both modes may share, and tbase)
+    uint32_t* off;      // per plain token: its span count (k_full_count), then its first span within its tile
+    uint64_t* tile;     // per token tile: its spans; srch_tiles(nbytes) entries
+    uint64_t* sup;      // per 256 token tiles: their sum (k_sup64)
+    uint64_t* tbase;    // per token tile: the spans before it (k_full_write)
+    uint32_t maxlen;    // the image's longest key, runes
+};
+// Enqueue the full-mode pass on `stream`, after run_pipeline's kernels (hmm = false) for the same batch.
+hipError_t run_full(const DevImage& im, const Work& w, const FullOut& fo, const uint8_t* d_text, uint64_t nbytes,
+                    uint32_t ndocs, hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

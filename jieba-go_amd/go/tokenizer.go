@@ -242,6 +242,32 @@ func (t *Tokenizer) CutForSearch(text string, useHmm bool) []string {
 	return spansToTokens(text, &s, 0)
 }
 
+// CutAll is full mode (jieba's cut_all=True; the reference has only Cut): every dictionary
+// word of two or more runes in the text's Han blocks, by start and then by length, overlapping
+// words included, and the single runes that no such word accounts for; non-Han text as Cut
+// cuts it (jb_cut_batch_full in jiebahip.h, with its three differences from Python jieba: the
+// DAG is buildDag's, non-Han text is cutNonZh's, the Han class is unicode.Han).  The HMM is
+// never consulted.  With the dictionary 甲 5 / 甲乙 5 / 甲乙丙 0 / 甲乙丙丁 5 / 乙 5 / 乙丙 5 /
+// 丙 5 / 丁 5, CutAll("甲乙丙丁戊丁") is 甲乙, 甲乙丙丁, 乙丙, 丁, 戊, 丁 (tests/c_abi_full.c).
+// Never returns nil.
+func (t *Tokenizer) CutAll(text string) []string {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	if len(text) == 0 {
+		return []string{}
+	}
+	b := []byte(text)
+	off := []uint64{0, uint64(len(b))}
+	var s C.jb_spans
+	if rc := C.jb_cut_batch_full(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+		1, &s); rc != C.JB_OK {
+		// JB_EPANIC: the reference panics on this input (cutDAG slice with tail -1)
+		panic("jiebahip: " + lastError())
+	}
+	defer C.jb_spans_free(&s)
+	return spansToTokens(text, &s, 0)
+}
+
 // CutParallel (tokenizer.go:81) returns the tokens of Cut in document order.
 // The library splits the work itself: the text goes to the device in pieces cut
 // at Han-run starts (jb_split_points), and over every device of a multi-device

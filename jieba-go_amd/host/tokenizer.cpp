@@ -75,6 +75,16 @@ std::vector<std::string> Tokenizer::CutForSearch(const std::string& text, bool u
     return out;
 }
 
+std::vector<std::string> Tokenizer::CutAll(const std::string& text) {
+    jb_spans sp;
+    check(jb_cut_full(ctx_, (const uint8_t*)text.data(), text.size(), &sp));
+    std::vector<std::string> out;
+    out.reserve(sp.ntokens);
+    for (uint64_t k = 0; k < sp.ntokens; k++) out.push_back(token_at(text, sp.start[k], sp.end[k]));
+    jb_spans_free(&sp);
+    return out;
+}
+
 std::vector<std::string> Tokenizer::CutParallel(const std::string& text, bool hmm, int, bool) {
     return Cut(text, hmm);
 }

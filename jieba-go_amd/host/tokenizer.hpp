@@ -49,6 +49,11 @@ public:
     // three, runes inside it that buildDag has as edges (jb_cut_search in jiebahip.h, with
     // its two differences from Python jieba).
     std::vector<std::string> CutForSearch(const std::string& text, bool useHmm);
+    // Full mode (jieba's cut_all; the reference has only Cut): every dictionary word of two or
+    // more runes in the text's Han blocks, by start and then by length, overlapping words
+    // included, and the single runes that no such word accounts for; non-Han text as Cut cuts
+    // it (jb_cut_full in jiebahip.h, with its three differences from Python jieba).
+    std::vector<std::string> CutAll(const std::string& text);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

@@ -33,6 +33,7 @@ EXPORTS = [
     "jb_image_stats", "jb_image_emit", "jb_go_log", "jb_shard_bounds", "jb_last_stats",
     "jb_suggest_freq", "jb_add_log", "jb_image_log_keys", "jb_device_status", "jb_cut_batch_into32",
     "jb_cut_search", "jb_cut_batch_search", "jb_cut_device_search", "jb_cut_device_search_into",
+    "jb_cut_full", "jb_cut_batch_full", "jb_cut_device_full", "jb_cut_device_full_into",
 ]
 
 
@@ -94,6 +95,8 @@ def lib():
                                         C.POINTER(C.c_uint64)]
         L.jb_cut_search.argtypes = L.jb_cut.argtypes
         L.jb_cut_batch_search.argtypes = L.jb_cut_batch.argtypes
+        L.jb_cut_full.argtypes = [vp, vp, C.c_size_t, C.POINTER(jb_spans)]  # (no hmm argument)
+        L.jb_cut_batch_full.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(jb_spans)]
         L.jb_spans_free.argtypes = [C.POINTER(jb_spans)]
         L.jb_spans_free.restype = None
         L.jb_cut_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, C.POINTER(vp), C.POINTER(vp),
@@ -102,6 +105,9 @@ def lib():
                                          vp]
         L.jb_cut_device_search.argtypes = L.jb_cut_device.argtypes
         L.jb_cut_device_search_into.argtypes = L.jb_cut_device_into.argtypes
+        L.jb_cut_device_full.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.POINTER(vp), C.POINTER(vp),
+                                         C.POINTER(vp), C.POINTER(vp)]
+        L.jb_cut_device_full_into.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp]
         L.jb_open_image.argtypes = [vp, C.POINTER(jb_config), C.POINTER(vp)]
         L.jb_cut_batch_mask.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.jb_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
@@ -330,6 +336,25 @@ class Tokenizer:
         s, e = self.cut_search_spans(text, useHmm)
         return spans_to_tokens(text, s.tolist(), e.tolist())
 
+    def cut_full_spans(self, text):
+        """jb_cut_full: every dictionary word of two or more runes in the text's Han blocks, by
+        start then length, and the single runes no such word accounts for (overlapping spans)."""
+        t = _b(text)
+        sp = jb_spans()
+        _check(lib().jb_cut_full(self.h, t, len(t), C.byref(sp)))
+        try:
+            n = sp.ntokens
+            s = np.ctypeslib.as_array(sp.start, (max(n, 1),))[:n].copy()
+            e = np.ctypeslib.as_array(sp.end, (max(n, 1),))[:n].copy()
+        finally:
+            lib().jb_spans_free(C.byref(sp))
+        return s, e
+
+    def CutAll(self, text):
+        """Full mode (jieba's cut_all=True on this reference's DAG, jiebahip.h)."""
+        s, e = self.cut_full_spans(text)
+        return spans_to_tokens(text, s.tolist(), e.tolist())
+
     def CutParallel(self, text, hmm, numWorkers=1, ordered=True):
         """Tokenizer.CutParallel (tokenizer.go:81): always in text order."""
         return self.Cut(text, hmm)
@@ -353,6 +378,23 @@ class Tokenizer:
     def cut_batch_search(self, buf, doc_off, hmm):
         """jb_cut_batch_search: cut_batch in search mode; doc_tok indexes the expanded spans."""
         return self.cut_batch(buf, doc_off, hmm, "jb_cut_batch_search")
+
+    def cut_batch_full(self, buf, doc_off):
+        """jb_cut_batch_full: cut_batch in full mode; doc_tok indexes the full-mode spans, which
+        may outnumber the bytes."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        nd = len(doc_off) - 1
+        sp = jb_spans()
+        _check(lib().jb_cut_batch_full(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, C.byref(sp)))
+        try:
+            n = sp.ntokens
+            s = np.ctypeslib.as_array(sp.start, (max(n, 1),))[:n].copy()
+            e = np.ctypeslib.as_array(sp.end, (max(n, 1),))[:n].copy()
+            d = np.ctypeslib.as_array(sp.doc_tok, (nd + 1,)).copy()
+        finally:
+            lib().jb_spans_free(C.byref(sp))
+        return s, e, d
 
     def cut_batch_into(self, buf, doc_off, hmm, out=None):
         """Host batch into caller-owned arrays (jb_cut_batch_into).  `out` =
@@ -430,6 +472,22 @@ class Tokenizer:
         """jb_cut_device_search_into: the expanded spans into caller-owned device arrays."""
         self.cut_device_into(d_text_ptr, nbytes, d_doc_off_ptr, ndocs, hmm, d_start, d_end, cap, d_doc_tok, d_ntok,
                              stream_ptr, "jb_cut_device_search_into")
+
+    def cut_device_full(self, d_text_ptr, nbytes, d_doc_off_ptr, ndocs, stream_ptr=0):
+        """jb_cut_device_full: cut_device in full mode.  The ctx-owned arrays hold nbytes spans; the
+        count and doc_tok describe the complete list (device_status reports JB_ELIMIT when it is longer)."""
+        a, b, c, d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().jb_cut_device_full(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_doc_off_ptr), ndocs,
+                                        C.c_void_p(stream_ptr), C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
+
+    def cut_device_full_into(self, d_text_ptr, nbytes, d_doc_off_ptr, ndocs, d_start, d_end, cap, d_doc_tok, d_ntok,
+                             stream_ptr=0):
+        """jb_cut_device_full_into: the full-mode spans into caller-owned device arrays of any
+        capacity; spans past it are counted, not written."""
+        _check(lib().jb_cut_device_full_into(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_doc_off_ptr), ndocs,
+                                             C.c_void_p(stream_ptr), C.c_void_p(d_start), C.c_void_p(d_end), cap,
+                                             C.c_void_p(d_doc_tok), C.c_void_p(d_ntok)))
 
     def cut_device_into(self, d_text_ptr, nbytes, d_doc_off_ptr, ndocs, hmm, d_start, d_end, cap, d_doc_tok, d_ntok,
                         stream_ptr=0, _fn="jb_cut_device_into"):
