@@ -257,6 +257,64 @@ int jb_cut_device_full_into(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes,
                             uint32_t ndocs, void *stream, uint32_t *d_start, uint32_t *d_end, uint64_t cap,
                             uint64_t *d_doc_tok, uint64_t *d_ntok);
 
+/* ---- token ids (the reference returns strings; a caller's next step numbers them) ------
+ * Every span of a span list looked up in a vocabulary of the caller's own, on the device: an
+ * embedding row, a term id, a stop-word flag.  The vocabulary is a list of byte strings, each
+ * 1..255 bytes of any content; a key's id is its index in the list.  It is not the dictionary:
+ * the trie holds only the all-Han keys buildDag can reach, so it cannot answer for "abc",
+ * "2024", "，" or a word the HMM made, and a model's vocabulary is not the segmentation
+ * dictionary.  The lookup is exact: the key's bytes are compared, not only their hash.
+ *
+ * The key of a span [s, e) is the bytes text[s..e), with one exception: a 1-byte span whose
+ * byte is >= 0x80 (an invalid UTF-8 byte, which the reference emits as "�") is looked up as
+ * EF BF BD.  The id is the key's index in the list, or JB_ID_UNK.
+ *
+ * jb_ids_device: d_start / d_end / d_ntok may be the ctx-owned results of any jb_cut_device*
+ * call or the caller's own arrays (of any mode: plain, search, full).  d_text is the text the
+ * spans index: nbytes bytes plus 64 readable padding bytes, as for jb_cut_device, 4-byte
+ * aligned.  The call writes d_ids[k] for k < min(*d_ntok, cap) and nothing else; *d_ntok is read
+ * on the device (in full mode it may exceed cap).  It queues one kernel on `stream` and returns:
+ * it does not synchronise, allocate or read anything on the host, and it does not use the
+ * per-device workspace, so it is safe from several threads and streams on one ctx (it holds the
+ * ctx's shared lock only while queuing).  Queue it on the stream the spans were produced on, or
+ * order the two streams yourself.
+ * The spans are not trusted: one with start >= end or end > nbytes gets JB_ID_UNK without a
+ * single text read (the kernel never reads outside [0, nbytes + 64)), and one longer than the
+ * vocabulary's longest key gets JB_ID_UNK without its bytes being read (a 1 MB alnum run is one
+ * token).
+ *
+ * jb_vocab_set builds the table, uploads it to ctx's first device and replaces any earlier one;
+ * keys == NULL with nkeys == 0 removes it (keys != NULL with nkeys == 0 attaches an empty
+ * vocabulary: every id is JB_ID_UNK).  It takes the exclusive lock and waits for all device work
+ * queued earlier on that device before it releases the old table, as jb_add_word does for the
+ * image.  On any error the old vocabulary stays attached.  The vocabulary is not part of
+ * jb_save, and jb_add_word does not touch it.
+ *
+ * Errors: JB_EINVAL without a vocabulary attached, for an empty key, for key_off that is not
+ * non-decreasing from 0 and for a duplicate key (the message names both indices); JB_ELIMIT for a
+ * key over 255 bytes and for nbytes >= 2 GiB.  jb_spans_ids is the convenience path for host
+ * spans: it uploads the byte range the spans cover and the spans as u32 to the first device,
+ * runs the same kernel and copies the ids back (JB_ELIMIT when that range is 2 GiB or more). */
+#define JB_ID_UNK 0xFFFFFFFFu
+typedef struct jb_vocab jb_vocab;
+/* Host only, no GPU needed (CPU tests): key i is keys[key_off[i] .. key_off[i+1]), key_off has
+ * nkeys + 1 entries.  nkeys == 0 is a valid, empty vocabulary. */
+int jb_vocab_build(const uint8_t *keys, const uint64_t *key_off, uint32_t nkeys, jb_vocab **out);
+void jb_vocab_free(jb_vocab *v);
+/* 1 found (*id set), 0 absent (*id = JB_ID_UNK): the device probe, on the host.  The bytes are
+ * looked up as they are (the invalid-byte rule above belongs to spans). */
+int jb_vocab_lookup(const jb_vocab *v, const uint8_t *tok, size_t len, uint32_t *id);
+/* keys, longest key in bytes, slots of the table (a power of two >= 2 * nkeys) */
+int jb_vocab_info(const jb_vocab *v, uint32_t *nkeys, uint32_t *maxlen, uint64_t *nslots);
+int jb_vocab_set(jb_ctx *ctx, const uint8_t *keys, const uint64_t *key_off, uint32_t nkeys);
+int64_t jb_vocab_size(jb_ctx *ctx); /* keys of the attached vocabulary; -1: none attached */
+/* ids of a device span list */
+int jb_ids_device(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uint32_t *d_start,
+                  const uint32_t *d_end, const uint64_t *d_ntok, uint64_t cap, void *stream, uint32_t *d_ids);
+/* ids of a host span list (any jb_spans the library returned for `text`): ids holds
+ * spans->ntokens entries. */
+int jb_spans_ids(jb_ctx *ctx, const uint8_t *text, const jb_spans *spans, uint32_t *ids);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

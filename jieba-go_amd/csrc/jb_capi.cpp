@@ -378,10 +378,20 @@ struct SpanBuf {
 
 }  // namespace
 
+struct jb_vocab {
+    Vocab v;
+};
+
 struct jb_ctx {
     std::unique_ptr<jb_image> im;
     std::vector<std::unique_ptr<Device>> devs;
     std::shared_mutex lock;  // prefixDictionary.lock: cuts share, AddWord excludes
+    // the caller's vocabulary (jb_vocab_set) and its copy on the first device; id calls read
+    // them under the shared lock, jb_vocab_set replaces them under the exclusive one
+    std::unique_ptr<Vocab> vocab;
+    uint32_t* d_vslots = nullptr;
+    uint8_t* d_vpool = nullptr;
+    DevVocab dvocab{};
 };
 
 // ---------------------------------------------------------------------------
@@ -1127,6 +1137,12 @@ extern "C" int jb_open(const jb_config* cfg, jb_ctx** out) {
 
 extern "C" void jb_close(jb_ctx* ctx) {
     if (!ctx) return;
+    if (ctx->vocab && !ctx->devs.empty()) {  // (k_ids may still be queued on a caller's stream)
+        (void)hipSetDevice(ctx->devs[0]->ordinal);
+        (void)hipDeviceSynchronize();
+        dfree(ctx->d_vslots);
+        dfree(ctx->d_vpool);
+    }
     for (auto& d : ctx->devs) {
         if (const char* tp = getenv("JB_SMALL_TRACE"); tp && !d->small_trace.empty())
             if (FILE* f = fopen(tp, "a")) {
@@ -2975,4 +2991,169 @@ extern "C" int jb_profile_read(jb_ctx* ctx, const char** names, double* ms, uint
         if (launches) launches[n] = tot_n[k];
     }
     return n;
+}
+
+// ---------------------------------------------------------------------------
+// token ids: a caller's vocabulary (jb_vocab.h) and the lookup of span lists in it
+// ---------------------------------------------------------------------------
+extern "C" int jb_vocab_build(const uint8_t* keys, const uint64_t* key_off, uint32_t nkeys, jb_vocab** out) {
+    if (!out) return fail(JB_EINVAL, "jb_vocab_build: null argument");
+    *out = nullptr;
+    try {
+        auto v = std::make_unique<jb_vocab>();
+        std::string err;
+        const int rc = vocab_build(keys, key_off, nkeys, &v->v, &err);
+        if (rc) return fail(rc, "%s", err.c_str());
+        *out = v.release();
+    } catch (const std::bad_alloc&) {
+        return fail(JB_ENOMEM, "out of host memory building the vocabulary");
+    }
+    return JB_OK;
+}
+
+extern "C" void jb_vocab_free(jb_vocab* v) { delete v; }
+
+extern "C" int jb_vocab_lookup(const jb_vocab* v, const uint8_t* tok, size_t len, uint32_t* id) {
+    if (!v || (!tok && len)) return fail(JB_EINVAL, "jb_vocab_lookup: null argument");
+    const uint32_t r = vocab_lookup(v->v, tok, len);
+    if (id) *id = r;
+    return r != JB_VOCAB_UNK;
+}
+
+extern "C" int jb_vocab_info(const jb_vocab* v, uint32_t* nkeys, uint32_t* maxlen, uint64_t* nslots) {
+    if (!v) return fail(JB_EINVAL, "jb_vocab_info: null vocabulary");
+    if (nkeys) *nkeys = v->v.nkeys;
+    if (maxlen) *maxlen = v->v.maxlen;
+    if (nslots) *nslots = v->v.nslots;
+    return JB_OK;
+}
+
+static_assert(JB_ID_UNK == JB_VOCAB_UNK, "the header's unknown id is the table's");
+
+extern "C" int jb_vocab_set(jb_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, uint32_t nkeys) {
+    if (!ctx) return fail(JB_EINVAL, "jb_vocab_set: null ctx");
+    const bool remove = !keys && nkeys == 0;
+    std::unique_ptr<Vocab> nv;
+    if (!remove) {  // built aside: on any error the old vocabulary stays attached
+        try {
+            nv = std::make_unique<Vocab>();
+            std::string err;
+            const int rc = vocab_build(keys, key_off, nkeys, nv.get(), &err);
+            if (rc) return fail(rc, "%s", err.c_str());
+        } catch (const std::bad_alloc&) {
+            return fail(JB_ENOMEM, "out of host memory building the vocabulary");
+        }
+    }
+    std::unique_lock<std::shared_mutex> wl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    uint32_t* ns = nullptr;
+    uint8_t* np = nullptr;
+    if (nv) {
+        hipError_t e = hipMalloc(&ns, nv->slots.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&np, nv->pool.size());
+        if (e == hipSuccess) e = hipMemcpy(ns, nv->slots.data(), nv->slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(np, nv->pool.data(), nv->pool.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            dfree(ns);
+            dfree(np);
+            return fail(JB_EDEVICE, "jb_vocab_set: uploading the table: %s", hipGetErrorString(e));
+        }
+    }
+    // the old table may be in use by id kernels queued earlier, on any stream of the device
+    if (ctx->vocab) (void)hipDeviceSynchronize();
+    dfree(ctx->d_vslots);
+    dfree(ctx->d_vpool);
+    ctx->d_vslots = ns;
+    ctx->d_vpool = np;
+    ctx->vocab = std::move(nv);
+    ctx->dvocab = ctx->vocab ? DevVocab{ns, np, (uint32_t)(ctx->vocab->nslots - 1u), ctx->vocab->maxlen} : DevVocab{};
+    return JB_OK;
+}
+
+extern "C" int64_t jb_vocab_size(jb_ctx* ctx) {
+    if (!ctx) return -1;
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    return ctx->vocab ? (int64_t)ctx->vocab->nkeys : -1;
+}
+
+extern "C" int jb_ids_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
+                             const uint32_t* d_end, const uint64_t* d_ntok, uint64_t cap, void* stream,
+                             uint32_t* d_ids) {
+    if (!ctx || (!d_text && nbytes) || !d_ntok || (cap && (!d_start || !d_end || !d_ids)))
+        return fail(JB_EINVAL, "jb_ids_device: null argument");
+    if (nbytes >= (1ull << 31)) return fail(JB_ELIMIT, "device batch of %llu bytes (limit 2 GiB)",
+                                            (unsigned long long)nbytes);
+    if (((uintptr_t)d_text & 3u) != 0) return fail(JB_EINVAL, "d_text must be 4-byte aligned");
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    if (!ctx->vocab) return fail(JB_EINVAL, "jb_ids_device: no vocabulary attached (jb_vocab_set)");
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_ids(ctx->dvocab, d_text, nbytes, d_start, d_end, d_ntok, cap, d_ids, d->ncu, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_ids(ctx->dvocab, d_text, nbytes, d_start, d_end, d_ntok, cap, d_ids, d->ncu, s, nullptr));
+    return JB_OK;
+}
+
+extern "C" int jb_spans_ids(jb_ctx* ctx, const uint8_t* text, const jb_spans* spans, uint32_t* ids) {
+    if (!ctx || !spans || (spans->ntokens && (!text || !spans->start || !spans->end || !ids)))
+        return fail(JB_EINVAL, "jb_spans_ids: null argument");
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    if (!ctx->vocab) return fail(JB_EINVAL, "jb_spans_ids: no vocabulary attached (jb_vocab_set)");
+    const uint64_t n = spans->ntokens;
+    if (n == 0) return JB_OK;
+    // the byte range the spans cover (empty and reversed spans cover nothing: they are unknown)
+    uint64_t lo = UINT64_MAX, hi = 0;
+    for (uint64_t k = 0; k < n; k++)
+        if (spans->start[k] < spans->end[k]) {
+            lo = std::min(lo, spans->start[k]);
+            hi = std::max(hi, spans->end[k]);
+        }
+    if (lo > hi) lo = hi = 0;
+    const uint64_t nb = hi - lo;
+    if (nb >= (1ull << 31))
+        return fail(JB_ELIMIT, "the spans cover %llu bytes (limit 2 GiB)", (unsigned long long)nb);
+    std::vector<uint32_t> se;
+    try {
+        se.resize(2 * n);
+    } catch (const std::bad_alloc&) {
+        return fail(JB_ENOMEM, "out of host memory for %llu spans", (unsigned long long)n);
+    }
+    for (uint64_t k = 0; k < n; k++) {
+        const bool ok = spans->start[k] < spans->end[k];
+        se[k] = ok ? (uint32_t)(spans->start[k] - lo) : 0u;
+        se[n + k] = ok ? (uint32_t)(spans->end[k] - lo) : 0u;
+    }
+    Device* d = ctx->devs[0].get();
+    std::lock_guard<std::mutex> g(d->mu);  // (d->stream and the timer)
+    HIPCHK(hipSetDevice(d->ordinal));
+    uint8_t* dt = nullptr;
+    uint32_t *dse = nullptr, *did = nullptr;
+    uint64_t* dn = nullptr;
+    auto run = [&]() -> int {
+        HIPCHK(hipMalloc(&dt, nb + 64));
+        HIPCHK(hipMalloc(&dse, 2 * n * sizeof(uint32_t)));
+        HIPCHK(hipMalloc(&did, n * sizeof(uint32_t)));
+        HIPCHK(hipMalloc(&dn, sizeof(uint64_t)));
+        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, d->stream));
+        if (nb) HIPCHK(hipMemcpyAsync(dt, text + lo, nb, hipMemcpyHostToDevice, d->stream));
+        HIPCHK(hipMemcpyAsync(dse, se.data(), 2 * n * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+        HIPCHK(hipMemcpyAsync(dn, &n, sizeof n, hipMemcpyHostToDevice, d->stream));
+        HIPCHK(run_ids(ctx->dvocab, dt, nb, dse, dse + n, dn, n, did, d->ncu, d->stream,
+                       d->profile ? &d->timer : nullptr));
+        HIPCHK(hipMemcpyAsync(ids, did, n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+        return JB_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(d->stream);  // (copies from `se` may be in flight)
+    dfree(dt);
+    dfree(dse);
+    dfree(did);
+    dfree(dn);
+    return rc;
 }

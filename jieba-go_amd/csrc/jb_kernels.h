@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "jb_common.h"
+#include "jb_vocab.h"
 
 namespace jb {
 
@@ -121,7 +122,7 @@ enum KernelId {
     K_DOCBITS = 0, K_MARK_WALK, K_ZH, K_NONZH,
     K_TOK_COUNT, K_SCAN_TOK, K_TOK_WRITE, K_DOC_TOK, K_LONG_SPEC, K_LONG_DP, K_LONG_SEG, K_LONG_PATH, K_LONG_TAIL, K_MASK_MERGE,
     K_LONG_PBITS, K_LONG, K_TOK1, K_SRCH_COUNT, K_SRCH_SCAN, K_SRCH_WRITE, K_SRCH_DOC,
-    K_FULL_COUNT, K_FULL_SCAN, K_FULL_WRITE, K_FULL_DOC,
+    K_FULL_COUNT, K_FULL_SCAN, K_FULL_WRITE, K_FULL_DOC, K_IDS,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -229,6 +230,18 @@ struct FullOut {
 // Enqueue the full-mode pass on `stream`, after run_pipeline's kernels (hmm = false) for the same batch.
 hipError_t run_full(const DevImage& im, const Work& w, const FullOut& fo, const uint8_t* d_text, uint64_t nbytes,
                     uint32_t ndocs, hipStream_t stream, KernelTimer* timer);
+
+// Token ids (jb_ids_device, jb_spans_ids): every span of a device span list looked up in the ctx's
+// vocabulary (jb_vocab.h), one lane per span.  The device copy of the table, passed by value:
+using DevVocab = JbVocabView;
+constexpr uint32_t kIdsTile = 256;     // spans per workgroup and trip: thread t owns spans j * 256 + t
+constexpr uint32_t kIdsWgPerCu = 8;    // the fixed grid: 8 workgroups of 4 waves fill a CU's 32 wave slots
+// Enqueue k_ids on `stream`: ids[k] for k < min(*d_ntok, cap), read on the device; nothing else is
+// written and no text byte outside [0, nbytes) + 64 is read, whatever the spans hold.  d_text is
+// 4-byte aligned.  A grid of at most ncu * kIdsWgPerCu workgroups loops over the tiles.
+hipError_t run_ids(const DevVocab& v, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
+                   const uint32_t* d_end, const uint64_t* d_ntok, uint64_t cap, uint32_t* d_ids, uint32_t ncu,
+                   hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

@@ -43,7 +43,7 @@ const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_
                                          "k_tok_write", "k_doc_tok", "k_long_spec", "k_long_dp", "k_long_seg", "k_long_path",
                                          "k_long_tail", "k_mask_merge", "k_long_pbits", "k_long", "k_tok1", "k_srch_count",
                                          "k_srch_scan", "k_srch_write", "k_srch_doc", "k_full_count", "k_full_scan",
-                                         "k_full_write", "k_full_doc"};
+                                         "k_full_write", "k_full_doc", "k_ids"};
 
 // newJiebaHMM literals (tokenizer.go:629-652)
 #define START_B (-0.26268660809250016)
@@ -6533,6 +6533,89 @@ hipError_t run_full(const DevImage& im, const Work& w, const FullOut& fo, const 
                                               fo.cap, fo.ntok));
     JB_TIMED(K_FULL_DOC, hipLaunchKernelGGL(k_full_doc, dim3((ndocs + 1u + 255u) / 256u), dim3(256), 0, stream,
                                             w.doc_tok, ndocs, w.counters, fo.off, fo.tbase, fo.doc_tok));
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Token ids: every span of a span list looked up in the caller's vocabulary (jb_vocab.h).
+// One lane per span, tiles of kIdsTile consecutive spans (coalesced span loads and id
+// stores; neighbouring spans are neighbouring text, so a wave's text reads share lines).
+// The span count is on the device, so a fixed grid loops over the tiles.  A lane reads its
+// token's bytes into registers (8, 16 or 24 of them by its length, from aligned dwords),
+// hashes them and probes: jb_vocab_find, the host lookup's code.  No atomics, no waits.
+// ---------------------------------------------------------------------------
+// Bytes [4 w, 4 w + 4) of a key of len bytes that are inside it, as a mask over the word.
+__device__ __forceinline__ uint32_t ids_word_mask(uint32_t len, uint32_t w) {
+    if (len >= 4u * w + 4u) return 0xFFFFFFFFu;
+    return len > 4u * w ? (1u << (8u * (len - 4u * w))) - 1u : 0u;
+}
+
+// The id of the span [s, e) of the text.  The spans are not trusted: one that is empty, reversed
+// or past nbytes, or longer than the longest key, is unknown without a text read; every other
+// read lies in [s & ~3, s + 28) with s < nbytes, or inside the span.
+__device__ __forceinline__ uint32_t ids_one(const uint8_t* __restrict__ text, uint32_t nbytes, const DevVocab& v,
+                                            uint32_t s, uint32_t e) {
+    if (s >= e || e > nbytes) return JB_VOCAB_UNK;
+    uint32_t len = e - s;
+    if (len > v.maxlen) return JB_VOCAB_UNK;
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(text + (s & ~3u));
+    const uint32_t sh = s & 3u;
+    uint32_t kw[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    const uint32_t d0 = a[0], d1 = a[1], d2 = a[2];
+    kw[0] = __builtin_amdgcn_alignbyte(d1, d0, sh);
+    kw[1] = __builtin_amdgcn_alignbyte(d2, d1, sh);
+    if (len > 8u) {
+        const uint32_t d3 = a[3], d4 = a[4];
+        kw[2] = __builtin_amdgcn_alignbyte(d3, d2, sh);
+        kw[3] = __builtin_amdgcn_alignbyte(d4, d3, sh);
+        if (len > 16u) {
+            const uint32_t d5 = a[5], d6 = a[6];
+            kw[4] = __builtin_amdgcn_alignbyte(d5, d4, sh);
+            kw[5] = __builtin_amdgcn_alignbyte(d6, d5, sh);
+        }
+    }
+    // a 1-byte span whose byte is >= 0x80 is an invalid UTF-8 byte: the token is "\xEF\xBF\xBD"
+    if (len == 1u && (kw[0] & 0x80u)) {
+        kw[0] = 0x00BDBFEFu;
+        kw[1] = 0u;
+        len = 3u;
+    } else {
+#pragma unroll
+        for (uint32_t w = 0; w < 6u; w++) kw[w] &= ids_word_mask(len, w);
+    }
+    return jb_vocab_find(v, kw, text + s, len);
+}
+
+__global__ __launch_bounds__(256) JB_SRCH_ATTR void k_ids(const uint8_t* __restrict__ text, uint32_t nbytes, DevVocab v,
+                                                          const uint32_t* __restrict__ ts,
+                                                          const uint32_t* __restrict__ te,
+                                                          const uint64_t* __restrict__ ntok, uint64_t cap,
+                                                          uint32_t* __restrict__ ids) {
+    const uint64_t n = std::min(*ntok, cap), step = (uint64_t)gridDim.x * kIdsTile;
+    uint64_t i = (uint64_t)blockIdx.x * kIdsTile + threadIdx.x;
+    uint32_t s1 = 0, e1 = 0;  // the next span, loaded one trip ahead
+    if (i < n) {
+        s1 = ts[i];
+        e1 = te[i];
+    }
+    for (; i < n; i += step) {
+        const uint32_t s = s1, e = e1;
+        if (i + step < n) {
+            s1 = ts[i + step];
+            e1 = te[i + step];
+        }
+        ids[i] = ids_one(text, nbytes, v, s, e);
+    }
+}
+
+hipError_t run_ids(const DevVocab& v, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
+                   const uint32_t* d_end, const uint64_t* d_ntok, uint64_t cap, uint32_t* d_ids, uint32_t ncu,
+                   hipStream_t stream, KernelTimer* timer) {
+    if (cap == 0) return hipSuccess;  // (nothing to write)
+    const uint64_t tiles = (cap + kIdsTile - 1u) / kIdsTile;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)std::max(1u, ncu) * kIdsWgPerCu);
+    JB_TIMED(K_IDS, hipLaunchKernelGGL(k_ids, dim3(grid), dim3(256), 0, stream, d_text, (uint32_t)nbytes, v, d_start,
+                                       d_end, d_ntok, cap, d_ids));
     return hipGetLastError();
 }
 

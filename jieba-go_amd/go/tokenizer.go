@@ -268,6 +268,80 @@ func (t *Tokenizer) CutAll(text string) []string {
 	return spansToTokens(text, &s, 0)
 }
 
+// IDUnknown is the id of a token that is not in the vocabulary (JB_ID_UNK).
+const IDUnknown = ^uint32(0)
+
+// SetVocab attaches the caller's vocabulary (jb_vocab_set in jiebahip.h): a key's id is its
+// index in keys; keys are 1..255 bytes each and distinct.  It replaces any earlier vocabulary;
+// nil removes it, an empty non-nil slice attaches an empty one.  On an error the old one stays.
+func (t *Tokenizer) SetVocab(keys []string) error {
+	t.mu.Lock()
+	defer t.mu.Unlock()
+	if keys == nil {
+		if rc := C.jb_vocab_set(t.ctx, nil, nil, 0); rc != C.JB_OK {
+			return errors.New("jiebahip: " + lastError())
+		}
+		return nil
+	}
+	buf := make([]byte, 0, 16)
+	off := make([]uint64, len(keys)+1)
+	for i, k := range keys {
+		buf = append(buf, k...)
+		off[i+1] = uint64(len(buf))
+	}
+	buf = append(buf, 0)
+	if rc := C.jb_vocab_set(t.ctx, (*C.uint8_t)(unsafe.Pointer(&buf[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+		C.uint32_t(len(keys))); rc != C.JB_OK {
+		return errors.New("jiebahip: " + lastError())
+	}
+	return nil
+}
+
+// CutIds is Cut (mode "cut"), CutForSearch ("search") or CutAll ("full", useHmm ignored) with
+// each token's id in the attached vocabulary, looked up on the GPU (jb_spans_ids): IDUnknown
+// for a token that is not a key.  With mini_dict.txt and the vocabulary abc, 今天, "�", 一刹那,
+// 刹那, 这, 天天, CutIds("abc \xff今天天氣 这一刹那", false, "cut") is abc, �, 今天, 天, 氣, 这,
+// 一刹那 with ids 0, 2, 1, unknown, unknown, 5, 3 (tests/c_abi_ids.c).  Never returns nil.
+func (t *Tokenizer) CutIds(text string, useHmm bool, mode string) ([]string, []uint32) {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	if len(text) == 0 {
+		return []string{}, []uint32{}
+	}
+	b := []byte(text)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	off := []uint64{0, uint64(len(b))}
+	tp := (*C.uint8_t)(unsafe.Pointer(&b[0]))
+	op := (*C.uint64_t)(unsafe.Pointer(&off[0]))
+	var s C.jb_spans
+	var rc C.int
+	switch mode {
+	case "cut":
+		rc = C.jb_cut_batch(t.ctx, tp, op, 1, hmm, &s)
+	case "search":
+		rc = C.jb_cut_batch_search(t.ctx, tp, op, 1, hmm, &s)
+	case "full":
+		rc = C.jb_cut_batch_full(t.ctx, tp, op, 1, &s)
+	default:
+		panic("jiebahip: CutIds mode " + mode + ": one of cut, search, full")
+	}
+	if rc != C.JB_OK {
+		// JB_EPANIC: the reference panics on this input (cutDAG slice with tail -1)
+		panic("jiebahip: " + lastError())
+	}
+	defer C.jb_spans_free(&s)
+	ids := make([]uint32, int(s.ntokens))
+	if len(ids) > 0 {
+		if rc := C.jb_spans_ids(t.ctx, tp, &s, (*C.uint32_t)(unsafe.Pointer(&ids[0]))); rc != C.JB_OK {
+			panic("jiebahip: " + lastError()) // JB_EINVAL: no vocabulary attached
+		}
+	}
+	return spansToTokens(text, &s, 0), ids
+}
+
 // CutParallel (tokenizer.go:81) returns the tokens of Cut in document order.
 // The library splits the work itself: the text goes to the device in pieces cut
 // at Han-run starts (jb_split_points), and over every device of a multi-device

@@ -85,6 +85,37 @@ std::vector<std::string> Tokenizer::CutAll(const std::string& text) {
     return out;
 }
 
+void Tokenizer::SetVocab(const std::vector<std::string>& keys) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& k : keys) {
+        all += k;
+        off.push_back(all.size());
+    }
+    // (keys.data() of an empty list may be null, which would remove the vocabulary: pass a byte)
+    check(jb_vocab_set(ctx_, (const uint8_t*)(all.empty() ? "" : all.data()), off.data(), (uint32_t)keys.size()));
+}
+
+std::vector<std::string> Tokenizer::CutIds(const std::string& text, bool useHmm, std::vector<uint32_t>* ids,
+                                           Mode mode) {
+    jb_spans sp;
+    const uint8_t* t = (const uint8_t*)text.data();
+    if (mode == Mode::Full) check(jb_cut_full(ctx_, t, text.size(), &sp));
+    else if (mode == Mode::Search) check(jb_cut_search(ctx_, t, text.size(), useHmm ? 1 : 0, &sp));
+    else check(jb_cut(ctx_, t, text.size(), useHmm ? 1 : 0, &sp));
+    std::vector<std::string> out;
+    out.reserve(sp.ntokens);
+    for (uint64_t k = 0; k < sp.ntokens; k++) out.push_back(token_at(text, sp.start[k], sp.end[k]));
+    int rc = JB_OK;
+    if (ids) {
+        ids->assign(sp.ntokens, JB_ID_UNK);
+        rc = jb_spans_ids(ctx_, t, &sp, ids->data());
+    }
+    jb_spans_free(&sp);
+    check(rc);
+    return out;
+}
+
 std::vector<std::string> Tokenizer::CutParallel(const std::string& text, bool hmm, int, bool) {
     return Cut(text, hmm);
 }

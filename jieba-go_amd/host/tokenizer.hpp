@@ -54,6 +54,14 @@ public:
     // included, and the single runes that no such word accounts for; non-Han text as Cut cuts
     // it (jb_cut_full in jiebahip.h, with its three differences from Python jieba).
     std::vector<std::string> CutAll(const std::string& text);
+    // Token ids (jb_vocab_set / jb_spans_ids in jiebahip.h): attach the caller's vocabulary (a key's
+    // id is its index; 1..255 bytes each, no duplicates), replacing any earlier one.
+    void SetVocab(const std::vector<std::string>& keys);
+    enum class Mode { Cut, Search, Full };
+    // Cut / CutForSearch / CutAll (full mode ignores useHmm) with each token's id in the attached
+    // vocabulary, JB_ID_UNK when it is not there; looked up on the GPU.
+    std::vector<std::string> CutIds(const std::string& text, bool useHmm, std::vector<uint32_t>* ids,
+                                    Mode mode = Mode::Cut);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

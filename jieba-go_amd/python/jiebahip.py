@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("JB_LIB") or os.path.join(PKG_DIR, "lib", "libjiebahip
 JB_OK, JB_EINVAL, JB_EIO, JB_EPARSE, JB_EDEVICE, JB_ENOMEM, JB_EPANIC, JB_ELIMIT = 0, -1, -2, -3, -4, -5, -6, -7
 JB_DICT_TXT, JB_DICT_PREFIX, JB_DICT_GOB, JB_DICT_IMAGE = 0, 1, 2, 3
 JIEBA_SIZE = 60_101_967  # tokenizer.go:454
+JB_ID_UNK = 0xFFFFFFFF  # the id of a token that is not in the vocabulary
 
 # Every symbol include/jiebahip.h declares.
 EXPORTS = [
@@ -34,6 +35,8 @@ EXPORTS = [
     "jb_suggest_freq", "jb_add_log", "jb_image_log_keys", "jb_device_status", "jb_cut_batch_into32",
     "jb_cut_search", "jb_cut_batch_search", "jb_cut_device_search", "jb_cut_device_search_into",
     "jb_cut_full", "jb_cut_batch_full", "jb_cut_device_full", "jb_cut_device_full_into",
+    "jb_vocab_build", "jb_vocab_free", "jb_vocab_lookup", "jb_vocab_info", "jb_vocab_set", "jb_vocab_size",
+    "jb_ids_device", "jb_spans_ids",
 ]
 
 
@@ -142,6 +145,16 @@ def lib():
         L.jb_device_status.argtypes = [vp, vp]
         L.jb_cut_batch_into32.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp, C.c_uint64, vp,
                                           C.POINTER(C.c_uint64)]
+        L.jb_vocab_build.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
+        L.jb_vocab_free.argtypes = [vp]
+        L.jb_vocab_free.restype = None
+        L.jb_vocab_lookup.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.jb_vocab_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.jb_vocab_set.argtypes = [vp, vp, vp, C.c_uint32]
+        L.jb_vocab_size.argtypes = [vp]
+        L.jb_vocab_size.restype = C.c_int64
+        L.jb_ids_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp]
+        L.jb_spans_ids.argtypes = [vp, vp, C.POINTER(jb_spans), vp]
         _lib = L
     return _lib
 
@@ -252,6 +265,51 @@ class Image:
         n, sz = C.c_uint64(), C.c_int64()
         _check(lib().jb_image_dict_info(self.h, C.byref(n), C.byref(sz)))
         return n.value, sz.value
+
+
+def pack_keys(keys):
+    """A list of str / bytes keys -> (bytes uint8, key_off uint64[nkeys + 1]) as jb_vocab_build takes them."""
+    ks = [_b(k) for k in keys]
+    off = np.zeros(len(ks) + 1, np.uint64)
+    if ks:
+        off[1:] = np.cumsum([len(k) for k in ks], dtype=np.uint64)
+    buf = np.frombuffer(b"".join(ks) + b"\0", np.uint8)  # (never an empty array: its pointer is passed)
+    return buf, off
+
+
+class Vocab:
+    """Host-only vocabulary table (no GPU needed): the builder and the device probe on the host.
+    `keys` is a list of str / bytes, or a (bytes, key_off) pair; a key's id is its index."""
+
+    def __init__(self, keys=None, packed=None):
+        buf, off = packed if packed is not None else pack_keys(keys)
+        buf = np.ascontiguousarray(buf, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        h = C.c_void_p()
+        _check(lib().jb_vocab_build(buf.ctypes.data, off.ctypes.data, len(off) - 1, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            lib().jb_vocab_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def lookup(self, tok):
+        """The key's id, or None."""
+        t = _b(tok)
+        i = C.c_uint32()
+        return i.value if _check(lib().jb_vocab_lookup(self.h, t, len(t), C.byref(i))) else None
+
+    def info(self):
+        n, ml, ns = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _check(lib().jb_vocab_info(self.h, C.byref(n), C.byref(ml), C.byref(ns)))
+        return dict(nkeys=n.value, maxlen=ml.value, nslots=ns.value)
 
 
 class Tokenizer:
@@ -495,6 +553,56 @@ class Tokenizer:
         _check(getattr(lib(), _fn)(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_doc_off_ptr), ndocs,
                                         int(hmm), C.c_void_p(stream_ptr), C.c_void_p(d_start), C.c_void_p(d_end),
                                         cap, C.c_void_p(d_doc_tok), C.c_void_p(d_ntok)))
+
+    # -- token ids -------------------------------------------------------
+    def set_vocab(self, keys, packed=None):
+        """jb_vocab_set: attach a vocabulary (a list of str / bytes; a key's id is its index), replacing
+        any earlier one.  None removes it; an empty list attaches an empty vocabulary."""
+        if keys is None and packed is None:
+            _check(lib().jb_vocab_set(self.h, None, None, 0))
+            return
+        buf, off = packed if packed is not None else pack_keys(keys)
+        buf = np.ascontiguousarray(buf, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        _check(lib().jb_vocab_set(self.h, buf.ctypes.data, off.ctypes.data, len(off) - 1))
+
+    @property
+    def vocab_size(self):
+        """Keys of the attached vocabulary; -1 when none is attached."""
+        return lib().jb_vocab_size(self.h)
+
+    def spans_ids(self, text, starts, ends):
+        """jb_spans_ids: the ids (uint32, JB_ID_UNK when absent) of host spans of `text` (str, bytes or
+        a uint8 array)."""
+        t = np.ascontiguousarray(text, np.uint8) if isinstance(text, np.ndarray) else np.frombuffer(
+            _b(text) + b"\0", np.uint8)
+        s = np.ascontiguousarray(starts, np.uint64)
+        e = np.ascontiguousarray(ends, np.uint64)
+        sp = jb_spans()
+        sp.ntokens = len(s)
+        sp.start = s.ctypes.data_as(C.POINTER(C.c_uint64))
+        sp.end = e.ctypes.data_as(C.POINTER(C.c_uint64))
+        ids = np.empty(len(s), np.uint32)
+        _check(lib().jb_spans_ids(self.h, t.ctypes.data, C.byref(sp), ids.ctypes.data))
+        return ids
+
+    def ids_device(self, d_text_ptr, nbytes, d_start, d_end, d_ntok, cap, d_ids, stream_ptr=0):
+        """jb_ids_device over raw device pointers: d_ids[k] for k < min(*d_ntok, cap); queued on the stream."""
+        _check(lib().jb_ids_device(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_start), C.c_void_p(d_end),
+                                   C.c_void_p(d_ntok), cap, C.c_void_p(stream_ptr), C.c_void_p(d_ids)))
+
+    def CutIds(self, text, useHmm, mode="cut"):
+        """Cut / CutForSearch / CutAll (mode "cut", "search", "full"; full mode ignores useHmm) and the
+        tokens' ids in the attached vocabulary: (tokens, ids uint32)."""
+        if mode == "cut":
+            s, e = self.cut_spans(text, useHmm)
+        elif mode == "search":
+            s, e = self.cut_search_spans(text, useHmm)
+        elif mode == "full":
+            s, e = self.cut_full_spans(text)
+        else:
+            raise ValueError(f"mode {mode!r}: one of 'cut', 'search', 'full'")
+        return spans_to_tokens(text, s.tolist(), e.tolist()), self.spans_ids(text, s, e)
 
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
