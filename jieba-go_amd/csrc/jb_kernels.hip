@@ -5942,7 +5942,8 @@ __device__ __forceinline__ uint32_t srch_next(const uint8_t* __restrict__ text, 
 __device__ __forceinline__ uint32_t srch_rune(const uint8_t* __restrict__ text, uint32_t p) {  // valid UTF-8, 3 or 4 bytes
     const uint32_t x = ld4(text, p), b0 = x & 0xFFu;
     const uint32_t r3 = ((b0 & 0x0Fu) << 12) | (((x >> 8) & 0x3Fu) << 6) | ((x >> 16) & 0x3Fu);
-    const uint32_t r4 = ((b0 & 0x07u) << 18) | (((x >> 8) & 0x3Fu) << 12) | (((x >> 16) & 0x3Fu) << 6) | (x >> 24);
+    const uint32_t r4 = ((b0 & 0x07u) << 18) | (((x >> 8) & 0x3Fu) << 12) | (((x >> 16) & 0x3Fu) << 6) |
+                        ((x >> 24) & 0x3Fu);
     return b0 >= 0xF0u ? r4 : r3;
 }
 // bit 0: E(i, 2), bit 1: E(i, 3) for the rune at a, whose next two runes start at b and (third
