@@ -1,5 +1,5 @@
 // Test harness (tests/test_unpack.py): the library's packed-span decoder, compiled on the
-// CPU with stand-ins for the few names it uses from jb_capi.cpp / jb_kernels.h.
+// CPU with stand-ins for the few names it uses from jb_device.cpp / jb_kernels.h.
 #include <immintrin.h>
 #include <stdint.h>
 #include <algorithm>

@@ -167,7 +167,7 @@ def exact_batch(o, corpus, target, hmm, share, fill_doc=4096):
 
 
 def pieces(doc_off, piece_bytes):
-    """cut_range's greedy rule: pieces of whole documents of at most piece_bytes bytes (a longer document
+    """plan_pieces' greedy rule (jb_plan.cpp): pieces of whole documents of at most piece_bytes bytes (a longer document
     is a piece of its own) -> [(first document, one past the last)]."""
     off = [int(x) for x in doc_off]
     out, a, n = [], 0, len(off) - 1

@@ -4,7 +4,7 @@ Two programs, each built here with -fsanitize=address,undefined -fno-sanitize-re
 - tests/host/image_fuzz.cpp over jieba-go_amd/csrc/jb_image.cpp (the dict.txt, gob and emission
   parsers, the image builder, its hot rows, save/load, lookups), one full pass on the synthetic
   dictionary and then mutation rounds against every parser and the image loader;
-- the packed-spans decoder of jb_capi.cpp in its test harness (tests/test_unpack.py's program).
+- the packed-spans decoder of jb_hostbatch.cpp in its test harness (tests/test_unpack.py's program).
 A report from either sanitizer fails the run.  (The GPU kernels cannot run under a sanitizer on
 this pool; the host code they are fed by can.)"""
 import os
@@ -50,7 +50,7 @@ def test_image_code_under_asan_ubsan(tmp_path, syn_small):
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="no clang")
 def test_span_decoder_under_asan_ubsan(tmp_path):
-    src = open(os.path.join(ROOT, "jieba-go_amd", "csrc", "jb_capi.cpp")).read()
+    src = open(os.path.join(ROOT, "jieba-go_amd", "csrc", "jb_hostbatch.cpp")).read()
     a = src.index("// One token of a packed piece")
     b = src.index("// Text already in pinned memory (jb_host_alloc)")
     h = os.path.join(ROOT, "tests", "host")

@@ -1,5 +1,5 @@
-"""The host half of the packed spans (jb_capi.cpp unpack_spans): the decoder's
-source is cut out of jb_capi.cpp, compiled on the CPU with stand-ins for the few library
+"""The host half of the packed spans (jb_hostbatch.cpp unpack_spans): the decoder's
+source is cut out of jb_hostbatch.cpp, compiled on the CPU with stand-ins for the few library
 names it uses (tests/host/unpack_harness_*.cpp), and run on random spans with escaped gaps
 and lengths, escapes in bulk and none, outputs misaligned against each other and aligned
 alike: the AVX-512 path (where the CPU has it) and the scalar path (JB_DECODE_AVX512=0)
@@ -16,7 +16,7 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 
 @pytest.mark.skipif(not os.path.exists(CLANG) and not shutil.which("clang++"), reason="no clang")
 def test_unpack_spans_paths(tmp_path):
-    src = open(os.path.join(ROOT, "jieba-go_amd", "csrc", "jb_capi.cpp")).read()
+    src = open(os.path.join(ROOT, "jieba-go_amd", "csrc", "jb_hostbatch.cpp")).read()
     a = src.index("// One token of a packed piece")
     b = src.index("// Text already in pinned memory (jb_host_alloc)")
     h = os.path.join(ROOT, "tests", "host")
