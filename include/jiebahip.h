@@ -315,6 +315,82 @@ int jb_ids_device(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uin
  * spans->ntokens entries. */
 int jb_spans_ids(jb_ctx *ctx, const uint8_t *text, const jb_spans *spans, uint32_t *ids);
 
+/* ---- term counts and keywords (jieba.analyse.extract_tags; the reference has only Cut) ------
+ * A document's distinct terms with their counts (the document-term matrix, as CSR), and the topk
+ * terms of each document by count x weight, on the device: a caller who wants keywords never
+ * pays for writing spans or ids back to the host.
+ *
+ * jb_terms_device.  d_ids is an id list of any mode (jb_ids_device's output or the caller's own)
+ * with ids_cap valid entries; d_doc_tok (u64[ndocs + 1]) and d_ntok (u64, read on the device) are
+ * those of the jb_cut_device* call whose spans the ids belong to.
+ *  - Token k takes part iff k < min(*d_ntok, ids_cap) and d_ids[k] != JB_ID_UNK.  Document d's
+ *    tokens are [doc_tok[d], doc_tok[d+1]) clamped to that bound (full mode's list may be longer
+ *    than the id array).  doc_tok is non-decreasing.
+ *  - Document d's terms are the distinct ids among its tokens, ascending by id, each with its
+ *    count: d_term_id / d_term_cnt at [term_off[d], term_off[d+1]).  *d_nterms == term_off[ndocs].
+ *  - Capacity, as in full mode: d_term_off (u64[ndocs + 1]) and *d_nterms always describe the
+ *    complete list; entries with index >= cap are not written, and nothing else is written.
+ *    cap = ids_cap is always enough.  There is no jb_device_status report: the caller checks
+ *    *d_nterms <= cap.
+ *  - The ids are not trusted: any u32 other than JB_ID_UNK is an id, and no table is indexed by
+ *    it.  The call needs no vocabulary.
+ *  - d_work is a caller-owned device buffer of nwork >= jb_terms_work_bytes(ids_cap, ndocs) bytes,
+ *    8-byte aligned (JB_EINVAL otherwise, with nothing queued): two 8-byte entries per token of
+ *    whole sort tiles of JB_TERMS_TILE tokens, plus 32 bytes per tile.  Its contents mean nothing
+ *    before or after the call; concurrent calls need buffers of their own.
+ *  - The call queues its kernels on `stream` and returns.  It does not synchronise, allocate,
+ *    read anything on the host or use the per-device workspace, so it is safe from several
+ *    threads and streams on one ctx, exactly like jb_ids_device.  The number of launches depends
+ *    on ids_cap alone (4, and 2 per doubling of ids_cap / JB_TERMS_TILE), never on device data.
+ *  - Counts are u32: a document has under 2^31 tokens, as batches are under 2 GiB.  JB_ELIMIT for
+ *    ids_cap >= 2^32 - JB_TERMS_TILE.
+ *
+ * jb_keywords_device.  A CSR as above (with the cap it was written with), the caller's per-id
+ * weight d_weight (f32[nweights]; IDF is one choice) and topk.
+ *  - A term is a candidate iff id < nweights and weight[id] > 0: zero, negative and NaN weights
+ *    exclude it, which is how a caller marks stop words and one-rune words.  +Inf is allowed.
+ *  - score = (float)cnt * weight[id]: one f32 conversion (round to nearest even) and one f32
+ *    multiply, bit-identical to numpy's np.float32(cnt) * w[id].  Products that are subnormal are
+ *    outside what is pinned (the device may flush them).
+ *  - Row d of d_kw_id / d_kw_score / d_kw_cnt (ndocs x topk each) holds the d_kw_n[d] =
+ *    min(topk, candidates) best candidates by score descending, ties by id ascending; the remaining
+ *    slots are JB_ID_UNK, 0.0f, 0.  Every slot of every row is written.
+ *  - 1 <= topk <= JB_KW_MAXK: JB_EINVAL for 0, JB_ELIMIT above.  jieba's default is 20.
+ *  - A CSR that overflowed its arrays (term_off[ndocs] > cap) is never read past cap: documents
+ *    whose range passes cap get kw_n = 0.  The caller checks *d_nterms <= cap.
+ *  - No vocabulary, allocation or synchronisation, as above: one kernel on `stream`.
+ *
+ * jb_keywords_batch: host text in, keywords out.  It runs plain Cut (extract_tags uses cut) ->
+ * ids -> terms -> keywords on ctx's first device, uploads the text and the weights and copies
+ * back only the ndocs x topk records and kw_n (and the token count, which sizes its buffers): no
+ * span or id reaches the host.  It needs an
+ * attached vocabulary (JB_EINVAL), a batch under 2 GiB (JB_ELIMIT) and doc_off non-decreasing;
+ * it allocates and synchronises, like jb_spans_ids, and keeps its device buffers (about 9 bytes per
+ * byte of text and 28 per token) for the next call, until jb_close; concurrent calls take turns.  It does not go through the piece /
+ * multi-device pipeline of the jb_cut_batch* calls, because pieces may split a document, and it
+ * uses one device.  Errors of the cut, JB_EPANIC included, pass through.
+ *
+ * Deliberate differences from jieba.analyse.extract_tags:
+ *  - the vocabulary is closed: unknown tokens are not terms (jieba gives them the median IDF);
+ *  - the score is not divided by the document's token total, a per-document constant that leaves
+ *    the order unchanged (the caller has doc_tok);
+ *  - the length and stop-word filters are the caller's zero weights;
+ *  - ties are resolved by id, where jieba's order on ties is arbitrary. */
+#define JB_KW_MAXK 64
+#define JB_TERMS_TILE 4096
+/* Host only, no ctx: non-decreasing in both arguments, never 0. */
+size_t jb_terms_work_bytes(uint64_t max_tokens, uint32_t ndocs);
+int jb_terms_device(jb_ctx *ctx, const uint32_t *d_ids, uint64_t ids_cap, const uint64_t *d_doc_tok,
+                    const uint64_t *d_ntok, uint32_t ndocs, void *stream, uint32_t *d_term_id, uint32_t *d_term_cnt,
+                    uint64_t cap, uint64_t *d_term_off, uint64_t *d_nterms, void *d_work, size_t nwork);
+int jb_keywords_device(jb_ctx *ctx, const uint32_t *d_term_id, const uint32_t *d_term_cnt, const uint64_t *d_term_off,
+                       uint32_t ndocs, uint64_t cap, const float *d_weight, uint32_t nweights, uint32_t topk,
+                       void *stream, uint32_t *d_kw_id, float *d_kw_score, uint32_t *d_kw_cnt, uint32_t *d_kw_n);
+/* kw_id / kw_score / kw_cnt: ndocs x topk host entries each; kw_n: ndocs. */
+int jb_keywords_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm,
+                      const float *weights, uint32_t nweights, uint32_t topk, uint32_t *kw_id, float *kw_score,
+                      uint32_t *kw_cnt, uint32_t *kw_n);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

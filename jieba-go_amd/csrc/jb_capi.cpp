@@ -225,6 +225,11 @@ extern "C" void jb_close(jb_ctx* ctx) {
         dfree(ctx->d_vslots);
         dfree(ctx->d_vpool);
     }
+    if ((ctx->kw_buf[0] || ctx->kw_buf[1]) && !ctx->devs.empty()) {
+        (void)hipSetDevice(ctx->devs[0]->ordinal);
+        dfree(ctx->kw_buf[0]);
+        dfree(ctx->kw_buf[1]);
+    }
     for (auto& d : ctx->devs) close_device(d.get());
     delete ctx;
 }
@@ -925,5 +930,178 @@ extern "C" int jb_spans_ids(jb_ctx* ctx, const uint8_t* text, const jb_spans* sp
     dfree(dse);
     dfree(did);
     dfree(dn);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// term counts and keywords (jb_terms.hip)
+// ---------------------------------------------------------------------------
+static_assert(JB_KW_MAXK == kKwMaxK && JB_TERMS_TILE == kTermsTile, "the header's constants are the kernels'");
+
+extern "C" size_t jb_terms_work_bytes(uint64_t max_tokens, uint32_t ndocs) { return terms_work_bytes(max_tokens, ndocs); }
+
+extern "C" int jb_terms_device(jb_ctx* ctx, const uint32_t* d_ids, uint64_t ids_cap, const uint64_t* d_doc_tok,
+                               const uint64_t* d_ntok, uint32_t ndocs, void* stream, uint32_t* d_term_id,
+                               uint32_t* d_term_cnt, uint64_t cap, uint64_t* d_term_off, uint64_t* d_nterms,
+                               void* d_work, size_t nwork) {
+    if (!ctx || !d_doc_tok || !d_ntok || !d_term_off || !d_nterms || !d_work || (ids_cap && !d_ids) ||
+        (cap && (!d_term_id || !d_term_cnt)))
+        return fail(JB_EINVAL, "jb_terms_device: null argument");
+    if (ids_cap >= (1ull << 32) - kTermsTile)
+        return fail(JB_ELIMIT, "jb_terms_device: an id list of %llu entries (limit 2^32 - %u)",
+                    (unsigned long long)ids_cap, kTermsTile);
+    if (((uintptr_t)d_work & 7u) != 0) return fail(JB_EINVAL, "jb_terms_device: d_work must be 8-byte aligned");
+    const size_t need = terms_work_bytes(ids_cap, ndocs);
+    if (nwork < need)
+        return fail(JB_EINVAL, "jb_terms_device: a work buffer of %llu bytes, jb_terms_work_bytes asks for %llu",
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_terms(d_ids, ids_cap, d_doc_tok, d_ntok, ndocs, d_term_id, d_term_cnt, cap, d_term_off, d_nterms,
+                         d_work, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_terms(d_ids, ids_cap, d_doc_tok, d_ntok, ndocs, d_term_id, d_term_cnt, cap, d_term_off, d_nterms, d_work,
+                     s, nullptr));
+    return JB_OK;
+}
+
+extern "C" int jb_keywords_device(jb_ctx* ctx, const uint32_t* d_term_id, const uint32_t* d_term_cnt,
+                                  const uint64_t* d_term_off, uint32_t ndocs, uint64_t cap, const float* d_weight,
+                                  uint32_t nweights, uint32_t topk, void* stream, uint32_t* d_kw_id, float* d_kw_score,
+                                  uint32_t* d_kw_cnt, uint32_t* d_kw_n) {
+    // (the limits of topk come first: they need no ctx)
+    if (topk == 0) return fail(JB_EINVAL, "jb_keywords_device: topk is 0");
+    if (topk > kKwMaxK) return fail(JB_ELIMIT, "jb_keywords_device: topk %u (limit JB_KW_MAXK = %u)", topk, kKwMaxK);
+    if (!ctx || !d_term_off || (cap && (!d_term_id || !d_term_cnt)) || (nweights && !d_weight) ||
+        (ndocs && (!d_kw_id || !d_kw_score || !d_kw_cnt || !d_kw_n)))
+        return fail(JB_EINVAL, "jb_keywords_device: null argument");
+    if (ndocs == 0) return JB_OK;
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    if (d->profile) {
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_keywords(d_term_id, d_term_cnt, d_term_off, ndocs, cap, d_weight, nweights, topk, d_kw_id,
+                            d_kw_score, d_kw_cnt, d_kw_n, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_keywords(d_term_id, d_term_cnt, d_term_off, ndocs, cap, d_weight, nweights, topk, d_kw_id, d_kw_score,
+                        d_kw_cnt, d_kw_n, s, nullptr));
+    return JB_OK;
+}
+
+// Host text in, keywords out: the device calls above chained on one stream of the first device.  The
+// chain goes through the public entry points, each of which takes the ctx's lock for itself.
+extern "C" int jb_keywords_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                                 const float* weights, uint32_t nweights, uint32_t topk, uint32_t* kw_id,
+                                 float* kw_score, uint32_t* kw_cnt, uint32_t* kw_n) {
+    // (the limits of topk come first: they need no ctx)
+    if (topk == 0) return fail(JB_EINVAL, "jb_keywords_batch: topk is 0");
+    if (topk > kKwMaxK) return fail(JB_ELIMIT, "jb_keywords_batch: topk %u (limit JB_KW_MAXK = %u)", topk, kKwMaxK);
+    if (!ctx || !doc_off || (nweights && !weights) || (ndocs && (!kw_id || !kw_score || !kw_cnt || !kw_n)))
+        return fail(JB_EINVAL, "jb_keywords_batch: null argument");
+    for (uint32_t k = 0; k < ndocs; k++)
+        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "jb_keywords_batch: doc_off decreases at %u", k);
+    const uint64_t nb = doc_off[ndocs] - doc_off[0];
+    if (nb && !text) return fail(JB_EINVAL, "jb_keywords_batch: null text");
+    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        if (!ctx->vocab) return fail(JB_EINVAL, "jb_keywords_batch: no vocabulary attached (jb_vocab_set)");
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    if (ndocs == 0) return JB_OK;
+    HIPCHK(hipSetDevice(ordinal));
+    std::vector<uint64_t> rel;
+    try {
+        rel.resize((size_t)ndocs + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
+    }
+    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
+    const uint64_t cap = std::max<uint64_t>(nb, 1);  // (a batch of n bytes has at most n tokens)
+    const size_t nrec = (size_t)ndocs * topk;
+    // one of the ctx's two buffers, grown to `need` bytes and cut into 256-byte aligned parts
+    struct Arena {
+        uint8_t* p = nullptr;
+        size_t off = 0;
+        void* take(size_t nbytes) {
+            void* r = p + off;
+            off += (nbytes + 255u) & ~(size_t)255u;
+            return r;
+        }
+    };
+    auto arena = [&](int which, size_t need, Arena* a) -> int {
+        if (ctx->kw_cap[which] < need) {
+            dfree(ctx->kw_buf[which]);
+            ctx->kw_buf[which] = nullptr;
+            ctx->kw_cap[which] = 0;
+            HIPCHK(hipMalloc(&ctx->kw_buf[which], need));
+            ctx->kw_cap[which] = need;
+        }
+        a->p = (uint8_t*)ctx->kw_buf[which];
+        return JB_OK;
+    };
+    auto r256 = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
+    std::lock_guard<std::mutex> kg(ctx->kw_mu);
+    hipStream_t st = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
+        Arena a;
+        if ((rc = arena(0, r256(nb + 64) + 3 * r256(ndoc8) + r256(16) + r256(2 * cap * 4) + r256((3 * nrec + ndocs) * 4) +
+                               r256(std::max<size_t>(nweights, 1) * 4), &a)))
+            return rc;
+        uint8_t* dt = (uint8_t*)a.take(nb + 64);
+        uint64_t* doff = (uint64_t*)a.take(ndoc8);
+        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
+        uint64_t* dtoff = (uint64_t*)a.take(ndoc8);
+        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the token count, the term count)
+        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
+        uint32_t* dkw = (uint32_t*)a.take((3 * nrec + ndocs) * 4);  // (ids, scores, counts, kw_n)
+        float* dw = (float*)a.take(std::max<size_t>(nweights, 1) * 4);
+        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
+        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+        if (nweights) HIPCHK(hipMemcpyAsync(dw, weights, (size_t)nweights * 4, hipMemcpyHostToDevice, st));
+        if ((rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt))) return rc;
+        if ((rc = jb_device_status(ctx, st))) return rc;  // (waits; the cut's errors, JB_EPANIC included)
+        // the token count sizes the rest: 28 bytes per token instead of per byte of text
+        uint64_t ntok = 0;
+        HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
+        const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);
+        const size_t nwork = terms_work_bytes(tcap, ndocs);
+        Arena b;
+        if ((rc = arena(1, r256(tcap * 4) + r256(2 * tcap * 4) + r256(nwork), &b))) return rc;
+        uint32_t* did = (uint32_t*)b.take(tcap * 4);
+        uint32_t* dterm = (uint32_t*)b.take(2 * tcap * 4);  // (term ids, term counts)
+        void* dwork = b.take(nwork);
+        if ((rc = jb_ids_device(ctx, dt, nb, dse, dse + cap, dcnt, tcap, st, did))) return rc;
+        if ((rc = jb_terms_device(ctx, did, tcap, dtok, dcnt, ndocs, st, dterm, dterm + tcap, tcap, dtoff, dcnt + 1,
+                                  dwork, nwork)))
+            return rc;
+        if ((rc = jb_keywords_device(ctx, dterm, dterm + tcap, dtoff, ndocs, tcap, dw, nweights, topk, st, dkw,
+                                     (float*)(dkw + nrec), dkw + 2 * nrec, dkw + 3 * nrec)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(kw_id, dkw, nrec * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(kw_score, dkw + nrec, nrec * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(kw_cnt, dkw + 2 * nrec, nrec * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(kw_n, dkw + 3 * nrec, (size_t)ndocs * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return JB_OK;
+    };
+    const int rc = run();
+    if (st) {
+        (void)hipStreamSynchronize(st);  // (copies from the caller's memory may be in flight)
+        (void)hipStreamDestroy(st);
+    }
     return rc;
 }

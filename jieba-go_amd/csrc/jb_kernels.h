@@ -123,6 +123,7 @@ enum KernelId {
     K_TOK_COUNT, K_SCAN_TOK, K_TOK_WRITE, K_DOC_TOK, K_LONG_SPEC, K_LONG_DP, K_LONG_SEG, K_LONG_PATH, K_LONG_TAIL, K_MASK_MERGE,
     K_LONG_PBITS, K_LONG, K_TOK1, K_SRCH_COUNT, K_SRCH_SCAN, K_SRCH_WRITE, K_SRCH_DOC,
     K_FULL_COUNT, K_FULL_SCAN, K_FULL_WRITE, K_FULL_DOC, K_IDS,
+    K_TERMS_SORT, K_TERMS_MERGE, K_TERMS_COUNT, K_TERMS_SCAN, K_TERMS_WRITE, K_KEYWORDS,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -242,6 +243,25 @@ constexpr uint32_t kIdsWgPerCu = 8;    // the fixed grid: 8 workgroups of 4 wave
 hipError_t run_ids(const DevVocab& v, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
                    const uint32_t* d_end, const uint64_t* d_ntok, uint64_t cap, uint32_t* d_ids, uint32_t ncu,
                    hipStream_t stream, KernelTimer* timer);
+
+// Term counts and keywords (jb_terms_device, jb_keywords_device; jb_terms.hip).  Sort tile = kTermsTile
+// consecutive tokens, one workgroup each: 4096 x 8 bytes of keys are 32 KiB of LDS.
+constexpr uint32_t kTermsTile = 4096;
+constexpr uint32_t kKwMaxK = 64;  // JB_KW_MAXK: k_keywords keeps one key per lane of a wave
+// Bytes of the work buffer run_terms needs for an id list of up to max_tokens entries.  Host only.
+size_t terms_work_bytes(uint64_t max_tokens, uint32_t ndocs);
+// Enqueue the term-count kernels on `stream`: the CSR of the tokens k < min(*d_ntok, ids_cap) whose id is
+// not JB_VOCAB_UNK.  term_id / term_cnt entries with index >= cap are not written; term_off (ndocs + 1) and
+// *d_nterms describe the complete list.  d_work holds terms_work_bytes(ids_cap, ndocs) bytes, 8-byte aligned.
+// (K_TERMS_MERGE times k_terms_merge and k_terms_copy together.)
+hipError_t run_terms(const uint32_t* d_ids, uint64_t ids_cap, const uint64_t* d_doc_tok, const uint64_t* d_ntok,
+                     uint32_t ndocs, uint32_t* d_term_id, uint32_t* d_term_cnt, uint64_t cap, uint64_t* d_term_off,
+                     uint64_t* d_nterms, void* d_work, hipStream_t stream, KernelTimer* timer);
+// Enqueue k_keywords on `stream`: per document the topk (1 .. kKwMaxK) candidates by score, then id.
+hipError_t run_keywords(const uint32_t* d_term_id, const uint32_t* d_term_cnt, const uint64_t* d_term_off,
+                        uint32_t ndocs, uint64_t cap, const float* d_weight, uint32_t nweights, uint32_t topk,
+                        uint32_t* d_kw_id, float* d_kw_score, uint32_t* d_kw_cnt, uint32_t* d_kw_n,
+                        hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

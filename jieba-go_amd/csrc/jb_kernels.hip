@@ -43,7 +43,8 @@ const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_
                                          "k_tok_write", "k_doc_tok", "k_long_spec", "k_long_dp", "k_long_seg", "k_long_path",
                                          "k_long_tail", "k_mask_merge", "k_long_pbits", "k_long", "k_tok1", "k_srch_count",
                                          "k_srch_scan", "k_srch_write", "k_srch_doc", "k_full_count", "k_full_scan",
-                                         "k_full_write", "k_full_doc", "k_ids"};
+                                         "k_full_write", "k_full_doc", "k_ids", "k_terms_sort", "k_terms_merge",
+                                         "k_terms_count", "k_terms_scan", "k_terms_write", "k_keywords"};
 
 // newJiebaHMM literals (tokenizer.go:629-652)
 #define START_B (-0.26268660809250016)

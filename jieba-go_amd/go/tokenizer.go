@@ -342,6 +342,74 @@ func (t *Tokenizer) CutIds(text string, useHmm bool, mode string) ([]string, []u
 	return spansToTokens(text, &s, 0), ids
 }
 
+// Tag is one keyword of ExtractTags: the term's id in the attached vocabulary, its score
+// (count x weight, as float32) and its count in the document.
+type Tag struct {
+	ID    uint32
+	Score float32
+	Count uint32
+}
+
+// ExtractTags is jieba.analyse.extract_tags over a batch of documents (jb_keywords_batch): per
+// document the topK (1..64) terms of the attached vocabulary by count x weights[id], best first,
+// ties by id.  A term whose weight is not > 0 (zero, negative, NaN) or whose id is past the table
+// is no candidate: that is how stop words and one-rune words are left out.  Cutting (plain Cut),
+// lookup, counting and ranking all run on the GPU; only the records come back.  The differences
+// from jieba's (closed vocabulary, no division by the token total, ties by id) are listed in
+// jiebahip.h.  With mini_dict.txt, the vocabulary abc, 今天, "�", 一刹那, 刹那, 这, 天天 and the
+// weights 1, 1.5, 0.5, 2, 1, 0, 1, ExtractTags([]string{"abc abc 今天"}, w, 3, false) is
+// {{0, 2, 2}, {1, 1.5, 1}} (tests/c_abi_keywords.c).  Never returns nil.
+func (t *Tokenizer) ExtractTags(docs []string, weights []float32, topK int, useHmm bool) [][]Tag {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	out := make([][]Tag, len(docs))
+	if len(docs) == 0 {
+		return out
+	}
+	if topK < 1 || topK > C.JB_KW_MAXK {
+		panic("jiebahip: ExtractTags topK out of range")
+	}
+	off := make([]uint64, len(docs)+1)
+	total := 0
+	for i, d := range docs {
+		total += len(d)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, d := range docs {
+		b = append(b, d...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	nrec := len(docs) * topK
+	id := make([]uint32, nrec)
+	score := make([]float32, nrec)
+	cnt := make([]uint32, nrec)
+	n := make([]uint32, len(docs))
+	var wp *C.float
+	if len(weights) > 0 {
+		wp = (*C.float)(unsafe.Pointer(&weights[0]))
+	}
+	rc := C.jb_keywords_batch(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+		C.uint32_t(len(docs)), hmm, wp, C.uint32_t(len(weights)), C.uint32_t(topK),
+		(*C.uint32_t)(unsafe.Pointer(&id[0])), (*C.float)(unsafe.Pointer(&score[0])),
+		(*C.uint32_t)(unsafe.Pointer(&cnt[0])), (*C.uint32_t)(unsafe.Pointer(&n[0])))
+	if rc != C.JB_OK {
+		// JB_EINVAL: no vocabulary attached; JB_EPANIC: the reference panics on this input
+		panic("jiebahip: " + lastError())
+	}
+	for d := range docs {
+		out[d] = make([]Tag, int(n[d]))
+		for r := range out[d] {
+			out[d][r] = Tag{id[d*topK+r], score[d*topK+r], cnt[d*topK+r]}
+		}
+	}
+	return out
+}
+
 // CutParallel (tokenizer.go:81) returns the tokens of Cut in document order.
 // The library splits the work itself: the text goes to the device in pieces cut
 // at Han-run starts (jb_split_points), and over every device of a multi-device

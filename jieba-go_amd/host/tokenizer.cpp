@@ -116,6 +116,26 @@ std::vector<std::string> Tokenizer::CutIds(const std::string& text, bool useHmm,
     return out;
 }
 
+std::vector<std::vector<Tokenizer::Tag>> Tokenizer::ExtractTags(const std::vector<std::string>& docs,
+                                                                const std::vector<float>& weights, uint32_t topK,
+                                                                bool useHmm) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& d : docs) {
+        all += d;
+        off.push_back(all.size());
+    }
+    const size_t nd = docs.size(), nrec = nd * (size_t)topK;
+    std::vector<uint32_t> id(nrec + 1), cnt(nrec + 1), n(nd + 1);
+    std::vector<float> score(nrec + 1);
+    check(jb_keywords_batch(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)nd, useHmm ? 1 : 0, weights.data(),
+                            (uint32_t)weights.size(), topK, id.data(), score.data(), cnt.data(), n.data()));
+    std::vector<std::vector<Tag>> out(nd);
+    for (size_t d = 0; d < nd; d++)
+        for (uint32_t r = 0; r < n[d]; r++) out[d].push_back(Tag{id[d * topK + r], score[d * topK + r], cnt[d * topK + r]});
+    return out;
+}
+
 std::vector<std::string> Tokenizer::CutParallel(const std::string& text, bool hmm, int, bool) {
     return Cut(text, hmm);
 }

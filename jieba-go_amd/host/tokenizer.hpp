@@ -62,6 +62,17 @@ public:
     // vocabulary, JB_ID_UNK when it is not there; looked up on the GPU.
     std::vector<std::string> CutIds(const std::string& text, bool useHmm, std::vector<uint32_t>* ids,
                                     Mode mode = Mode::Cut);
+    // Keywords (jieba.analyse.extract_tags; jb_keywords_batch in jiebahip.h, with its differences from
+    // jieba's): per document the topK terms of the attached vocabulary by count x weights[id], best
+    // first, ties by id; a term whose weight is not > 0 (or whose id is past the table) is no candidate.
+    // Counted and ranked on the GPU: no span reaches the host.
+    struct Tag {
+        uint32_t id;
+        float score;
+        uint32_t count;
+    };
+    std::vector<std::vector<Tag>> ExtractTags(const std::vector<std::string>& docs, const std::vector<float>& weights,
+                                              uint32_t topK = 20, bool useHmm = true);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

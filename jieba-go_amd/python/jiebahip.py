@@ -23,6 +23,8 @@ JB_OK, JB_EINVAL, JB_EIO, JB_EPARSE, JB_EDEVICE, JB_ENOMEM, JB_EPANIC, JB_ELIMIT
 JB_DICT_TXT, JB_DICT_PREFIX, JB_DICT_GOB, JB_DICT_IMAGE = 0, 1, 2, 3
 JIEBA_SIZE = 60_101_967  # tokenizer.go:454
 JB_ID_UNK = 0xFFFFFFFF  # the id of a token that is not in the vocabulary
+JB_KW_MAXK = 64  # the largest topk of the keyword calls
+JB_TERMS_TILE = 4096  # tokens per sort tile of jb_terms_device
 
 # Every symbol include/jiebahip.h declares.
 EXPORTS = [
@@ -37,6 +39,7 @@ EXPORTS = [
     "jb_cut_full", "jb_cut_batch_full", "jb_cut_device_full", "jb_cut_device_full_into",
     "jb_vocab_build", "jb_vocab_free", "jb_vocab_lookup", "jb_vocab_info", "jb_vocab_set", "jb_vocab_size",
     "jb_ids_device", "jb_spans_ids",
+    "jb_terms_work_bytes", "jb_terms_device", "jb_keywords_device", "jb_keywords_batch",
 ]
 
 
@@ -155,6 +158,13 @@ def lib():
         L.jb_vocab_size.restype = C.c_int64
         L.jb_ids_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp]
         L.jb_spans_ids.argtypes = [vp, vp, C.POINTER(jb_spans), vp]
+        L.jb_terms_work_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        L.jb_terms_work_bytes.restype = C.c_size_t
+        L.jb_terms_device.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp,
+                                      C.c_size_t]
+        L.jb_keywords_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, C.c_uint32, C.c_uint32, vp, vp,
+                                         vp, vp, vp]
+        L.jb_keywords_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -604,6 +614,52 @@ class Tokenizer:
             raise ValueError(f"mode {mode!r}: one of 'cut', 'search', 'full'")
         return spans_to_tokens(text, s.tolist(), e.tolist()), self.spans_ids(text, s, e)
 
+    # -- term counts and keywords ----------------------------------------
+    def terms_device(self, d_ids, ids_cap, d_doc_tok, d_ntok, ndocs, d_term_id, d_term_cnt, cap, d_term_off, d_nterms,
+                     d_work, nwork, stream_ptr=0):
+        """jb_terms_device over raw device pointers: the CSR of per-document (id, count), ids ascending;
+        entries with index >= cap are not written.  d_work: terms_work_bytes(ids_cap, ndocs) bytes."""
+        _check(lib().jb_terms_device(self.h, C.c_void_p(d_ids), ids_cap, C.c_void_p(d_doc_tok), C.c_void_p(d_ntok),
+                                     ndocs, C.c_void_p(stream_ptr), C.c_void_p(d_term_id), C.c_void_p(d_term_cnt), cap,
+                                     C.c_void_p(d_term_off), C.c_void_p(d_nterms), C.c_void_p(d_work), nwork))
+
+    def keywords_device(self, d_term_id, d_term_cnt, d_term_off, ndocs, cap, d_weight, nweights, topk, d_kw_id,
+                        d_kw_score, d_kw_cnt, d_kw_n, stream_ptr=0):
+        """jb_keywords_device over raw device pointers: per document the topk terms by count x weight."""
+        _check(lib().jb_keywords_device(self.h, C.c_void_p(d_term_id), C.c_void_p(d_term_cnt), C.c_void_p(d_term_off),
+                                        ndocs, cap, C.c_void_p(d_weight), nweights, topk, C.c_void_p(stream_ptr),
+                                        C.c_void_p(d_kw_id), C.c_void_p(d_kw_score), C.c_void_p(d_kw_cnt),
+                                        C.c_void_p(d_kw_n)))
+
+    def keywords_batch(self, buf, doc_off, hmm, weights, topk=20):
+        """jb_keywords_batch: host batch -> (kw_id u32[ndocs, topk], kw_score f32, kw_cnt u32, kw_n u32[ndocs])."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        nd = len(doc_off) - 1
+        rows = max(nd, 1) * max(int(topk), 1)
+        ki, ks, kc = np.empty(rows, np.uint32), np.empty(rows, np.float32), np.empty(rows, np.uint32)
+        kn = np.empty(max(nd, 1), np.uint32)
+        _check(lib().jb_keywords_batch(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, int(hmm),
+                                       w.ctypes.data if len(w) else None, len(w), topk, ki.ctypes.data, ks.ctypes.data,
+                                       kc.ctypes.data, kn.ctypes.data))
+        shape = (nd, int(topk))
+        return ki[:nd * topk].reshape(shape), ks[:nd * topk].reshape(shape), kc[:nd * topk].reshape(shape), kn[:nd]
+
+    def extract_tags(self, texts, weights, topK=20, hmm=True, keys=None):
+        """jieba.analyse.extract_tags over a list of documents (str / bytes), with the attached vocabulary
+        and the caller's per-id weights: per document a list of (key, score, count), best first.  `key`
+        is the term's id, or keys[id] when the vocabulary's key list is passed.  The differences from
+        jieba's (closed vocabulary, no division by the token total, ties by id) are in jiebahip.h."""
+        docs = [_b(t) for t in texts]
+        off = np.zeros(len(docs) + 1, np.uint64)
+        if docs:
+            off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+        buf = np.frombuffer(b"".join(docs) + b"\0", np.uint8)
+        ki, ks, kc, kn = self.keywords_batch(buf, off, hmm, weights, topK)
+        return [[(int(ki[d, r]) if keys is None else keys[int(ki[d, r])], float(ks[d, r]), int(kc[d, r]))
+                 for r in range(int(kn[d]))] for d in range(len(docs))]
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -732,6 +788,11 @@ def split_points(buf, doc_off, nparts):
     cut = np.zeros(nparts + 1, np.uint64)
     _check(lib().jb_split_points(buf.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1, nparts, cut.ctypes.data))
     return [int(x) for x in cut]
+
+
+def terms_work_bytes(max_tokens, ndocs):
+    """jb_terms_work_bytes: bytes of the work buffer jb_terms_device needs (host only)."""
+    return lib().jb_terms_work_bytes(max_tokens, ndocs)
 
 
 def go_log(x):

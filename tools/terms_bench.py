@@ -1,0 +1,190 @@
+#!/usr/bin/env python3
+"""The cost of jb_terms_device and jb_keywords_device on the benchmark's corpus.
+
+Corpus, dictionary and vocabulary as tools/ids_bench.py (bench.py's config 4: C_syn against the
+350k-word D_syn dictionary, JB_DICT_PREFIX, size 60,101,967; the vocabulary is the dictionary's words
+with freq > 0), at 1 GiB, at 128 MiB and for the 10,000-sentence batch, and one 1,000,000-rune
+document whose terms go through the merge passes.  Per batch: the plain jb_cut_device step,
+jb_ids_device, jb_terms_device and jb_keywords_device (topk 20), each timed with device events on the
+launch stream (--steps after --warmup), the term kernels once more through jb_profile_read, and
+jb_keywords_batch from host memory beside jb_cut_batch_into32 for the largest corpus.  The weights
+are a fixed-seed IDF-like table, 0 for one-rune keys.
+Writes one JSON document (--out) and prints it.
+
+    python tools/terms_bench.py --out profiles/terms_bench.json
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for sub in ("gen", os.path.join("jieba-go_amd", "python")):
+    sys.path.insert(0, os.path.join(ROOT, sub))
+
+TOPK = 20
+
+
+def timed(torch, fn, steps, warmup):
+    """Median and spread (ms) of fn() over `steps` calls, device events around each call."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    ms = np.array([a.elapsed_time(b) for a, b in ev])
+    return {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(float(ms.min()), 4),
+            "max_ms": round(float(ms.max()), 4)}
+
+
+def measure(torch, J, tk, d_w, nw, label, buf, off, steps, warmup):
+    stream = torch.cuda.current_stream().cuda_stream
+    nb, nd = int(off[-1]), len(off) - 1
+    d_text = torch.from_numpy(np.ascontiguousarray(buf[:nb])).cuda()
+    d_text = torch.cat([d_text, torch.zeros(64, dtype=torch.uint8, device="cuda")])
+    d_off = torch.from_numpy(np.asarray(off, np.int64)).cuda()
+    cut = lambda: tk.cut_device(d_text.data_ptr(), nb, d_off.data_ptr(), nd, True, stream)  # noqa: E731
+    ps, pe, pd, pn = cut()
+    torch.cuda.synchronize()
+    tk.device_status(stream)
+    ntok = int(J.dev_to_host(pn, 8, np.uint64)[0])
+    doc_tok = J.dev_to_host(pd, 8 * (nd + 1), np.uint64).astype(np.int64)
+    T = J.JB_TERMS_TILE
+    multi = (doc_tok[1:] > doc_tok[:-1]) & ((doc_tok[1:] - 1) // T != doc_tok[:-1] // T)
+    d_ids = torch.empty(ntok, dtype=torch.int32, device="cuda")
+    t_id = torch.empty(ntok, dtype=torch.int32, device="cuda")
+    t_cnt = torch.empty(ntok, dtype=torch.int32, device="cuda")
+    t_off = torch.empty(nd + 1, dtype=torch.int64, device="cuda")
+    t_n = torch.zeros(1, dtype=torch.int64, device="cuda")
+    k_id = torch.empty(nd * TOPK, dtype=torch.int32, device="cuda")
+    k_sc = torch.empty(nd * TOPK, dtype=torch.float32, device="cuda")
+    k_cnt = torch.empty(nd * TOPK, dtype=torch.int32, device="cuda")
+    k_n = torch.empty(nd, dtype=torch.int32, device="cuda")
+    need = J.terms_work_bytes(ntok, nd)
+    work = torch.empty(need, dtype=torch.uint8, device="cuda")
+    ids = lambda: tk.ids_device(d_text.data_ptr(), nb, ps, pe, pn, ntok, d_ids.data_ptr(), stream)  # noqa: E731
+    terms = lambda: tk.terms_device(d_ids.data_ptr(), ntok, pd, pn, nd, t_id.data_ptr(), t_cnt.data_ptr(), ntok,  # noqa: E731
+                                    t_off.data_ptr(), t_n.data_ptr(), work.data_ptr(), need, stream)
+    kw = lambda: tk.keywords_device(t_id.data_ptr(), t_cnt.data_ptr(), t_off.data_ptr(), nd, ntok, d_w.data_ptr(), nw,  # noqa: E731
+                                    TOPK, k_id.data_ptr(), k_sc.data_ptr(), k_cnt.data_ptr(), k_n.data_ptr(), stream)
+    t_cut = timed(torch, cut, steps, warmup)
+    t_ids = timed(torch, ids, steps, warmup)
+    t_terms = timed(torch, terms, steps, warmup)
+    t_kw = timed(torch, kw, steps, warmup)
+    nterms = int(t_n.cpu()[0])
+    known = int((d_ids != -1).sum().item())
+    tk.profile(True)
+    tk.profile_reset()
+    for _ in range(steps):
+        terms()
+        kw()
+    torch.cuda.synchronize()
+    prof = {k: round(v[0] / max(v[1], 1) * (v[1] / steps), 4) for k, v in tk.profile_read().items()
+            if k.startswith("k_terms") or k == "k_keywords"}
+    tk.profile(False)
+    base = t_cut["median_ms"]
+    # the call's own traffic: the ids in, the sorted runs out and in twice more (count, write), the CSR out
+    moved = 4 * ntok + 8 * T * ((ntok + T - 1) // T) + 8 * known + 2 * 8 * ntok + 8 * nterms
+    res = {
+        "batch": label, "bytes": nb, "docs": nd, "tokens": ntok, "known_tokens": known, "nterms": nterms,
+        "kw_rows_filled": int(k_n.sum().item()),
+        "multi_tile_docs": int(multi.sum()),
+        "tokens_in_multi_tile_docs_share": round(float((doc_tok[1:] - doc_tok[:-1])[multi].sum()) / max(ntok, 1), 4),
+        "work_bytes": int(need),
+        "cut_device_hmm1": t_cut, "ids_device": t_ids, "terms_device": t_terms, "keywords_device_top20": t_kw,
+        "ids_over_cut": round(t_ids["median_ms"] / base, 4), "terms_over_cut": round(t_terms["median_ms"] / base, 4),
+        "keywords_over_cut": round(t_kw["median_ms"] / base, 4),
+        "kernels_profile_ms_per_call": prof,
+        "terms_bytes_moved_per_token": round(moved / max(ntok, 1), 2),
+        "terms_algorithmic_min_bytes_per_token": round((4 * ntok + 8 * nterms) / max(ntok, 1), 2),
+        "terms_moved_gb_per_s": round(moved / (t_terms["median_ms"] * 1e-3) / 1e9, 1),
+    }
+    del d_text, d_off, d_ids, t_id, t_cnt, work
+    torch.cuda.empty_cache()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes-mib", type=float, nargs="+", default=[1024.0, 128.0])
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--nwords", type=int, default=350_000)
+    ap.add_argument("--host-steps", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "terms_bench.json"))
+    args = ap.parse_args()
+
+    import torch
+
+    import jiebahip as J
+    import synth
+
+    if not torch.cuda.is_available():
+        print("terms_bench.py: no GPU (this measurement does not fall back)", file=sys.stderr)
+        return 2
+    s = synth.Synth(nwords=args.nwords)
+    tmp = tempfile.mkdtemp(prefix="jb_terms_bench_")
+    dpath, epath = s.write_files(tmp)
+    tk = J.Tokenizer(J.make_config(dict_path=dpath, emit_path=epath, kind=J.JB_DICT_PREFIX,
+                                   size_override=J.JIEBA_SIZE, device=0))
+    with open(dpath, encoding="utf-8") as f:
+        keys = [p[0].encode() for p in (ln.split(" ") for ln in f if ln.strip()) if int(p[1]) > 0]
+    keys = list(dict.fromkeys(keys))
+    tk.set_vocab(keys)
+    rng = np.random.default_rng(7)
+    w = (1.0 + 10.0 * rng.random(len(keys))).astype(np.float32)
+    w[np.array([len(k.decode("utf-8", "replace")) < 2 for k in keys])] = 0.0
+    d_w = torch.from_numpy(w).cuda()
+    out = {"device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "topk": TOPK,
+           "tile_tokens": J.JB_TERMS_TILE, "vocabulary_keys": len(keys), "zero_weights": int((w == 0).sum()),
+           "batches": []}
+    threads = max(1, min(16, os.cpu_count() or 1))
+    big = None
+    for mib in args.sizes_mib:
+        buf, off, _ = s.corpus_parallel(synth.KIND_DOCS, 0, target_bytes=int(mib * (1 << 20)), threads=threads)
+        if big is None:
+            big = (buf, off, mib)
+        out["batches"].append(measure(torch, J, tk, d_w, len(w), f"C_syn {mib:g} MiB", buf, off, args.steps, args.warmup))
+    buf, off, _ = s.corpus(synth.KIND_SENTENCES, 0, max_docs=10_000, target_bytes=64 << 20)
+    out["batches"].append(measure(torch, J, tk, d_w, len(w), "S10k: 10,000 sentences", buf, off, args.steps, args.warmup))
+    buf, off, _ = s.corpus(synth.KIND_LONG_PUNCT, 0, target_runes=1_000_000)
+    out["batches"].append(measure(torch, J, tk, d_w, len(w), "L1M: one 1,000,000-rune document", buf, off, args.steps,
+                                  args.warmup))
+    # host memory in, records out, beside the span-returning host call, same machine and run
+    buf, off, mib = big
+    nb = int(off[-1])
+    host = {"batch": f"C_syn {mib:g} MiB from pageable host memory", "bytes": nb}
+    o32 = None
+    for name, fn in (("cut_batch_into32_hmm1", lambda: tk.cut_batch_into32(buf, off, True, o32)),
+                     ("keywords_batch_hmm1_top20", lambda: tk.keywords_batch(buf, off, True, w, TOPK))):
+        ts = []
+        for k in range(args.host_steps + 1):
+            t0 = time.perf_counter()
+            r = fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            if name.startswith("cut"):
+                o32 = r[3]
+        ts = ts[1:]  # (the first call grows buffers)
+        host[name] = {"median_ms": round(float(np.median(ts)), 2), "min_ms": round(min(ts), 2), "max_ms": round(max(ts), 2)}
+    host["keywords_over_into32"] = round(host["keywords_batch_hmm1_top20"]["median_ms"] /
+                                         host["cut_batch_into32_hmm1"]["median_ms"], 4)
+    out["host"] = host
+    tk.close()
+    text = json.dumps(out, indent=1)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
