@@ -391,6 +391,72 @@ int jb_keywords_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off,
                       const float *weights, uint32_t nweights, uint32_t topk, uint32_t *kw_id, float *kw_score,
                       uint32_t *kw_cnt, uint32_t *kw_n);
 
+/* ---- document frequencies and IDF weights (the weight table extract_tags presupposes) ------
+ * In how many documents each id occurs, and the IDF weight of each id from those counts, on the
+ * device: a caller who cuts their own corpus with their own vocabulary fits the d_weight table of
+ * jb_keywords_device here, and the chain "fit on the corpus, then rank every document" never
+ * copies a token to the host.
+ *
+ * jb_df_device adds one batch's document frequencies into d_df (u32[ndf]).  d_term_id, d_nterms and
+ * cap are the flat id list of a CSR as jb_terms_device wrote it: a row holds each of its
+ * document's ids once, so the document frequency of an id is the number of entries that carry it.
+ *  - Entry i takes part iff i < min(*d_nterms, cap) and d_term_id[i] < ndf.  *d_nterms is read on
+ *    the device; cap is the capacity the CSR was written with.  An overflowed CSR is never read
+ *    past cap: as before, the caller checks *d_nterms <= cap.
+ *  - Each such entry does d_df[id] += 1.  Nothing else is written, in particular nothing at or past
+ *    d_df[ndf].  The call accumulates: the caller zeroes d_df before the first batch, and counts
+ *    that stay within u32 are the caller's bound.
+ *  - The ids are not trusted: any u32 is an id, and ids >= ndf are skipped.
+ *  - The rows are trusted to hold distinct ids.  A caller's own CSR with an id repeated in a row
+ *    counts every entry.
+ *  - The call needs no term_off, no vocabulary and no work buffer.
+ *  - It queues one kernel on `stream` and returns, exactly like jb_ids_device: it does not
+ *    synchronise, allocate, read anything on the host or use the per-device workspace, and it holds
+ *    the ctx's shared lock only while queuing, so it is safe from several threads and streams.
+ *  - The result is integer sums: identical whatever the order of the adds, and from run to run.
+ *  - Errors: JB_EINVAL for a null pointer.  ndf == 0 is valid: nothing is added.
+ *
+ * jb_idf (host only, no ctx, no GPU) and jb_idf_device compute weight[id] (f32[ndf]) from df[id]
+ * (u32[ndf]) by one rule, bit for bit:
+ *  - weight[id] = 0.0f when df[id] == 0, when df[id] < min_df, when df[id] > max_df (JB_DF_NOMAX:
+ *    no upper bound) or when keep != NULL and keep[id] == 0.  Zero is how jb_keywords_device leaves
+ *    out stop words and one-rune words: max_df finds the corpus' own stop words, and keep (u8[ndf])
+ *    carries the caller's length filter without a host pass over the weights.
+ *  - Otherwise weight[id] = (float)(jb_go_log((double)(ndocs_total + 1) / (double)(df[id] + 1)) + 1.0),
+ *    the sums taken in 64 bits: one f64 divide, Go's math.Log as jb_go_log restates it, one f64 add
+ *    and one narrowing, round to nearest even.  It is scikit-learn's smoothed IDF.  No clamp is
+ *    applied: df[id] > ndocs_total gives what the formula gives, and a weight <= 0 is no candidate
+ *    downstream.
+ *  - Every one of the ndf weights is written, and nothing else.
+ *  - Errors: JB_ELIMIT for ndocs_total >= 2^53, where the conversion to f64 stops being exact;
+ *    JB_EINVAL for a null pointer (keep may be NULL; ndf == 0 is valid).
+ *  - jb_idf_device queues one kernel on `stream`, with the no-synchronisation contract above.
+ *
+ * jb_df_batch: host text in, the batch's document frequencies added to the caller's host array
+ * df[ndf].  It runs plain Cut -> ids -> terms -> df on ctx's first device through the buffers
+ * jb_keywords_batch keeps in the ctx (its ndf device counters are one more buffer that only
+ * grows; concurrent calls take turns), copies ndf counters back and adds them to df.  Requirements
+ * and errors are jb_keywords_batch's: an attached vocabulary (JB_EINVAL), a batch under 2 GiB
+ * (JB_ELIMIT), doc_off non-decreasing, and the cut's errors pass through.  The caller sums ndocs
+ * itself: ndocs_total of jb_idf is the number of documents of all batches.
+ *
+ * Deliberate differences from jieba's idf.txt and TFIDF:
+ *  - the vocabulary is closed: there is no median IDF for unknown words;
+ *  - the logarithm is Go's restatement (jb_go_log), so that the host rule and the device rule
+ *    agree to the bit;
+ *  - frequencies count the documents of the caller's batches, whatever "document" means to the
+ *    caller (jieba's file was fitted on a corpus of its authors'). */
+#define JB_DF_NOMAX 0xFFFFFFFFu
+int jb_df_device(jb_ctx *ctx, const uint32_t *d_term_id, const uint64_t *d_nterms, uint64_t cap, uint32_t *d_df,
+                 uint32_t ndf, void *stream);
+int jb_idf_device(jb_ctx *ctx, const uint32_t *d_df, uint32_t ndf, uint64_t ndocs_total, uint32_t min_df,
+                  uint32_t max_df, const uint8_t *d_keep, void *stream, float *d_weight);
+/* host only, no ctx, no GPU: the same rule, and the reference the device kernel is pinned to */
+int jb_idf(const uint32_t *df, uint32_t ndf, uint64_t ndocs_total, uint32_t min_df, uint32_t max_df,
+           const uint8_t *keep, float *weight);
+int jb_df_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm, uint32_t *df,
+                uint32_t ndf);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

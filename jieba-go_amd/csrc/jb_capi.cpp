@@ -225,10 +225,9 @@ extern "C" void jb_close(jb_ctx* ctx) {
         dfree(ctx->d_vslots);
         dfree(ctx->d_vpool);
     }
-    if ((ctx->kw_buf[0] || ctx->kw_buf[1]) && !ctx->devs.empty()) {
+    if ((ctx->kw_buf[0] || ctx->kw_buf[1] || ctx->kw_buf[2]) && !ctx->devs.empty()) {
         (void)hipSetDevice(ctx->devs[0]->ordinal);
-        dfree(ctx->kw_buf[0]);
-        dfree(ctx->kw_buf[1]);
+        for (void* p : ctx->kw_buf) dfree(p);
     }
     for (auto& d : ctx->devs) close_device(d.get());
     delete ctx;
@@ -996,25 +995,127 @@ extern "C" int jb_keywords_device(jb_ctx* ctx, const uint32_t* d_term_id, const 
     return JB_OK;
 }
 
-// Host text in, keywords out: the device calls above chained on one stream of the first device.  The
-// chain goes through the public entry points, each of which takes the ctx's lock for itself.
-extern "C" int jb_keywords_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                                 const float* weights, uint32_t nweights, uint32_t topk, uint32_t* kw_id,
-                                 float* kw_score, uint32_t* kw_cnt, uint32_t* kw_n) {
-    // (the limits of topk come first: they need no ctx)
-    if (topk == 0) return fail(JB_EINVAL, "jb_keywords_batch: topk is 0");
-    if (topk > kKwMaxK) return fail(JB_ELIMIT, "jb_keywords_batch: topk %u (limit JB_KW_MAXK = %u)", topk, kKwMaxK);
-    if (!ctx || !doc_off || (nweights && !weights) || (ndocs && (!kw_id || !kw_score || !kw_cnt || !kw_n)))
-        return fail(JB_EINVAL, "jb_keywords_batch: null argument");
+// ---------------------------------------------------------------------------
+// document frequencies and IDF weights (jb_terms.hip)
+// ---------------------------------------------------------------------------
+extern "C" int jb_df_device(jb_ctx* ctx, const uint32_t* d_term_id, const uint64_t* d_nterms, uint64_t cap,
+                            uint32_t* d_df, uint32_t ndf, void* stream) {
+    if (!ctx) return fail(JB_EINVAL, "jb_df_device: null ctx");
+    if (!d_nterms) return fail(JB_EINVAL, "jb_df_device: null d_nterms");
+    if (cap && !d_term_id) return fail(JB_EINVAL, "jb_df_device: null d_term_id");
+    if (ndf && !d_df) return fail(JB_EINVAL, "jb_df_device: null d_df");
+    if (ndf == 0 || cap == 0) return JB_OK;  // (nothing to add)
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    const bool combine = d->lc.df_combine != 0;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_df(d_term_id, d_nterms, cap, d_df, ndf, combine, d->ncu, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_df(d_term_id, d_nterms, cap, d_df, ndf, combine, d->ncu, s, nullptr));
+    return JB_OK;
+}
+
+static int idf_args(const char* who, const void* df, uint32_t ndf, uint64_t ndocs_total, const void* weight) {
+    if (ndf && !df) return fail(JB_EINVAL, "%s: null df", who);
+    if (ndf && !weight) return fail(JB_EINVAL, "%s: null weight", who);
+    if (ndocs_total >= (1ull << 53))
+        return fail(JB_ELIMIT, "%s: ndocs_total %llu (limit 2^53 - 1)", who, (unsigned long long)ndocs_total);
+    return JB_OK;
+}
+
+extern "C" int jb_idf(const uint32_t* df, uint32_t ndf, uint64_t ndocs_total, uint32_t min_df, uint32_t max_df,
+                      const uint8_t* keep, float* weight) {
+    if (const int rc = idf_args("jb_idf", df, ndf, ndocs_total, weight)) return rc;
+    const double num = (double)(ndocs_total + 1u);
+    for (uint32_t id = 0; id < ndf; id++) {
+        const uint32_t f = df[id];
+        float w = 0.0f;
+        if (f != 0 && f >= min_df && f <= max_df && (keep == nullptr || keep[id] != 0))
+            w = (float)(go_log(num / (double)((uint64_t)f + 1u)) + 1.0);
+        weight[id] = w;
+    }
+    return JB_OK;
+}
+
+extern "C" int jb_idf_device(jb_ctx* ctx, const uint32_t* d_df, uint32_t ndf, uint64_t ndocs_total, uint32_t min_df,
+                             uint32_t max_df, const uint8_t* d_keep, void* stream, float* d_weight) {
+    if (!ctx) return fail(JB_EINVAL, "jb_idf_device: null ctx");
+    if (const int rc = idf_args("jb_idf_device", d_df, ndf, ndocs_total, d_weight)) return rc;
+    if (ndf == 0) return JB_OK;
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    if (d->profile) {
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_idf(d_df, ndf, ndocs_total, min_df, max_df, d_keep, d_weight, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_idf(d_df, ndf, ndocs_total, min_df, max_df, d_keep, d_weight, s, nullptr));
+    return JB_OK;
+}
+
+// ---------------------------------------------------------------------------
+// host text in: jb_keywords_batch, jb_df_batch
+// ---------------------------------------------------------------------------
+namespace {
+
+// A part of one of the ctx's grow-only buffers, cut into 256-byte aligned pieces.
+struct Arena {
+    uint8_t* p = nullptr;
+    size_t off = 0;
+    void* take(size_t nbytes) {
+        void* r = p + off;
+        off += (nbytes + 255u) & ~(size_t)255u;
+        return r;
+    }
+};
+size_t r256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+
+// ctx->kw_buf[which], grown to `need` bytes (under kw_mu).
+int kw_arena(jb_ctx* ctx, int which, size_t need, Arena* a) {
+    if (ctx->kw_cap[which] < need) {
+        dfree(ctx->kw_buf[which]);
+        ctx->kw_buf[which] = nullptr;
+        ctx->kw_cap[which] = 0;
+        HIPCHK(hipMalloc(&ctx->kw_buf[which], need));
+        ctx->kw_cap[which] = need;
+    }
+    *a = Arena{};
+    a->p = (uint8_t*)ctx->kw_buf[which];
+    return JB_OK;
+}
+
+// What the chain leaves on the device for the call's last step.
+struct BatchCsr {
+    hipStream_t st;
+    const uint32_t *term_id, *term_cnt;  // tcap entries each
+    const uint64_t* term_off;            // ndocs + 1
+    const uint64_t* nterms;
+    uint64_t tcap;
+};
+
+// The front of the host-text calls: plain Cut -> ids -> terms of one batch on a stream of the first
+// device, through the public entry points (each takes the ctx's lock for itself), in the ctx's buffers
+// [0] (sized by the batch's bytes, with `extra0` bytes for the caller behind the chain's own) and [1]
+// (sized by its token count).  `last(csr, extra)` queues the call's own step and its copies back; the
+// stream is synchronised after it.  `who` names the entry point in the messages.
+template <class Last>
+int batch_chain(jb_ctx* ctx, const char* who, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                size_t extra0, Last last) {
     for (uint32_t k = 0; k < ndocs; k++)
-        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "jb_keywords_batch: doc_off decreases at %u", k);
+        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
     const uint64_t nb = doc_off[ndocs] - doc_off[0];
-    if (nb && !text) return fail(JB_EINVAL, "jb_keywords_batch: null text");
+    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
     if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
     int ordinal;
     {
         std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        if (!ctx->vocab) return fail(JB_EINVAL, "jb_keywords_batch: no vocabulary attached (jb_vocab_set)");
+        if (!ctx->vocab) return fail(JB_EINVAL, "%s: no vocabulary attached (jb_vocab_set)", who);
         ordinal = ctx->devs[0]->ordinal;
     }
     if (ndocs == 0) return JB_OK;
@@ -1027,29 +1128,6 @@ extern "C" int jb_keywords_batch(jb_ctx* ctx, const uint8_t* text, const uint64_
     }
     for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
     const uint64_t cap = std::max<uint64_t>(nb, 1);  // (a batch of n bytes has at most n tokens)
-    const size_t nrec = (size_t)ndocs * topk;
-    // one of the ctx's two buffers, grown to `need` bytes and cut into 256-byte aligned parts
-    struct Arena {
-        uint8_t* p = nullptr;
-        size_t off = 0;
-        void* take(size_t nbytes) {
-            void* r = p + off;
-            off += (nbytes + 255u) & ~(size_t)255u;
-            return r;
-        }
-    };
-    auto arena = [&](int which, size_t need, Arena* a) -> int {
-        if (ctx->kw_cap[which] < need) {
-            dfree(ctx->kw_buf[which]);
-            ctx->kw_buf[which] = nullptr;
-            ctx->kw_cap[which] = 0;
-            HIPCHK(hipMalloc(&ctx->kw_buf[which], need));
-            ctx->kw_cap[which] = need;
-        }
-        a->p = (uint8_t*)ctx->kw_buf[which];
-        return JB_OK;
-    };
-    auto r256 = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
     std::lock_guard<std::mutex> kg(ctx->kw_mu);
     hipStream_t st = nullptr;
     auto run = [&]() -> int {
@@ -1057,21 +1135,16 @@ extern "C" int jb_keywords_batch(jb_ctx* ctx, const uint8_t* text, const uint64_
         HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
         Arena a;
-        if ((rc = arena(0, r256(nb + 64) + 3 * r256(ndoc8) + r256(16) + r256(2 * cap * 4) + r256((3 * nrec + ndocs) * 4) +
-                               r256(std::max<size_t>(nweights, 1) * 4), &a)))
-            return rc;
+        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 3 * r256(ndoc8) + r256(16) + r256(2 * cap * 4) + extra0, &a))) return rc;
         uint8_t* dt = (uint8_t*)a.take(nb + 64);
         uint64_t* doff = (uint64_t*)a.take(ndoc8);
         uint64_t* dtok = (uint64_t*)a.take(ndoc8);
         uint64_t* dtoff = (uint64_t*)a.take(ndoc8);
         uint64_t* dcnt = (uint64_t*)a.take(16);  // (the token count, the term count)
         uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
-        uint32_t* dkw = (uint32_t*)a.take((3 * nrec + ndocs) * 4);  // (ids, scores, counts, kw_n)
-        float* dw = (float*)a.take(std::max<size_t>(nweights, 1) * 4);
         HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
         if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-        if (nweights) HIPCHK(hipMemcpyAsync(dw, weights, (size_t)nweights * 4, hipMemcpyHostToDevice, st));
         if ((rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt))) return rc;
         if ((rc = jb_device_status(ctx, st))) return rc;  // (waits; the cut's errors, JB_EPANIC included)
         // the token count sizes the rest: 28 bytes per token instead of per byte of text
@@ -1080,7 +1153,7 @@ extern "C" int jb_keywords_batch(jb_ctx* ctx, const uint8_t* text, const uint64_
         const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);
         const size_t nwork = terms_work_bytes(tcap, ndocs);
         Arena b;
-        if ((rc = arena(1, r256(tcap * 4) + r256(2 * tcap * 4) + r256(nwork), &b))) return rc;
+        if ((rc = kw_arena(ctx, 1, r256(tcap * 4) + r256(2 * tcap * 4) + r256(nwork), &b))) return rc;
         uint32_t* did = (uint32_t*)b.take(tcap * 4);
         uint32_t* dterm = (uint32_t*)b.take(2 * tcap * 4);  // (term ids, term counts)
         void* dwork = b.take(nwork);
@@ -1088,20 +1161,73 @@ extern "C" int jb_keywords_batch(jb_ctx* ctx, const uint8_t* text, const uint64_
         if ((rc = jb_terms_device(ctx, did, tcap, dtok, dcnt, ndocs, st, dterm, dterm + tcap, tcap, dtoff, dcnt + 1,
                                   dwork, nwork)))
             return rc;
-        if ((rc = jb_keywords_device(ctx, dterm, dterm + tcap, dtoff, ndocs, tcap, dw, nweights, topk, st, dkw,
-                                     (float*)(dkw + nrec), dkw + 2 * nrec, dkw + 3 * nrec)))
-            return rc;
-        HIPCHK(hipMemcpyAsync(kw_id, dkw, nrec * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(kw_score, dkw + nrec, nrec * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(kw_cnt, dkw + 2 * nrec, nrec * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(kw_n, dkw + 3 * nrec, (size_t)ndocs * 4, hipMemcpyDeviceToHost, st));
+        if ((rc = last(BatchCsr{st, dterm, dterm + tcap, dtoff, dcnt + 1, tcap}, &a))) return rc;
         HIPCHK(hipStreamSynchronize(st));
         return JB_OK;
     };
     const int rc = run();
     if (st) {
-        (void)hipStreamSynchronize(st);  // (copies from the caller's memory may be in flight)
+        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
         (void)hipStreamDestroy(st);
     }
     return rc;
 }
+
+}  // namespace
+
+// Host text in, keywords out: batch_chain, then jb_keywords_device and the records' way back.
+extern "C" int jb_keywords_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                                 const float* weights, uint32_t nweights, uint32_t topk, uint32_t* kw_id,
+                                 float* kw_score, uint32_t* kw_cnt, uint32_t* kw_n) {
+    // (the limits of topk come first: they need no ctx)
+    if (topk == 0) return fail(JB_EINVAL, "jb_keywords_batch: topk is 0");
+    if (topk > kKwMaxK) return fail(JB_ELIMIT, "jb_keywords_batch: topk %u (limit JB_KW_MAXK = %u)", topk, kKwMaxK);
+    if (!ctx || !doc_off || (nweights && !weights) || (ndocs && (!kw_id || !kw_score || !kw_cnt || !kw_n)))
+        return fail(JB_EINVAL, "jb_keywords_batch: null argument");
+    const size_t nrec = (size_t)ndocs * topk;
+    const size_t extra = r256((3 * nrec + ndocs) * 4) + r256(std::max<size_t>(nweights, 1) * 4);
+    return batch_chain(ctx, "jb_keywords_batch", text, doc_off, ndocs, hmm, extra, [&](const BatchCsr& c, Arena* a) -> int {
+        uint32_t* dkw = (uint32_t*)a->take((3 * nrec + ndocs) * 4);  // (ids, scores, counts, kw_n)
+        float* dw = (float*)a->take(std::max<size_t>(nweights, 1) * 4);
+        if (nweights) HIPCHK(hipMemcpyAsync(dw, weights, (size_t)nweights * 4, hipMemcpyHostToDevice, c.st));
+        if (const int rc = jb_keywords_device(ctx, c.term_id, c.term_cnt, c.term_off, ndocs, c.tcap, dw, nweights, topk,
+                                              c.st, dkw, (float*)(dkw + nrec), dkw + 2 * nrec, dkw + 3 * nrec))
+            return rc;
+        HIPCHK(hipMemcpyAsync(kw_id, dkw, nrec * 4, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipMemcpyAsync(kw_score, dkw + nrec, nrec * 4, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipMemcpyAsync(kw_cnt, dkw + 2 * nrec, nrec * 4, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipMemcpyAsync(kw_n, dkw + 3 * nrec, (size_t)ndocs * 4, hipMemcpyDeviceToHost, c.st));
+        return JB_OK;
+    });
+}
+
+// Host text in, the batch's document frequencies added to df: batch_chain, then jb_df_device into the
+// ctx's third buffer and ndf counters back.
+extern "C" int jb_df_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                           uint32_t* df, uint32_t ndf) {
+    if (!ctx) return fail(JB_EINVAL, "jb_df_batch: null ctx");
+    if (!doc_off) return fail(JB_EINVAL, "jb_df_batch: null doc_off");
+    if (ndf && !df) return fail(JB_EINVAL, "jb_df_batch: null df");
+    std::vector<uint32_t> got;
+    try {
+        got.resize(ndf);
+    } catch (const std::bad_alloc&) {
+        return fail(JB_ENOMEM, "out of host memory for %u counters", ndf);
+    }
+    bool ran = false;
+    const int rc = batch_chain(ctx, "jb_df_batch", text, doc_off, ndocs, hmm, 0, [&](const BatchCsr& c, Arena*) -> int {
+        if (ndf == 0) return JB_OK;
+        Arena b;
+        if (const int r = kw_arena(ctx, 2, (size_t)ndf * 4, &b)) return r;
+        uint32_t* ddf = (uint32_t*)b.p;
+        HIPCHK(hipMemsetAsync(ddf, 0, (size_t)ndf * 4, c.st));
+        if (const int r = jb_df_device(ctx, c.term_id, c.nterms, c.tcap, ddf, ndf, c.st)) return r;
+        HIPCHK(hipMemcpyAsync(got.data(), ddf, (size_t)ndf * 4, hipMemcpyDeviceToHost, c.st));
+        ran = true;
+        return JB_OK;
+    });
+    if (rc == JB_OK && ran)
+        for (uint32_t k = 0; k < ndf; k++) df[k] += got[k];
+    return rc;
+}
+

@@ -241,6 +241,7 @@ static const uint64_t kMaxPiece = 1ull << 30;  // (a piece of several documents;
 //                (default 65536), pipelined over three streams (cut_range)
 //   JB_SMALL     host batches up to this many bytes take k_small (0: never)
 //   JB_STAMPS    (STAMPS=1 builds only) per-wave phase clocks to stderr
+//   JB_DF_COMBINE jb_df_device's kernel: 1 k_df_combine (default), 0 k_df
 static int init_launch_cfg(Device* d) {
     LaunchCfg& lc = d->lc;
     lc.zh_waves = d->ncu * std::max(zh_waves_per_cu(true, false), zh_waves_per_cu(false, false));
@@ -299,6 +300,9 @@ static int init_launch_cfg(Device* d) {
     const int ss = env_int("JB_SMALL_SLOTS", 4);
     if (ss < 1 || ss > 8) return fail(JB_EINVAL, "JB_SMALL_SLOTS=%d: want 1 .. 8", ss);
     d->small_slots = (uint32_t)ss;
+    const int dc = env_int("JB_DF_COMBINE", 1);
+    if (dc < 0 || dc > 1) return fail(JB_EINVAL, "JB_DF_COMBINE=%d: want 0 or 1", dc);
+    lc.df_combine = (uint32_t)dc;
     return JB_OK;
 }
 

@@ -338,11 +338,12 @@ struct jb_ctx {
     uint32_t* d_vslots = nullptr;
     uint8_t* d_vpool = nullptr;
     DevVocab dvocab{};
-    // jb_keywords_batch's device buffers on the first device, kept for the next call (they only grow;
-    // calls take kw_mu in turn): [0] sized by the batch's bytes, [1] by its token count
+    // jb_keywords_batch's and jb_df_batch's device buffers on the first device, kept for the next call
+    // (they only grow; calls take kw_mu in turn): [0] sized by the batch's bytes, [1] by its token count,
+    // [2] jb_df_batch's ndf counters
     std::mutex kw_mu;
-    void* kw_buf[2] = {nullptr, nullptr};
-    size_t kw_cap[2] = {0, 0};
+    void* kw_buf[3] = {nullptr, nullptr, nullptr};
+    size_t kw_cap[3] = {0, 0, 0};
 };
 
 #pragma GCC visibility pop

@@ -124,6 +124,7 @@ enum KernelId {
     K_LONG_PBITS, K_LONG, K_TOK1, K_SRCH_COUNT, K_SRCH_SCAN, K_SRCH_WRITE, K_SRCH_DOC,
     K_FULL_COUNT, K_FULL_SCAN, K_FULL_WRITE, K_FULL_DOC, K_IDS,
     K_TERMS_SORT, K_TERMS_MERGE, K_TERMS_COUNT, K_TERMS_SCAN, K_TERMS_WRITE, K_KEYWORDS,
+    K_DF, K_IDF,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -158,6 +159,7 @@ struct LaunchCfg {
                                // (JB_LONG_WAIT_US x 100; default 20 s)
     int32_t mw_split;        // k_mark_walk: 2^s workgroups per tile, each walking its share of the entries
                              // (JB_MW_SPLIT: -1 = 1 when the batch has at most one tile per CU, else 0; 0-3 fixed)
+    uint32_t df_combine;     // jb_df_device: 1 k_df_combine, 0 k_df (JB_DF_COMBINE; results do not depend on it)
 };
 
 // k_zh's group split: g1 groups of grp bytes, then groups of *sgrp bytes to the end.
@@ -262,6 +264,15 @@ hipError_t run_keywords(const uint32_t* d_term_id, const uint32_t* d_term_cnt, c
                         uint32_t ndocs, uint64_t cap, const float* d_weight, uint32_t nweights, uint32_t topk,
                         uint32_t* d_kw_id, float* d_kw_score, uint32_t* d_kw_cnt, uint32_t* d_kw_n,
                         hipStream_t stream, KernelTimer* timer);
+// Document frequencies and IDF weights (jb_df_device, jb_idf_device; jb_terms.hip).
+// Enqueue k_df (combine: k_df_combine, the same sums through a table in LDS) on `stream`: d_df[id] += 1
+// for every entry i < min(*d_nterms, cap) of d_term_id whose id is < ndf (ndf > 0); nothing else is
+// written and nothing at or past cap is read.  A grid of a few workgroups per CU, sized by cap.
+hipError_t run_df(const uint32_t* d_term_id, const uint64_t* d_nterms, uint64_t cap, uint32_t* d_df, uint32_t ndf,
+                  bool combine, uint32_t ncu, hipStream_t stream, KernelTimer* timer);
+// Enqueue k_idf on `stream`: d_weight[id] for every id < ndf (ndf > 0) by jb_idf's rule, bit for bit.
+hipError_t run_idf(const uint32_t* d_df, uint32_t ndf, uint64_t ndocs_total, uint32_t min_df, uint32_t max_df,
+                   const uint8_t* d_keep, float* d_weight, hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

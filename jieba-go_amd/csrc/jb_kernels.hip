@@ -44,7 +44,8 @@ const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_
                                          "k_long_tail", "k_mask_merge", "k_long_pbits", "k_long", "k_tok1", "k_srch_count",
                                          "k_srch_scan", "k_srch_write", "k_srch_doc", "k_full_count", "k_full_scan",
                                          "k_full_write", "k_full_doc", "k_ids", "k_terms_sort", "k_terms_merge",
-                                         "k_terms_count", "k_terms_scan", "k_terms_write", "k_keywords"};
+                                         "k_terms_count", "k_terms_scan", "k_terms_write", "k_keywords", "k_df",
+                                         "k_idf"};
 
 // newJiebaHMM literals (tokenizer.go:629-652)
 #define START_B (-0.26268660809250016)

@@ -25,6 +25,12 @@
 // lanes, reads the document's terms 64 at a time, and joins a batch that holds a better key by a
 // bitonic sort of the batch and one bitonic merge.
 //
+// jb_df_device: k_df / k_df_combine add 1 to df[id] for every entry of a CSR's flat id list, the
+// document frequencies of the batch (a row holds each id once).  k_df is one global atomic per entry;
+// k_df_combine gives each workgroup a contiguous share of the list and a direct-mapped table in LDS
+// (id tag and count per slot), and flushes the table with one global atomic per occupied slot.
+// jb_idf_device: k_idf, one thread per id, the rule of jb_idf with go_log restated for the device.
+//
 // Nothing here synchronises, allocates or reads on the host; the launch counts depend on host values.
 #include <hip/hip_runtime.h>
 
@@ -599,6 +605,161 @@ __global__ __launch_bounds__(256) void k_keywords(const uint32_t* __restrict__ t
     if (lane == 0) kw_n[d] = (uint32_t)__popcll(nk);
 }
 
+// ---------------------------------------------------------------------------
+// k_df / k_df_combine
+// ---------------------------------------------------------------------------
+// The list as both kernels read it: `head` leading entries up to the first 16-byte boundary, `nv` whole
+// uint4 after them, and up to 3 entries after those.  The list is never read at or past n.
+struct DfSpan {
+    uint64_t n, nv, tail0;
+    uint32_t head;
+    const uint4* vec;
+};
+
+__device__ __forceinline__ DfSpan df_span(const uint32_t* __restrict__ term_id, const uint64_t* __restrict__ nterms,
+                                          uint64_t cap) {
+    DfSpan s;
+    s.n = std::min(*nterms, cap);
+    s.head = (uint32_t)std::min<uint64_t>(s.n, ((16u - ((uintptr_t)term_id & 15u)) & 15u) >> 2);
+    s.nv = (s.n - s.head) >> 2;
+    s.tail0 = s.head + 4u * s.nv;
+    s.vec = (const uint4*)(term_id + s.head);
+    return s;
+}
+
+// The entry that thread th of workgroup 0 owns outside the vectors (the head, then the tail), or kNone.
+__device__ __forceinline__ uint32_t df_edge(const uint32_t* __restrict__ term_id, const DfSpan& s, uint32_t th) {
+    if (th < s.head) return term_id[th];
+    if (th >= 4u && th < 8u && s.tail0 + (th - 4u) < s.n) return term_id[s.tail0 + (th - 4u)];
+    return kNone;
+}
+
+// The plain form: one relaxed device-scope add per entry (an id of kNone is never < ndf).
+__global__ __launch_bounds__(256) void k_df(const uint32_t* __restrict__ term_id, const uint64_t* __restrict__ nterms,
+                                            uint64_t cap, uint32_t* __restrict__ df, uint32_t ndf) {
+    const DfSpan s = df_span(term_id, nterms, cap);
+    const uint32_t th = threadIdx.x;
+    if (blockIdx.x == 0 && th < 8u) {
+        const uint32_t id = df_edge(term_id, s, th);
+        if (id < ndf) atomicAdd(&df[id], 1u);
+    }
+    const uint64_t stride = (uint64_t)gridDim.x * 1024u;
+    for (uint64_t v0 = (uint64_t)blockIdx.x * 1024u; v0 < s.nv; v0 += stride) {
+        uint4 x[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint64_t v = v0 + j * 256u + th;
+            x[j] = v < s.nv ? s.vec[v] : make_uint4(kNone, kNone, kNone, kNone);
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            if (x[j].x < ndf) atomicAdd(&df[x[j].x], 1u);
+            if (x[j].y < ndf) atomicAdd(&df[x[j].y], 1u);
+            if (x[j].z < ndf) atomicAdd(&df[x[j].z], 1u);
+            if (x[j].w < ndf) atomicAdd(&df[x[j].w], 1u);
+        }
+    }
+}
+
+// The combining form.  Workgroup b owns the vectors [b * share, (b + 1) * share), share = the vectors
+// divided evenly over the grid, in whole trips of 1024 and at least kDfMinShare.  A slot's tag is kNone
+// until an id claims it (no id < ndf is kNone); the id that finds another id's tag there goes to the
+// global counter itself.
+constexpr uint32_t kDfSlots = 4096;      // 32 KiB of LDS: five workgroups per CU
+constexpr uint32_t kDfMinShare = 1024;   // vectors: 4096 entries
+
+__device__ __forceinline__ void df_add(uint32_t id, uint32_t ndf, uint32_t* tag, uint32_t* cnt,
+                                       uint32_t* __restrict__ df) {
+    if (id >= ndf) return;
+    const uint32_t slot = id & (kDfSlots - 1u);
+    uint32_t t = __hip_atomic_load(&tag[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (t == kNone) {
+        t = atomicCAS(&tag[slot], kNone, id);
+        if (t == kNone) t = id;
+    }
+    if (t == id) atomicAdd(&cnt[slot], 1u);
+    else atomicAdd(&df[id], 1u);
+}
+
+__global__ __launch_bounds__(256) void k_df_combine(const uint32_t* __restrict__ term_id,
+                                                    const uint64_t* __restrict__ nterms, uint64_t cap,
+                                                    uint32_t* __restrict__ df, uint32_t ndf) {
+    __shared__ uint32_t tag[kDfSlots], cnt[kDfSlots];
+    const DfSpan s = df_span(term_id, nterms, cap);
+    const uint32_t th = threadIdx.x;
+    uint64_t share = (s.nv + gridDim.x - 1u) / gridDim.x;
+    share = std::max<uint64_t>((share + 1023u) & ~(uint64_t)1023u, kDfMinShare);
+    const uint64_t b0 = (uint64_t)blockIdx.x * share;
+    if (b0 >= s.nv && blockIdx.x != 0) return;  // (workgroup 0 also owns the head and the tail)
+    const uint64_t b1 = std::min(b0 + share, s.nv);
+    for (uint32_t i = th; i < kDfSlots; i += 256u) {
+        tag[i] = kNone;
+        cnt[i] = 0;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && th < 8u) df_add(df_edge(term_id, s, th), ndf, tag, cnt, df);
+    for (uint64_t v0 = b0; v0 < b1; v0 += 1024u) {
+        uint4 x[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint64_t v = v0 + j * 256u + th;
+            x[j] = v < b1 ? s.vec[v] : make_uint4(kNone, kNone, kNone, kNone);
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            df_add(x[j].x, ndf, tag, cnt, df);
+            df_add(x[j].y, ndf, tag, cnt, df);
+            df_add(x[j].z, ndf, tag, cnt, df);
+            df_add(x[j].w, ndf, tag, cnt, df);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = th; i < kDfSlots; i += 256u) {
+        const uint32_t c = cnt[i];
+        if (c) atomicAdd(&df[tag[i]], c);  // (a counted slot has a tag < ndf)
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_idf
+// ---------------------------------------------------------------------------
+// go_log (jb_image.cpp) for a positive normal x: the same operations in the same order, frexp by the bits.
+__device__ __forceinline__ double dev_go_log(double x) {
+    const double Ln2Hi = 6.93147180369123816490e-01, Ln2Lo = 1.90821492927058770002e-10,
+                 L1 = 6.666666666666735130e-01, L2 = 3.999999999940941908e-01, L3 = 2.857142874366239149e-01,
+                 L4 = 2.222219843214978396e-01, L5 = 1.818357216161805012e-01, L6 = 1.531383769920937332e-01,
+                 L7 = 1.479819860511658591e-01;
+    const uint64_t bits = (uint64_t)__double_as_longlong(x);
+    int ki = (int)((bits >> 52) & 0x7FFu) - 1022;
+    double f1 = __longlong_as_double((long long)((bits & ~(0x7FFull << 52)) | (1022ull << 52)));  // [0.5, 1)
+    if (f1 < 0.70710678118654752440) {  // Sqrt2/2
+        f1 *= 2;
+        ki--;
+    }
+    const double f = f1 - 1;
+    const double k = (double)ki;
+    const double s = f / (2 + f);
+    const double s2 = s * s;
+    const double s4 = s2 * s2;
+    const double t1 = s2 * (L1 + s4 * (L3 + s4 * (L5 + s4 * L7)));
+    const double t2 = s4 * (L2 + s4 * (L4 + s4 * L6));
+    const double R = t1 + t2;
+    const double hfsq = 0.5 * f * f;
+    return k * Ln2Hi - ((hfsq - (s * (hfsq + R) + k * Ln2Lo)) - f);
+}
+
+__global__ __launch_bounds__(256) void k_idf(const uint32_t* __restrict__ df, uint32_t ndf, uint64_t ndocs_total,
+                                             uint32_t min_df, uint32_t max_df, const uint8_t* __restrict__ keep,
+                                             float* __restrict__ weight) {
+    const uint64_t id = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (id >= ndf) return;
+    const uint32_t f = df[id];
+    float w = 0.0f;
+    if (f != 0 && f >= min_df && f <= max_df && (keep == nullptr || keep[id] != 0))
+        w = (float)(dev_go_log((double)(ndocs_total + 1u) / (double)((uint64_t)f + 1u)) + 1.0);
+    weight[id] = w;
+}
+
 struct TermsWork {
     uint64_t ntl;
     uint64_t *W0, *W1, *base;
@@ -670,6 +831,27 @@ hipError_t run_keywords(const uint32_t* d_term_id, const uint32_t* d_term_cnt, c
     JB_TIMED(K_KEYWORDS, hipLaunchKernelGGL(k_keywords, dim3(grid), dim3(256), 0, stream, d_term_id, d_term_cnt,
                                             d_term_off, ndocs, cap, d_weight, nweights, topk, d_kw_id, d_kw_score,
                                             d_kw_cnt, d_kw_n));
+    return hipGetLastError();
+}
+
+hipError_t run_df(const uint32_t* d_term_id, const uint64_t* d_nterms, uint64_t cap, uint32_t* d_df, uint32_t ndf,
+                  bool combine, uint32_t ncu, hipStream_t stream, KernelTimer* timer) {
+    // the grid follows cap (a host value), up to a few workgroups per CU; the kernels loop or share
+    const uint64_t trips = std::max<uint64_t>(1u, (cap / 4u + 1023u) / 1024u);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(trips, (uint64_t)std::max(ncu, 1u) * (combine ? 5u : 8u));
+    if (combine)
+        JB_TIMED(K_DF, hipLaunchKernelGGL(k_df_combine, dim3(grid), dim3(256), 0, stream, d_term_id, d_nterms, cap, d_df,
+                                          ndf));
+    else
+        JB_TIMED(K_DF, hipLaunchKernelGGL(k_df, dim3(grid), dim3(256), 0, stream, d_term_id, d_nterms, cap, d_df, ndf));
+    return hipGetLastError();
+}
+
+hipError_t run_idf(const uint32_t* d_df, uint32_t ndf, uint64_t ndocs_total, uint32_t min_df, uint32_t max_df,
+                   const uint8_t* d_keep, float* d_weight, hipStream_t stream, KernelTimer* timer) {
+    const uint32_t grid = (uint32_t)(((uint64_t)ndf + 255u) / 256u);
+    JB_TIMED(K_IDF, hipLaunchKernelGGL(k_idf, dim3(grid), dim3(256), 0, stream, d_df, ndf, ndocs_total, min_df, max_df,
+                                       d_keep, d_weight));
     return hipGetLastError();
 }
 

@@ -410,6 +410,82 @@ func (t *Tokenizer) ExtractTags(docs []string, weights []float32, topK int, useH
 	return out
 }
 
+// IdfFit is the result of FitIdf: per id of the attached vocabulary its IDF weight and the number
+// of documents it occurs in, and the number of documents fitted on.
+type IdfFit struct {
+	Weights []float32
+	Df      []uint32
+	Ndocs   uint64
+}
+
+// FitIdf fits IDF weights for the attached vocabulary on a corpus given as batches of documents
+// (jb_df_batch per batch, then jb_idf).  Weights[id] is the smoothed IDF
+// float32(log((Ndocs+1)/(Df[id]+1)) + 1) with the library's restatement of math.Log, or 0 where
+// Df[id] is 0, below minDf, above maxDf (0: no upper bound) or where keep (nil, or one byte per
+// id) is 0.  Cutting (plain Cut), lookup and counting run on the GPU; per batch only the
+// counters come back.  ExtractTags(docs, fit.Weights, ...) afterwards is the whole of TF-IDF.
+// With mini_dict.txt, the vocabulary abc, 今天, "�", 一刹那, 刹那, 这, 天天 and the documents
+// "abc abc 今天", "abc \xff今天天氣 这一刹那", "这一刹那 今天", "", "刹那 abc", Df is
+// {3, 3, 1, 2, 1, 2, 0} (tests/c_abi_df.c).
+func (t *Tokenizer) FitIdf(batches [][]string, useHmm bool, minDf, maxDf uint32, keep []byte) IdfFit {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	nv := int64(C.jb_vocab_size(t.ctx))
+	if nv < 0 {
+		panic("jiebahip: FitIdf without a vocabulary (SetVocab)")
+	}
+	if keep != nil && int64(len(keep)) != nv {
+		panic("jiebahip: FitIdf keep holds one byte per id")
+	}
+	if maxDf == 0 {
+		maxDf = C.JB_DF_NOMAX
+	}
+	fit := IdfFit{Weights: make([]float32, nv), Df: make([]uint32, nv)}
+	if nv == 0 {
+		for _, docs := range batches {
+			fit.Ndocs += uint64(len(docs))
+		}
+		return fit
+	}
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	for _, docs := range batches {
+		if len(docs) == 0 {
+			continue
+		}
+		off := make([]uint64, len(docs)+1)
+		total := 0
+		for i, d := range docs {
+			total += len(d)
+			off[i+1] = uint64(total)
+		}
+		b := make([]byte, 0, total+1)
+		for _, d := range docs {
+			b = append(b, d...)
+		}
+		b = append(b, 0) // (never an empty slice: its address is passed)
+		rc := C.jb_df_batch(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+			C.uint32_t(len(docs)), hmm, (*C.uint32_t)(unsafe.Pointer(&fit.Df[0])), C.uint32_t(nv))
+		if rc != C.JB_OK {
+			// JB_EPANIC: the reference panics on this input
+			panic("jiebahip: " + lastError())
+		}
+		fit.Ndocs += uint64(len(docs))
+	}
+	var kp *C.uint8_t
+	if keep != nil {
+		kp = (*C.uint8_t)(unsafe.Pointer(&keep[0]))
+	}
+	rc := C.jb_idf((*C.uint32_t)(unsafe.Pointer(&fit.Df[0])), C.uint32_t(nv), C.uint64_t(fit.Ndocs),
+		C.uint32_t(minDf), C.uint32_t(maxDf), kp, (*C.float)(unsafe.Pointer(&fit.Weights[0])))
+	if rc != C.JB_OK {
+		panic("jiebahip: " + lastError())
+	}
+	return fit
+}
+
 // CutParallel (tokenizer.go:81) returns the tokens of Cut in document order.
 // The library splits the work itself: the text goes to the device in pieces cut
 // at Han-run starts (jb_split_points), and over every device of a multi-device

@@ -136,6 +136,29 @@ std::vector<std::vector<Tokenizer::Tag>> Tokenizer::ExtractTags(const std::vecto
     return out;
 }
 
+Tokenizer::IdfFit Tokenizer::FitIdf(const std::vector<std::vector<std::string>>& batches, bool useHmm, uint32_t minDf,
+                                    uint32_t maxDf, const std::vector<uint8_t>& keep) {
+    const int64_t nv = jb_vocab_size(ctx_);
+    if (nv < 0) throw Error(JB_EINVAL, "FitIdf: no vocabulary attached (SetVocab)");
+    if (!keep.empty() && keep.size() != (size_t)nv) throw Error(JB_EINVAL, "FitIdf: keep holds one byte per id");
+    IdfFit fit{std::vector<float>((size_t)nv), std::vector<uint32_t>((size_t)nv, 0u), 0};
+    for (const auto& docs : batches) {
+        if (docs.empty()) continue;
+        std::string all;
+        std::vector<uint64_t> off(1, 0);
+        for (const auto& d : docs) {
+            all += d;
+            off.push_back(all.size());
+        }
+        check(jb_df_batch(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)docs.size(), useHmm ? 1 : 0,
+                          fit.df.data(), (uint32_t)nv));
+        fit.ndocs += docs.size();
+    }
+    check(jb_idf(fit.df.data(), (uint32_t)nv, fit.ndocs, minDf, maxDf, keep.empty() ? nullptr : keep.data(),
+                 fit.weights.data()));
+    return fit;
+}
+
 std::vector<std::string> Tokenizer::CutParallel(const std::string& text, bool hmm, int, bool) {
     return Cut(text, hmm);
 }

@@ -73,6 +73,18 @@ public:
     };
     std::vector<std::vector<Tag>> ExtractTags(const std::vector<std::string>& docs, const std::vector<float>& weights,
                                               uint32_t topK = 20, bool useHmm = true);
+    // IDF weights for the attached vocabulary, fitted on a corpus given as batches of documents
+    // (jb_df_batch per batch, then jb_idf; both in jiebahip.h): df[id] is the number of documents id
+    // occurs in, weights[id] the smoothed IDF float(log((ndocs + 1) / (df + 1)) + 1), or 0 where df is 0,
+    // below minDf, above maxDf (JB_DF_NOMAX: no upper bound) or where keep (empty, or one byte per id)
+    // is 0.  ExtractTags(docs, fit.weights) afterwards is the whole of TF-IDF.
+    struct IdfFit {
+        std::vector<float> weights;
+        std::vector<uint32_t> df;
+        uint64_t ndocs;
+    };
+    IdfFit FitIdf(const std::vector<std::vector<std::string>>& batches, bool useHmm = true, uint32_t minDf = 1,
+                  uint32_t maxDf = JB_DF_NOMAX, const std::vector<uint8_t>& keep = {});
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

@@ -25,6 +25,7 @@ JIEBA_SIZE = 60_101_967  # tokenizer.go:454
 JB_ID_UNK = 0xFFFFFFFF  # the id of a token that is not in the vocabulary
 JB_KW_MAXK = 64  # the largest topk of the keyword calls
 JB_TERMS_TILE = 4096  # tokens per sort tile of jb_terms_device
+JB_DF_NOMAX = 0xFFFFFFFF  # max_df of the idf calls: no upper bound
 
 # Every symbol include/jiebahip.h declares.
 EXPORTS = [
@@ -40,6 +41,7 @@ EXPORTS = [
     "jb_vocab_build", "jb_vocab_free", "jb_vocab_lookup", "jb_vocab_info", "jb_vocab_set", "jb_vocab_size",
     "jb_ids_device", "jb_spans_ids",
     "jb_terms_work_bytes", "jb_terms_device", "jb_keywords_device", "jb_keywords_batch",
+    "jb_df_device", "jb_idf_device", "jb_idf", "jb_df_batch",
 ]
 
 
@@ -165,6 +167,10 @@ def lib():
         L.jb_keywords_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, C.c_uint32, C.c_uint32, vp, vp,
                                          vp, vp, vp]
         L.jb_keywords_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+        L.jb_df_device.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp]
+        L.jb_idf_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.jb_idf.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]
+        L.jb_df_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint32]
         _lib = L
     return _lib
 
@@ -660,6 +666,48 @@ class Tokenizer:
         return [[(int(ki[d, r]) if keys is None else keys[int(ki[d, r])], float(ks[d, r]), int(kc[d, r]))
                  for r in range(int(kn[d]))] for d in range(len(docs))]
 
+    # -- document frequencies and IDF weights ------------------------------
+    def df_device(self, d_term_id, d_nterms, cap, d_df, ndf, stream_ptr=0):
+        """jb_df_device over raw device pointers: d_df[id] += 1 for every entry i < min(*d_nterms, cap) of the
+        CSR's flat id list whose id is < ndf; queued on the stream."""
+        _check(lib().jb_df_device(self.h, C.c_void_p(d_term_id), C.c_void_p(d_nterms), cap, C.c_void_p(d_df), ndf,
+                                  C.c_void_p(stream_ptr)))
+
+    def idf_device(self, d_df, ndf, ndocs, d_weight, min_df=1, max_df=None, d_keep=0, stream_ptr=0):
+        """jb_idf_device over raw device pointers: d_weight[id] for every id < ndf, by the rule of idf()."""
+        _check(lib().jb_idf_device(self.h, C.c_void_p(d_df), ndf, ndocs, min_df, JB_DF_NOMAX if max_df is None else max_df,
+                                   C.c_void_p(d_keep), C.c_void_p(stream_ptr), C.c_void_p(d_weight)))
+
+    def df_batch(self, buf, doc_off, hmm, df):
+        """jb_df_batch: the host batch's document frequencies, added in place to df (a contiguous uint32
+        array indexed by id); returns df."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        if not (isinstance(df, np.ndarray) and df.dtype == np.uint32 and df.flags.c_contiguous and df.flags.writeable):
+            raise ValueError("df: a writeable contiguous uint32 array")
+        _check(lib().jb_df_batch(self.h, buf.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1, int(hmm),
+                                 df.ctypes.data if len(df) else None, len(df)))
+        return df
+
+    def fit_idf(self, batches, hmm=True, min_df=1, max_df=None, keep=None):
+        """Fit IDF weights for the attached vocabulary on a corpus given as an iterable of batches, each a
+        list of documents (str / bytes): (weights f32[vocab_size], df u32[vocab_size], ndocs).
+        extract_tags(texts, weights) afterwards is the whole of TF-IDF."""
+        nv = self.vocab_size
+        if nv < 0:
+            raise JbError(JB_EINVAL, "fit_idf: no vocabulary attached (set_vocab)")
+        df = np.zeros(nv, np.uint32)
+        ndocs = 0
+        for batch in batches:
+            docs = [_b(t) for t in batch]
+            if not docs:
+                continue
+            off = np.zeros(len(docs) + 1, np.uint64)
+            off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+            self.df_batch(np.frombuffer(b"".join(docs) + b"\0", np.uint8), off, hmm, df)
+            ndocs += len(docs)
+        return idf(df, ndocs, min_df, max_df, keep), df, ndocs
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -709,10 +757,11 @@ class Tokenizer:
         _check(lib().jb_profile_reset(self.h))
 
     def profile_read(self):
-        names = (C.c_char_p * 32)()
-        ms = (C.c_double * 32)()
-        n = (C.c_uint64 * 32)()
-        k = _check(lib().jb_profile_read(self.h, names, ms, n, 32))
+        cap = 64  # (more than the library's kernels: 34)
+        names = (C.c_char_p * cap)()
+        ms = (C.c_double * cap)()
+        n = (C.c_uint64 * cap)()
+        k = _check(lib().jb_profile_read(self.h, names, ms, n, cap))
         return {names[i].decode(): (ms[i], n[i]) for i in range(k)}
 
 
@@ -797,3 +846,20 @@ def terms_work_bytes(max_tokens, ndocs):
 
 def go_log(x):
     return lib().jb_go_log(float(x))
+
+
+def idf(df, ndocs, min_df=1, max_df=None, keep=None):
+    """jb_idf (host only): weights f32[len(df)] from document frequencies: 0 where df is 0, below min_df,
+    above max_df (None: no upper bound) or where keep[id] == 0; else the smoothed IDF
+    float32(go_log((ndocs + 1) / (df + 1)) + 1)."""
+    df = np.ascontiguousarray(df, dtype=np.uint32)
+    w = np.empty(len(df), np.float32)
+    k = None
+    if keep is not None:
+        k = np.ascontiguousarray(keep, dtype=np.uint8)
+        if len(k) != len(df):
+            raise ValueError("keep: one entry per id")
+    _check(lib().jb_idf(df.ctypes.data if len(df) else None, len(df), ndocs, min_df,
+                        JB_DF_NOMAX if max_df is None else max_df, k.ctypes.data if k is not None and len(k) else None,
+                        w.ctypes.data if len(w) else None))
+    return w

@@ -9,11 +9,16 @@ jb_ids_device, jb_terms_device and jb_keywords_device (topk 20), each timed with
 launch stream (--steps after --warmup), the term kernels once more through jb_profile_read, and
 jb_keywords_batch from host memory beside jb_cut_batch_into32 for the largest corpus.  The weights
 are a fixed-seed IDF-like table, 0 for one-rune keys.
-Writes one JSON document (--out) and prints it.
+Then, on the CSR the terms step left on the device, the document-frequency steps with the same event
+method in the same process: the hipMemsetAsync of df, jb_df_device in both forms (JB_DF_COMBINE 0 and 1,
+the order alternated from step to step) and jb_idf_device, each beside the terms step of the same run;
+and jb_df_batch from host memory beside jb_keywords_batch.
+Writes two JSON documents (--out, and --df-out for the document-frequency rows) and prints them.
 
-    python tools/terms_bench.py --out profiles/terms_bench.json
+    python tools/terms_bench.py --out profiles/terms_bench.json --df-out profiles/df_bench.json
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -45,7 +50,67 @@ def timed(torch, fn, steps, warmup):
             "max_ms": round(float(ms.max()), 4)}
 
 
-def measure(torch, J, tk, d_w, nw, label, buf, off, steps, warmup):
+def timed_ab(torch, fns, steps, warmup):
+    """timed() for two forms of one step, in one loop: each step runs both, in alternating order."""
+    names = list(fns)
+    for _ in range(warmup):
+        for n in names:
+            fns[n]()
+    torch.cuda.synchronize()
+    ev = {n: [] for n in names}
+    for k in range(steps):
+        for n in (names if k % 2 == 0 else names[::-1]):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fns[n]()
+            b.record()
+            ev[n].append((a, b))
+    torch.cuda.synchronize()
+    out = {}
+    for n in names:
+        ms = np.array([a.elapsed_time(b) for a, b in ev[n]])
+        out[n] = {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(float(ms.min()), 4),
+                  "max_ms": round(float(ms.max()), 4)}
+    return out
+
+
+def measure_df(torch, J, forms, hip, t_id, t_n, nterms, cap, nw, nd, t_terms, steps, warmup):
+    """The document-frequency steps on the CSR the terms step of this run left on the device: the
+    hipMemsetAsync of df, jb_df_device in both forms (forms: {name: a tokenizer opened with that
+    JB_DF_COMBINE}), jb_idf_device; the forms' counters are compared with each other and with numpy."""
+    stream = torch.cuda.current_stream().cuda_stream
+    d_df = torch.zeros(nw, dtype=torch.int32, device="cuda")
+    d_wt = torch.empty(nw, dtype=torch.float32, device="cuda")
+    any_tk = next(iter(forms.values()))
+    zero = lambda: hip.hipMemsetAsync(C.c_void_p(d_df.data_ptr()), 0, C.c_size_t(4 * nw), C.c_void_p(stream))  # noqa: E731
+    df_fn = {n: (lambda t=t: t.df_device(t_id.data_ptr(), t_n.data_ptr(), cap, d_df.data_ptr(), nw, stream))
+             for n, t in forms.items()}
+    idf = lambda: any_tk.idf_device(d_df.data_ptr(), nw, nd, d_wt.data_ptr(), stream_ptr=stream)  # noqa: E731
+    t_zero = timed(torch, zero, steps, warmup)
+    t_df = timed_ab(torch, df_fn, steps, warmup)
+    counts = {}
+    for n in forms:
+        zero()
+        df_fn[n]()
+        torch.cuda.synchronize()
+        counts[n] = d_df.cpu().numpy().view(np.uint32).copy()
+    t_idf = timed(torch, idf, steps, warmup)  # (on real counters: the last form's)
+    ref = np.bincount(t_id[:nterms].cpu().numpy().view(np.uint32).astype(np.int64), minlength=nw)[:nw].astype(np.uint32)
+    names = list(forms)
+    best = min(names, key=lambda n: t_df[n]["median_ms"])
+    res = {"ndf": nw, "nterms": nterms, "memset_df": t_zero, "idf_device": t_idf,
+           "counters_equal_numpy": bool(all(np.array_equal(counts[n], ref) for n in names)),
+           "max_df": int(ref.max()), "ids_with_df_over_half_the_docs": int((ref > nd // 2).sum()),
+           "faster_form": best, "terms_device_median_ms": t_terms["median_ms"]}
+    for n in names:
+        res["df_device_" + n] = t_df[n]
+        res["df_" + n + "_over_terms"] = round(t_df[n]["median_ms"] / t_terms["median_ms"], 4)
+        res["df_" + n + "_entries_per_us"] = round(nterms / (t_df[n]["median_ms"] * 1e3), 1)
+    res["idf_over_terms"] = round(t_idf["median_ms"] / t_terms["median_ms"], 4)
+    return res
+
+
+def measure(torch, J, tk, d_w, nw, label, buf, off, steps, warmup, forms=None, hip=None):
     stream = torch.cuda.current_stream().cuda_stream
     nb, nd = int(off[-1]), len(off) - 1
     d_text = torch.from_numpy(np.ascontiguousarray(buf[:nb])).cuda()
@@ -107,6 +172,9 @@ def measure(torch, J, tk, d_w, nw, label, buf, off, steps, warmup):
         "terms_algorithmic_min_bytes_per_token": round((4 * ntok + 8 * nterms) / max(ntok, 1), 2),
         "terms_moved_gb_per_s": round(moved / (t_terms["median_ms"] * 1e-3) / 1e9, 1),
     }
+    if forms:
+        res["df"] = measure_df(torch, J, forms, hip, t_id, t_n, nterms, ntok, nw, nd, t_terms, steps, warmup)
+    print(f"terms_bench.py: {label} measured", file=sys.stderr, flush=True)
     del d_text, d_off, d_ids, t_id, t_cnt, work
     torch.cuda.empty_cache()
     return res
@@ -120,6 +188,7 @@ def main():
     ap.add_argument("--nwords", type=int, default=350_000)
     ap.add_argument("--host-steps", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "terms_bench.json"))
+    ap.add_argument("--df-out", default=os.path.join(ROOT, "profiles", "df_bench.json"))
     args = ap.parse_args()
 
     import torch
@@ -143,6 +212,20 @@ def main():
     w = (1.0 + 10.0 * rng.random(len(keys))).astype(np.float32)
     w[np.array([len(k.decode("utf-8", "replace")) < 2 for k in keys])] = 0.0
     d_w = torch.from_numpy(w).cuda()
+    # jb_df_device's two forms: the knob is read at jb_open, so one more tokenizer per form (the call
+    # needs no vocabulary); hipMemsetAsync from the runtime the library is bound to
+    forms = {}
+    old = os.environ.get("JB_DF_COMBINE")
+    for name, val in (("atomic", "0"), ("combine", "1")):
+        os.environ["JB_DF_COMBINE"] = val
+        forms[name] = J.Tokenizer(J.make_config(dict_path=dpath, emit_path=epath, kind=J.JB_DICT_PREFIX,
+                                                size_override=J.JIEBA_SIZE, device=0))
+    if old is None:
+        del os.environ["JB_DF_COMBINE"]
+    else:
+        os.environ["JB_DF_COMBINE"] = old
+    hip = C.CDLL("libamdhip64.so.7")
+    hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
     out = {"device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "topk": TOPK,
            "tile_tokens": J.JB_TERMS_TILE, "vocabulary_keys": len(keys), "zero_weights": int((w == 0).sum()),
            "batches": []}
@@ -152,19 +235,23 @@ def main():
         buf, off, _ = s.corpus_parallel(synth.KIND_DOCS, 0, target_bytes=int(mib * (1 << 20)), threads=threads)
         if big is None:
             big = (buf, off, mib)
-        out["batches"].append(measure(torch, J, tk, d_w, len(w), f"C_syn {mib:g} MiB", buf, off, args.steps, args.warmup))
+        out["batches"].append(measure(torch, J, tk, d_w, len(w), f"C_syn {mib:g} MiB", buf, off, args.steps, args.warmup,
+                                      forms, hip))
     buf, off, _ = s.corpus(synth.KIND_SENTENCES, 0, max_docs=10_000, target_bytes=64 << 20)
-    out["batches"].append(measure(torch, J, tk, d_w, len(w), "S10k: 10,000 sentences", buf, off, args.steps, args.warmup))
+    out["batches"].append(measure(torch, J, tk, d_w, len(w), "S10k: 10,000 sentences", buf, off, args.steps, args.warmup,
+                                  forms, hip))
     buf, off, _ = s.corpus(synth.KIND_LONG_PUNCT, 0, target_runes=1_000_000)
     out["batches"].append(measure(torch, J, tk, d_w, len(w), "L1M: one 1,000,000-rune document", buf, off, args.steps,
-                                  args.warmup))
+                                  args.warmup, forms, hip))
     # host memory in, records out, beside the span-returning host call, same machine and run
     buf, off, mib = big
     nb = int(off[-1])
     host = {"batch": f"C_syn {mib:g} MiB from pageable host memory", "bytes": nb}
     o32 = None
+    hdf = np.zeros(len(keys), np.uint32)
     for name, fn in (("cut_batch_into32_hmm1", lambda: tk.cut_batch_into32(buf, off, True, o32)),
-                     ("keywords_batch_hmm1_top20", lambda: tk.keywords_batch(buf, off, True, w, TOPK))):
+                     ("keywords_batch_hmm1_top20", lambda: tk.keywords_batch(buf, off, True, w, TOPK)),
+                     ("df_batch_hmm1", lambda: tk.df_batch(buf, off, True, hdf))):
         ts = []
         for k in range(args.host_steps + 1):
             t0 = time.perf_counter()
@@ -176,13 +263,25 @@ def main():
         host[name] = {"median_ms": round(float(np.median(ts)), 2), "min_ms": round(min(ts), 2), "max_ms": round(max(ts), 2)}
     host["keywords_over_into32"] = round(host["keywords_batch_hmm1_top20"]["median_ms"] /
                                          host["cut_batch_into32_hmm1"]["median_ms"], 4)
+    host["df_batch_over_keywords_batch"] = round(host["df_batch_hmm1"]["median_ms"] /
+                                                 host["keywords_batch_hmm1_top20"]["median_ms"], 4)
     out["host"] = host
     tk.close()
-    text = json.dumps(out, indent=1)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text + "\n")
-    print(text)
+    for t in forms.values():
+        t.close()
+    # the document-frequency rows as a document of their own, beside the terms step of the same run
+    df_doc = {k: out[k] for k in ("device", "steps", "warmup", "vocabulary_keys")}
+    df_doc["forms"] = {"atomic": "JB_DF_COMBINE=0: k_df, one global atomic per entry",
+                       "combine": "JB_DF_COMBINE=1: k_df_combine, a table in LDS per workgroup"}
+    df_doc["batches"] = [dict(batch=b["batch"], docs=b["docs"], tokens=b["tokens"], **b.pop("df")) for b in out["batches"]]
+    df_doc["host"] = {k: host[k] for k in ("batch", "bytes", "keywords_batch_hmm1_top20", "df_batch_hmm1",
+                                           "df_batch_over_keywords_batch")}
+    for path, doc in ((args.out, out), (args.df_out, df_doc)):
+        text = json.dumps(doc, indent=1)
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text + "\n")
+        print(text)
     return 0
 
 
