@@ -1,51 +1,14 @@
-// jb_kernels.hip — gfx950 kernels of the jieba-go Cut path.
-//
-// Pipeline for one batch of documents (all in HBM, one stream):
-//   k_docbits     document starts -> 1 bit per byte
-//   k_mark_walk   per 4 KiB tile: UTF-8 decode at lead bytes (Go rules), \p{Han}
-//                 runs -> block-start masks + counts (zh regex + splitText,
-//                 tokenizer.go:21,154-155,165-210); then the trie walk (DAG
-//                 edges) of every Han rune of the tile, one walk per lane at a
-//                 time from an LDS entry list (buildDag, :462-497)
-//   k_zh          per 6 KiB group (1 KiB in small batches): its Han blocks from the
-//                 block-start masks, dealt to lanes by length; backward max-prob DP
-//                 over the edges + forward path + BMES Viterbi on singleton runs
-//                                               (cutZh/cutDAG/buildDag/calcDagProba/
-//                                                findDagPath/maxIndexProba/viterbi/cutHMM,
-//                                                tokenizer.go:221-285,462-578,668-756)
-//   k_long_*      Han blocks of 8 KiB or more (one serial DP chain each)
-//   k_nonzh       the non-Han blocks with an alnum byte, from the alnum16 bits and
-//                 the masks: alnum runs, single runes, spaces dropped (cutNonZh,
-//                 tokenizer.go:289-310; blocks without alnum have no tokens)
-//   k_tok<0>/k_tok<1>  token start/end bitmaps -> counts (+ 256-tile sums, k_sup)
-//                 -> (start, end) spans
-//   k_doc_tok     per document first token (Cut per document)
-//
-// Output format on the device: two bitmaps, 1 bit per input byte each (token
-// first byte, token last byte), compacted to u32 spans.  All float64
-// arithmetic is IEEE add/compare in the reference's order; the library is
-// built with -ffp-contract=off and without fast-math (±Inf must propagate).
-#include <hip/hip_runtime.h>
-
+// jb_kernels.hip — the gfx950 kernels of the Cut path that share the HMM, DP and non-Han device code
+// (k_docbits, k_mark_walk, k_zh, the long-block family, k_nonzh, k_small) and their enqueue functions.
+// jb_pipeline.cpp has the pipeline overview and run_pipeline.
 #include <type_traits>
 
-#include "jb_kernels.h"
+#include "jb_kdev.h"
+#include "jb_kstages.h"
 
 #include <algorithm>
 
-#ifndef JB_STAMPS
-#define JB_STAMPS 0
-#endif
-
 namespace jb {
-
-const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_nonzh", "k_tok_count", "k_scan_tok",
-                                         "k_tok_write", "k_doc_tok", "k_long_spec", "k_long_dp", "k_long_seg", "k_long_path",
-                                         "k_long_tail", "k_mask_merge", "k_long_pbits", "k_long", "k_tok1", "k_srch_count",
-                                         "k_srch_scan", "k_srch_write", "k_srch_doc", "k_full_count", "k_full_scan",
-                                         "k_full_write", "k_full_doc", "k_ids", "k_terms_sort", "k_terms_merge",
-                                         "k_terms_count", "k_terms_scan", "k_terms_write", "k_keywords", "k_df",
-                                         "k_idf"};
 
 // newJiebaHMM literals (tokenizer.go:629-652)
 #define START_B (-0.26268660809250016)
@@ -58,94 +21,6 @@ const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_
 #define T_MM (-1.2603623820268226)
 #define T_SB (-0.7211965654669841)
 #define T_SS (-0.6658631448798212)
-
-// ---------------------------------------------------------------------------
-// small device helpers
-// ---------------------------------------------------------------------------
-// 4 bytes at any offset: one 8-byte load at the dword below + v_alignbyte.  The
-// text buffer is 4-byte aligned and readable 8 bytes past every offset used.
-__device__ __forceinline__ uint32_t ld4(const uint8_t* __restrict__ t, uint64_t q) {
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2), aligned(4)));
-    const u32x2 a = *reinterpret_cast<const u32x2*>(t + (q & ~3ull));
-    return __builtin_amdgcn_alignbyte(a.y, a.x, (uint32_t)(q & 3));
-}
-
-// 4 bytes at window offset k of staged text (k + 8 readable).
-__device__ __forceinline__ uint32_t lds4(const uint8_t* tx, uint32_t k) {
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(tx + (k & ~3u));
-    return __builtin_amdgcn_alignbyte(a[1], a[0], k & 3u);
-}
-
-// Token bitmaps: bits are accumulated per 32-byte word in registers and
-// flushed with one atomicOr per word (neighbouring blocks may share a word).
-struct Emitter {
-    uint32_t* sb;
-    uint32_t* eb;
-    uint32_t word, s, e;
-    uint32_t ties = 0;  // exact Viterbi route ties seen by this lane (Q12)
-    bool off = false;   // drop the bits instead of flushing them (k_zh_long: only lane 0 writes)
-    __device__ Emitter(uint32_t* s_, uint32_t* e_) : sb(s_), eb(e_), word(0xFFFFFFFFu), s(0), e(0) {}
-    __device__ __forceinline__ void flush() {
-        if (!off) {
-            if (s) atomicOr(sb + word, s);
-            if (e) atomicOr(eb + word, e);
-        }
-        s = e = 0;
-    }
-    __device__ __forceinline__ void at(uint32_t pos) {
-        const uint32_t w = pos >> 5;
-        if (w != word) {
-            flush();
-            word = w;
-        }
-    }
-    // token = bytes [a, b)
-    __device__ __forceinline__ void token(uint32_t a, uint32_t b) {
-        at(a);
-        s |= 1u << (a & 31u);
-        at(b - 1u);
-        e |= 1u << ((b - 1u) & 31u);
-    }
-    // start / end bits sm, em_ of bitmap word w
-    __device__ __forceinline__ void bits(uint32_t w, uint32_t sm, uint32_t em_) {
-        if (!(sm | em_)) return;
-        if (w != word) {
-            flush();
-            word = w;
-        }
-        s |= sm;
-        e |= em_;
-    }
-};
-
-// The same for a wave's LDS token bitmaps: word index = global word - w0.
-struct LdsEmitter {
-    uint32_t* sb;
-    uint32_t* eb;
-    uint32_t w0;
-    uint32_t word, s, e;
-    uint32_t ties = 0;  // exact Viterbi route ties seen by this lane (Q12)
-    __device__ LdsEmitter(uint32_t* s_, uint32_t* e_, uint32_t w0_)
-        : sb(s_), eb(e_), w0(w0_), word(0xFFFFFFFFu), s(0), e(0) {}
-    __device__ __forceinline__ void flush() {
-        if (s) atomicOr(sb + (word - w0), s);
-        if (e) atomicOr(eb + (word - w0), e);
-        s = e = 0;
-    }
-    __device__ __forceinline__ void at(uint32_t pos) {
-        const uint32_t w = pos >> 5;
-        if (w != word) {
-            flush();
-            word = w;
-        }
-    }
-    __device__ __forceinline__ void token(uint32_t a, uint32_t b) {
-        at(a);
-        s |= 1u << (a & 31u);
-        at(b - 1u);
-        e |= 1u << ((b - 1u) & 31u);
-    }
-};
 
 // ---------------------------------------------------------------------------
 // k_docbits
@@ -170,108 +45,6 @@ __global__ void k_docbits(const uint64_t* __restrict__ doc_off, uint32_t ndocs, 
 // utf8.DecodeRune, bounded by the document end) covers it, else it starts a
 // rune of its own.  Block starts: document starts and changes of Han-ness.
 // ---------------------------------------------------------------------------
-// Inclusive prefix sum over a wave's 64 lanes with DPP moves (VALU, no LDS round
-// trips): row_shr 1/2/4/8 scans each row of 16 lanes, row_bcast15/31 carry the row
-// totals into the rows above.  Lanes a move cannot source keep 0 (old = 0, bound_ctrl off).
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);  // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);  // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);  // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);  // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
-    return x;
-}
-
-__device__ __forceinline__ uint32_t block_scan_u32(uint32_t v, uint32_t* lds, uint32_t* total) {
-    // exclusive scan over a 256-thread workgroup
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    const uint32_t x = wave_incl_scan(v);
-    if (lane == 63) lds[wid] = x;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-    const uint32_t nw = blockDim.x >> 6;
-    for (uint32_t k = 0; k < nw; k++) {
-        const uint32_t t = lds[k];
-        if (k < wid) base += t;
-        tot += t;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
-
-// Exclusive prefix of tile t's (x, y) counts, by a 256-thread workgroup: the
-// 256-tile sums (k_sup) before t's group of 256, plus the counts of the tiles
-// before t in its own group.  The loads are issued first (pf_load) and summed
-// later (pf_sum), so their latency hides under the caller's own loads.
-// Replaces a single-workgroup scan launch.
-struct PrefixLoads {
-    uint32_t x, y;
-};
-__device__ __forceinline__ PrefixLoads pf_load(const uint2* __restrict__ cnt, const uint2* __restrict__ sup,
-                                               uint32_t t) {
-    PrefixLoads p{0u, 0u};
-    const uint32_t sn = t >> 8, r = t & 255u;
-    for (uint32_t i = threadIdx.x; i < sn; i += 256u) {
-        const uint2 v = sup[i];
-        p.x += v.x;
-        p.y += v.y;
-    }
-    if (threadIdx.x < r) {
-        const uint2 c = cnt[(t & ~255u) + threadIdx.x];
-        p.x += c.x;
-        p.y += c.y;
-    }
-    return p;
-}
-__device__ uint2 pf_sum(PrefixLoads p, uint32_t* lds) {
-    // wave sums by DPP scans (a shuffle reduction was twelve LDS round trips)
-    const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(p.x), 63);
-    const uint32_t y = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(p.y), 63);
-    const uint32_t wid = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0) {
-        lds[wid] = x;
-        lds[4u + wid] = y;
-    }
-    __syncthreads();
-    const uint2 out = make_uint2(lds[0] + lds[1] + lds[2] + lds[3], lds[4] + lds[5] + lds[6] + lds[7]);
-    __syncthreads();
-    return out;
-}
-
-// k_sup: the (x, y) sums of each group of 256 consecutive tile counts.
-__global__ __launch_bounds__(256) void k_sup(const uint2* __restrict__ cnt, uint32_t n, uint2* __restrict__ sup) {
-    __shared__ uint32_t lds[8];
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    PrefixLoads p{0u, 0u};
-    if (i < n) {
-        const uint2 c = cnt[i];
-        p.x = c.x;
-        p.y = c.y;
-    }
-    const uint2 s = pf_sum(p, lds);
-    if (threadIdx.x == 0) sup[blockIdx.x] = s;
-}
-
-// \p{Han} (unicode.Han, Unicode 13) with the common ranges first: the two
-// big BMP blocks, a bitmask for U+3000-303F (CJK punctuation: only 3005,
-// 3007, 3021-3029, 3038-303B are Han), and the full table only for the rare
-// rest (radicals, compatibility ideographs, the supplementary planes).
-__device__ __forceinline__ bool han_cp(uint32_t r) {
-    constexpr uint64_t k3000 = (1ull << 5) | (1ull << 7) | (0x1FFull << 0x21) | (0xFull << 0x38);
-    bool h = (r - 0x4E00u <= 0x9FFCu - 0x4E00u) | (r - 0x3400u <= 0x4DBFu - 0x3400u);
-    const uint32_t o = r - 0x3000u;
-    h |= o < 64u && ((k3000 >> (o & 63u)) & 1ull);
-    const bool rare = (r - 0x2E80u < 0x180u) | (r - 0xF900u < 0x200u) | (r >= 0x16FF0u);
-    if (rare) h = jb_is_han(r);
-    return h;
-}
-
-constexpr uint32_t kEdgeMaxL = 8;     // edge lengths a record holds
-constexpr uint32_t kEdgeIdxBits = 14;  // a record field: weight index + 1 (0: phantom edge)
-constexpr uint32_t kRecIdxMax = (1u << kEdgeIdxBits) - 2u;  // the largest weight index a record holds
-constexpr uint32_t kRecTop = 8u + 3u * kEdgeIdxBits;         // bit of the last field (a new edge enters there)
 constexpr uint32_t kTileE = kTileBytes / 3 + 2;  // Han rune entries of a tile (>= 3 bytes each)
 constexpr uint32_t kLA = 8;                      // lookahead entries: runes of the last run past the tile end
 constexpr uint32_t kLABytes = 40;                // ... starting in the first 40 bytes after it
@@ -282,12 +55,10 @@ constexpr uint32_t kMwOffE = kTileEX * 8u;                                // aft
 constexpr uint32_t kMwOffDb = kMwOffE + kTileEX * 4u;                     // u32 per 32 bytes of the tile, +2
 constexpr uint32_t kMwOffWl = kMwOffDb + (kTileBytes / 32u + 3u) * 4u;    // u16 per entry
 constexpr uint32_t kMwOffScan = (kMwOffWl + kTileE * 2u + 3u) & ~3u;      // u32 x 8
-#ifndef JB_MW_SORT
-#define JB_MW_SORT 1  // the walk list grouped by the line of each walk's first probe
-#endif
+// the walk list is grouped by the line of each walk's first probe
 constexpr uint32_t kMwSortB = 64u;                   // buckets of the walk-list sort
 constexpr uint32_t kMwOffHist = kMwOffScan + 8u * 4u;  // u32 per bucket
-constexpr uint32_t kMwLds = kMwOffHist + (JB_MW_SORT ? kMwSortB * 4u : 0u);
+constexpr uint32_t kMwLds = kMwOffHist + kMwSortB * 4u;
 constexpr uint32_t kMwOffHot = (kMwOffE + 15u) & ~15u;  // hot level-1 rows (phase 1 only), under the entries
 static_assert(kMwOffHot % 16u == 0u && kMwOffHot + 10u * JB_HOT_SLOTS <= kMwOffDb && JB_HOT_SLOTS == 512u,
               "k_mark_walk: the hot rows fit under the entry list, 256 threads stage them");
@@ -295,25 +66,6 @@ static_assert(kMwOffE >= kMwStage, "staged text must fit under the entry cells")
 static_assert(kTileBytes + kLABytes + 4u <= kMwStage - 16u && kTileBytes + kLABytes + 4u <= kTileBytes + 64u,
               "lookahead bytes are staged and have document bits");
 static_assert(kMwLds + 16u <= 163840u / 8u, "k_mark_walk: 8 workgroups per CU");
-// utf8.DecodeRune (Go rules, as jb_decode) at a lead byte (>= 0xC0), without
-// branches: the phase-1 lead loop runs every lane's leads in step, so a
-// branchy decode diverged on every byte class (k_mark_walk 0.601 -> 0.598 ms).
-__device__ __forceinline__ uint32_t dec_lead(uint32_t x, uint32_t lim, uint32_t* rune) {
-    const uint32_t b0 = x & 0xFFu, b1 = (x >> 8) & 0xFFu, b2 = (x >> 16) & 0xFFu, b3 = x >> 24;
-    const uint32_t n = b0 >= 0xF0u ? 4u : (b0 >= 0xE0u ? 3u : 2u);
-    uint32_t lo = b0 == 0xE0u ? 0xA0u : 0x80u;
-    lo = b0 == 0xF0u ? 0x90u : lo;
-    uint32_t hi = b0 == 0xEDu ? 0x9Fu : 0xBFu;
-    hi = b0 == 0xF4u ? 0x8Fu : hi;
-    const bool ok = (b0 - 0xC2u <= 0xF4u - 0xC2u) & (b1 >= lo) & (b1 <= hi) &
-                    ((n < 3u) | ((b2 & 0xC0u) == 0x80u)) & ((n < 4u) | ((b3 & 0xC0u) == 0x80u)) & (n <= lim);
-    const uint32_t m0 = n == 2u ? 0x1Fu : (n == 3u ? 0x0Fu : 0x07u);
-    uint32_t cp = ((b0 & m0) << 6) | (b1 & 0x3Fu);
-    cp = n >= 3u ? ((cp << 6) | (b2 & 0x3Fu)) : cp;
-    cp = n == 4u ? ((cp << 6) | (b3 & 0x3Fu)) : cp;
-    *rune = ok ? cp : 0xFFFDu;
-    return ok ? n : 1u;
-}
 
 // entry: rune (bits 0-17; Han runes are < 0x40000) | tile offset (bits 18-29)
 constexpr uint32_t kEntCont = 0x40000000u;  // the next entry continues the run
@@ -322,38 +74,6 @@ constexpr uint32_t kEntEdge = 0x80000000u;  // the run may continue past the til
 __device__ __forceinline__ uint32_t ent_code(uint32_t e) { return e & 0x1FFFFu; }
 __device__ __forceinline__ uint32_t ent_pos(uint32_t e) { return (e >> 18) & 0xFFFu; }
 __device__ __forceinline__ uint32_t ent_w(uint32_t e) { return 3u + ((e >> 17) & 1u); }
-
-// The Han rune encoded by x (Go-valid, within `lim` bytes), or 0.  A 3-byte
-// form with a Han value cannot be overlong (E0) or a surrogate (ED), and a
-// 4-byte form with a Han value is >= U+16FF0, so the bit patterns suffice.
-__device__ __forceinline__ uint32_t han_rune(uint32_t x, uint32_t lim, uint32_t* w) {
-    const uint32_t b0 = x & 0xFFu;
-    if ((x & 0x00C0C0F0u) == 0x008080E0u) {
-        const uint32_t r = ((b0 & 0x0Fu) << 12) | (((x >> 8) & 0x3Fu) << 6) | ((x >> 16) & 0x3Fu);
-        if (lim < 3u || !han_cp(r)) return 0u;
-        *w = 3u;
-        return r;
-    }
-    if ((x & 0xC0C0C0F8u) == 0x808080F0u) {
-        const uint32_t r =
-            ((b0 & 0x07u) << 18) | (((x >> 8) & 0x3Fu) << 12) | (((x >> 16) & 0x3Fu) << 6) | ((x >> 24) & 0x3Fu);
-        if (lim < 4u || !han_cp(r)) return 0u;
-        *w = 4u;
-        return r;
-    }
-    return 0u;
-}
-
-// One trie step in the double array: the cell that holds rune r (code k) under
-// the node whose cell is c; a hit when its check names that node.
-__device__ __forceinline__ uint32_t rune_code(const DevImage& im, uint32_t r) {
-    return im.code[jb_row(im.pagemap, r)];
-}
-__device__ __forceinline__ uint32_t dat_slot_k(uint64_t c, uint32_t k) { return jb_cell_base(c) + k; }
-__device__ __forceinline__ uint32_t dat_slot(const DevImage& im, uint64_t c, uint32_t r) {
-    return dat_slot_k(c, rune_code(im, r));
-}
-__device__ __forceinline__ bool dat_hit(uint64_t child, uint32_t id) { return jb_cell_check(child) == id + 1u; }
 
 // k_mark_walk: one workgroup per 4 KiB tile, staged in LDS, two phases.
 //
@@ -457,10 +177,8 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
         s_nla = 0;
         s_nwl = 0;
     }
-#if JB_MW_SORT
     uint32_t* const s_hist = reinterpret_cast<uint32_t*>(s_raw + kMwOffHist);
     if (threadIdx.x < kMwSortB) s_hist[threadIdx.x] = 0u;
-#endif
     const uint64_t p0 = t0 + threadIdx.x * 16u;
     // doc-start / past-the-end mask, bit k <-> byte p0 - 4 + k (k < 24)
     uint64_t M;
@@ -730,7 +448,7 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
     // has no children or ends its Han run gets its record now (in its LDS cell,
     // which only its own walk would read); the others go on the walk list.
     const uint32_t nla = s_nla;
-    [[maybe_unused]] uint32_t wm = 0;  // (JB_MW_SORT) which of the thread's entries went on the walk list
+    uint32_t wm = 0;  // which of the thread's entries went on the walk list
     for (uint32_t i = threadIdx.x, k = 0; i < nent; i += 256u, k++) {
         const uint32_t e = s_e[i];
         const uint32_t nxt = ent_pos(e) + ent_w(e);
@@ -761,7 +479,6 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
         } else if (i < ((nent * part) >> split) || i >= ((nent * (part + 1u)) >> split)) {
             // (another workgroup of the tile walks it)
         } else {
-#if JB_MW_SORT
             // Walks whose first probes fall in one 128-byte line of cells go next to each
             // other on the list, so that a wave's gather asks L2 for fewer lines: a
             // counting sort by a hash of that line (the order within a bucket does not
@@ -773,14 +490,10 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
             const uint32_t rk = atomicAdd(&s_hist[b], 1u);
             s_c[i] = (c1 & ~0x3FFFFFull) | (b << 11) | rk;
             wm |= 1u << k;
-#else
-            s_wl[atomicAdd(&s_nwl, 1u)] = (uint16_t)i;
-#endif
         }
     }
     const int any4 = __syncthreads_or(has4);  // (also the barrier after the run links)
     if (threadIdx.x == 0) tile4[tile] = any4 ? 1u : 0u;  // k_zh: general rune stepping near this tile
-#if JB_MW_SORT
     if (threadIdx.x < 64u) {  // bucket offsets: wave 0, a bucket per lane
         const uint32_t h = s_hist[threadIdx.x];
         const uint32_t x = wave_incl_scan(h);
@@ -796,7 +509,6 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
         }
     }
     __syncthreads();
-#endif
     if (stamps) c2 = __builtin_amdgcn_s_memtime();
     // ---- walks: wave w takes a quarter of the walk list ------------------------------
     const uint32_t* ent = s_e;
@@ -913,36 +625,6 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
         o[6] = c0b - c0;
         o[7] = c1b - c1;
     }
-}
-
-// The first block start after chunk c (16 bytes each), or nbytes: the rest of c's
-// tile chunk by chunk, then whole tiles by their block counts (tile_cnt.x).
-__device__ uint32_t nz_block_end(const uint32_t* __restrict__ lanemask, const uint2* __restrict__ tile_cnt,
-                                 uint32_t ntiles, uint32_t nbytes, uint32_t c) {
-    const uint32_t nch = ntiles * 256u;
-    uint32_t k = c + 1u;
-    while (k < nch) {
-        if ((k & 255u) == 0u) {
-            uint32_t t = k >> 8;
-            while (t < ntiles && tile_cnt[t].x == 0u) t++;
-            if (t >= ntiles) break;
-            k = t * 256u;
-        }
-        const uint32_t m = lanemask[k] & 0xFFFFu;
-        if (m) return min(nbytes, k * 16u + (uint32_t)__builtin_ctz(m));
-        k++;
-    }
-    return nbytes;
-}
-
-// The end of the block that starts at byte bs: the next block start of any kind
-// (k_mark_walk's lane masks), or nbytes.
-__device__ uint32_t block_end_at(const uint32_t* __restrict__ lanemask, const uint2* __restrict__ tile_cnt,
-                                 uint32_t ntiles, uint32_t nbytes, uint32_t bs) {
-    const uint32_t c = bs >> 4;
-    const uint32_t above = lanemask[c] & 0xFFFFu & ~((2u << (bs & 15u)) - 1u);
-    if (above) return c * 16u + (uint32_t)__builtin_ctz(above);
-    return nz_block_end(lanemask, tile_cnt, ntiles, nbytes, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -1160,24 +842,10 @@ struct TblSrc {
         return false;
     }
 };
-struct TblPeek {  // (the lane's block after the current one, TblSrc::peek)
+struct TblPeek {  // (the lane's block after the current one, tbl_peek)
     uint32_t bs, be;
     bool ok;
 };
-__device__ __forceinline__ TblPeek tbl_peek(const TblSrc& src, uint32_t j) {
-    TblPeek p{0u, 0u, false};
-    while (j < src.nseg) {
-        const uint32_t x = src.t[j * 64u];
-        j++;
-        if (x != ~0u) {
-            p.bs = src.wb + (x & 0xFFFFu);
-            p.be = src.wb + (x >> 16);
-            p.ok = true;
-            break;
-        }
-    }
-    return p;
-}
 // The same blocks read into registers once (a lane holds at most kZhChunk / 64 = 3, and
 // only the last can be ~0u): a block change in the DP then takes its next block and the
 // one after it from registers, not from LDS.  A lane's blocks end at different steps, so
@@ -1870,12 +1538,6 @@ __device__ __forceinline__ bool zh_fwd_a3(const GrpZvT<true>& v, const DevImage&
     return ok;
 }
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // any 4-byte UTF-8 lead byte (>= 0xF0) in the 16-byte words covering [bs, be)
 // (bytes of neighbours in the same words may give a false positive: that only
 // selects the general rune stepping)
@@ -1898,16 +1560,9 @@ __device__ __forceinline__ void zh_chunk_main(const uint8_t* __restrict__ text, 
                               uint32_t* __restrict__ counters, uint32_t winw, uint32_t& nties, uint64_t* st) {
     const GrpZvT<A3> v{text, bls, wb};
     uint32_t steps;
-#ifndef JB_ZH_REGSRC
-#define JB_ZH_REGSRC 1
-#endif
     if constexpr (A3) {
         uint32_t redom = 0;
-#if JB_ZH_REGSRC
         steps = zh_dp_a3<WL>(v, im, erec, gbest, ring, rb0, lb, RegSrc(src), redom);
-#else
-        steps = zh_dp_a3<WL>(v, im, erec, gbest, ring, rb0, lb, src, redom);
-#endif
         while (redom) {  // (rare) blocks with an edge past the ring, best values in gbest
             const uint32_t k = (uint32_t)__builtin_ctz(redom);
             redom &= redom - 1u;
@@ -1943,11 +1598,7 @@ __device__ __forceinline__ void zh_chunk_main(const uint8_t* __restrict__ text, 
         if constexpr (A3) {
             if (lane == 0u) *nrun = 0u;
             wave_sync();
-#if JB_ZH_REGSRC
             ok = zh_fwd_a3<HMM>(v, im, RegSrc(src), sb, eb, le, &rl);
-#else
-            ok = zh_fwd_a3<HMM>(v, im, src, sb, eb, le, &rl);
-#endif
             wave_sync();
             const uint32_t nr = min(*nrun, kZhRuns * 64u);  // the pool's entries k = lane + 64 r are this lane's
             rl.n = nr > lane ? (nr - lane + 63u) / 64u : 0u;
@@ -2624,15 +2275,6 @@ struct LItem {
     double w;
     uint32_t L, pad;
 };
-// c ? a : b for a mask c of all ones or zero, as two v_bfi_b32 (a select the compiler
-// keeps: it turns ternaries whose arms are loads into exec-mask branches)
-__device__ __forceinline__ double bitsel64(uint32_t m, double a, double b) {
-    const uint64_t ua = __builtin_bit_cast(uint64_t, a), ub = __builtin_bit_cast(uint64_t, b);
-    uint32_t lo, hi;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(lo) : "v"(m), "v"((uint32_t)ua), "v"((uint32_t)ub));
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(hi) : "v"(m), "v"((uint32_t)(ua >> 32)), "v"((uint32_t)(ub >> 32)));
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
 
 struct LSpec {  // a rune's speculative choice (k_long_spec) as the decided chain takes it
     double w;     // the chosen item's weight
@@ -3916,7 +3558,6 @@ __global__ __launch_bounds__(256) void k_long_dp(const uint8_t* __restrict__ tex
     long_dp_body<HMM>(text, im, erec, gbl, gbest, longblk, counters, sbits, ebits, lflag, lsegb, lpath, dbg, spec, blockIdx.x, gridDim.x, S);
 }
 
-
 // k_long_seg: one lane per 64-rune segment of a long block that k_long_dp ran
 // the chain for.  The chosen lengths are maxIndexProba over the same sums
 // w + best(i + L) the chain formed (the same float64 adds of the same values),
@@ -4281,7 +3922,6 @@ __global__ __launch_bounds__(256) void k_long_tail(const uint8_t* __restrict__ t
     long_tail_body<HMM>(text, im, gbl, longblk, lsegb, lflag, counters, lcode, lcx, bp, sbits, ebits, blockIdx.x, gridDim.x, s_cd);
 }
 
-
 // k_nonzh: cutNonZh (tokenizer.go:289-310) for exactly the non-Han blocks that hold
 // a [0-9A-Za-z] byte; every other non-Han block has no tokens (:290-293).  An alnum
 // byte is never Han, so it always lies in a non-Han block.  One wave per 64 alnum16
@@ -4317,356 +3957,6 @@ __global__ __launch_bounds__(256) void k_nonzh(const uint8_t* __restrict__ text,
     __shared__ __attribute__((aligned(16))) NzLds s_nz;
     nonzh_body(text, nbytes, lanemask, tile_cnt, ntiles, alnum16, sbits, ebits, docbits, doc_off, ndocs, blockIdx.x,
                gridDim.x, s_nz);
-}
-
-// ---------------------------------------------------------------------------
-// token bitmaps -> spans
-// ---------------------------------------------------------------------------
-#ifndef JB_TOK_CAP
-#define JB_TOK_CAP 3072
-#endif
-constexpr uint32_t kTokCap = JB_TOK_CAP;  // tokens per tile staged in LDS (k_tok's write pass)
-// block `blk` of `nblk` (the write pass: token tile blk; the count pass: tiles 2 blk, 2 blk + 1)
-template <bool WRITE>
-__device__ __forceinline__ void tok_body(const uint32_t* __restrict__ sbits, const uint32_t* __restrict__ ebits,
-                                         uint64_t nwords, uint2* __restrict__ tile_cnt,
-                                         const uint2* __restrict__ supt, uint32_t* __restrict__ counters,
-                                         uint32_t* __restrict__ tok_start, uint32_t* __restrict__ tok_end,
-                                         uint32_t blk, uint32_t nblk, uint32_t* lds, uint32_t* s_s, uint32_t* s_e) {
-    // bitmap words per lane: the write pass takes a token tile per workgroup, the count
-    // pass two (16-byte loads, half the workgroups; a tile's count is the half's sum)
-    constexpr uint32_t W = (WRITE ? 1u : 2u) * (kTokTileWords / 256);
-    constexpr uint32_t kCap = kTokCap;
-    const uint64_t w0 = ((uint64_t)blk * 256u + threadIdx.x) * W;
-    PrefixLoads pl{0u, 0u};
-    if (WRITE) pl = pf_load(tile_cnt, supt, blk);
-    uint32_t s[W], e[W];
-    if (w0 + W <= nwords) {
-        if constexpr (W == 4u) {
-            const uint4 a = *reinterpret_cast<const uint4*>(sbits + w0);
-            const uint4 b = *reinterpret_cast<const uint4*>(ebits + w0);
-            s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
-            e[0] = b.x; e[1] = b.y; e[2] = b.z; e[3] = b.w;
-        } else {
-            const uint2 a = *reinterpret_cast<const uint2*>(sbits + w0);
-            const uint2 b = *reinterpret_cast<const uint2*>(ebits + w0);
-            s[0] = a.x; s[1] = a.y;
-            e[0] = b.x; e[1] = b.y;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < W; k++) {
-            s[k] = w0 + k < nwords ? sbits[w0 + k] : 0u;
-            e[k] = w0 + k < nwords ? ebits[w0 + k] : 0u;
-        }
-    }
-    uint32_t cs = 0, ce = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++) {
-        cs += __popc(s[k]);
-        ce += __popc(e[k]);
-    }
-    uint32_t ts, te;
-    const uint32_t xs = block_scan_u32(cs, lds, &ts);
-    const uint32_t xe = block_scan_u32(ce, lds, &te);
-    if (!WRITE) {  // lanes 0-127 hold the first tile: its count is lane 128's exclusive prefix
-        if (threadIdx.x == 128u) {
-            tile_cnt[2u * blk] = make_uint2(xs, xe);
-            tile_cnt[2u * blk + 1u] = make_uint2(ts - xs, te - xe);
-        }
-        return;
-    }
-    const uint2 to = pf_sum(pl, lds);
-    if (blk == nblk - 1u && threadIdx.x == 0) {  // token totals
-        counters[CNT_NTOK] = to.x + ts;
-        counters[CNT_NTOKE] = to.y + te;
-        *reinterpret_cast<uint64_t*>(counters + CNT_NWORDS) = to.x + ts;
-    }
-    // spans go to LDS in tile order, then out in one coalesced pass (a lane's own
-    // tokens are ~60 bytes apart in the output: direct stores touch a line each)
-    const bool staged = ts <= kCap && te <= kCap;
-    // staged at LDS index (output index mod 4) + k, so that LDS and output share their
-    // 16-byte alignment and the copy-out moves four spans per lane and store
-    // (k_tok_write 0.298 -> 0.288 ms at 1 GiB; caller arrays not 16-byte aligned: one each)
-    const bool v4 = (((uintptr_t)tok_start | (uintptr_t)tok_end) & 15u) == 0u;
-    const uint32_t shs = v4 ? (to.x & 3u) : 0u, she = v4 ? (to.y & 3u) : 0u;
-    uint32_t* os = staged ? s_s + shs : tok_start + to.x;
-    uint32_t* oe = staged ? s_e + she : tok_end + to.y;
-    uint32_t gs = xs, ge = xe;
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++) {
-        const uint32_t base = (uint32_t)((w0 + k) << 5);
-        uint32_t m = s[k];
-        while (m) {
-            os[gs++] = base + (uint32_t)__builtin_ctz(m);
-            m &= m - 1;
-        }
-        m = e[k];
-        while (m) {
-            oe[ge++] = base + (uint32_t)__builtin_ctz(m) + 1u;
-            m &= m - 1;
-        }
-    }
-    if (staged) {
-        __syncthreads();
-        if (v4) {
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            auto out = [&](const uint32_t* a, uint32_t sh, uint32_t n, uint32_t* g) {  // g: output at LDS index 0
-                const uint32_t lo = (sh + 3u) & ~3u, hi = (sh + n) & ~3u;  // whole vectors: [lo, hi)
-                if (lo < hi) {
-                    for (uint32_t p = lo + 4u * threadIdx.x; p < hi; p += 1024u)
-                        __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(a + p), reinterpret_cast<u32x4*>(g + p));
-                    if (threadIdx.x < lo - sh) __builtin_nontemporal_store(a[sh + threadIdx.x], g + sh + threadIdx.x);
-                    if (threadIdx.x < sh + n - hi) __builtin_nontemporal_store(a[hi + threadIdx.x], g + hi + threadIdx.x);
-                } else if (threadIdx.x < n) {
-                    __builtin_nontemporal_store(a[sh + threadIdx.x], g + sh + threadIdx.x);
-                }
-            };
-            out(s_s, shs, ts, tok_start + to.x - shs);
-            out(s_e, she, te, tok_end + to.y - she);
-            return;
-        }
-        for (uint32_t k = threadIdx.x; k < ts; k += 256u) __builtin_nontemporal_store(s_s[k], tok_start + to.x + k);
-        for (uint32_t k = threadIdx.x; k < te; k += 256u) __builtin_nontemporal_store(s_e[k], tok_end + to.y + k);
-    }
-}
-template <bool WRITE>
-__global__ __launch_bounds__(256) void k_tok(const uint32_t* __restrict__ sbits, const uint32_t* __restrict__ ebits,
-                                             uint64_t nwords, uint2* __restrict__ tile_cnt,
-                                             const uint2* __restrict__ supt, uint32_t* __restrict__ counters,
-                                             uint32_t* __restrict__ tok_start, uint32_t* __restrict__ tok_end) {
-    __shared__ uint32_t lds[8];
-    __shared__ __attribute__((aligned(16))) uint32_t s_s[WRITE ? kTokCap + 4 : 1], s_e[WRITE ? kTokCap + 4 : 1];
-    tok_body<WRITE>(sbits, ebits, nwords, tile_cnt, supt, counters, tok_start, tok_end, blockIdx.x, gridDim.x, lds, s_s,
-                    s_e);
-}
-
-// tokens of document d: [doc_tok[d], doc_tok[d+1]) = lower_bound over starts.
-// G lanes per document.  G = 16 (a small batch: few documents, so the kernel's time
-// is one search's dependent loads): each trip, lane k probes the last start of the
-// k-th sixteenth of the range and a ballot counts the sixteenths wholly before the
-// target, log16 loads instead of log2.  G = 1 (many documents: their searches hide
-// each other's latency, and 16 lanes each would cost more loads in all): binary.
-template <uint32_t G>
-__device__ __forceinline__ void doc_tok_body(const uint64_t* __restrict__ doc_off, uint32_t ndocs,
-                                             const uint32_t* __restrict__ tok_start,
-                                             const uint32_t* __restrict__ counters, uint64_t* __restrict__ doc_tok,
-                                             uint32_t g) {
-    static_assert(G == 1u || G == 16u, "binary or 16-ary");
-    const uint32_t d = g / G, k = threadIdx.x & (G - 1u), gsh = threadIdx.x & (63u & ~(G - 1u));
-    if (d > ndocs) return;  // (whole groups: a group is one document)
-    const uint32_t n = counters[CNT_NTOK];
-    const uint64_t target = doc_off[d];
-    uint32_t lo = 0, hi = n;  // the answer is in [lo, hi]
-    if constexpr (G == 1u) {
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if ((uint64_t)tok_start[mid] < target) lo = mid + 1;
-            else hi = mid;
-        }
-    } else {
-        while (lo < hi) {
-            const uint32_t s = (hi - lo + 15u) >> 4;  // a sixteenth, rounded up
-            const uint32_t i = lo + (k + 1u) * s - 1u;
-            const bool before = i < hi && (uint64_t)tok_start[i] < target;
-            const uint32_t c = (uint32_t)__popcll((__ballot(before) >> gsh) & 0xFFFFull);
-            const uint32_t nlo = lo + c * s;
-            if (s == 1u || nlo >= hi) {
-                lo = min(nlo, hi);
-                break;
-            }
-            hi = min(hi, nlo + s - 1u);  // (the probe ending the c-th sixteenth is >= target)
-            lo = nlo;
-        }
-    }
-    if (k == 0u) doc_tok[d] = lo;
-}
-template <uint32_t G>
-__global__ __launch_bounds__(256) void k_doc_tok(const uint64_t* __restrict__ doc_off, uint32_t ndocs,
-                                                 const uint32_t* __restrict__ tok_start,
-                                                 const uint32_t* __restrict__ counters, uint64_t* __restrict__ doc_tok) {
-    doc_tok_body<G>(doc_off, ndocs, tok_start, counters, doc_tok, blockIdx.x * blockDim.x + threadIdx.x);
-}
-constexpr uint32_t kDocTokWide = 16384;  // documents from which k_doc_tok searches one lane each
-
-// k_tok1: the span kernels in one pass (round 5): k_tok's count pass, k_sup, its write
-// pass and k_doc_tok.  A workgroup takes the next token tile by a ticket (tiles in
-// claim order), counts its tokens, publishes the count, and finds its exclusive prefix
-// by looking back over the tiles before it (decoupled look-back: a tile's status word is
-// its count, flag 1, or its inclusive prefix, flag 2; it waits only on tiles claimed
-// before it, so by running workgroups).  Then it writes its spans as k_tok's write pass
-// does, and the per-document first tokens of the documents that start in its bytes
-// (k_doc_tok's lower bound, here over the tile's own starts in LDS).
-// Status: flag << 62 | starts prefix (31 bits) << 31 | ends prefix (31 bits).
-__device__ __forceinline__ uint64_t ts_pack(uint32_t f, uint32_t x, uint32_t y) {
-    return ((uint64_t)f << 62) | ((uint64_t)x << 31) | (uint64_t)y;
-}
-__global__ __launch_bounds__(256) void k_tok1(const uint32_t* __restrict__ sbits, const uint32_t* __restrict__ ebits,
-                                              uint64_t nwords, uint32_t ntt, uint64_t* __restrict__ tstat,
-                                              uint32_t* __restrict__ counters, uint32_t* __restrict__ tok_start,
-                                              uint32_t* __restrict__ tok_end, const uint64_t* __restrict__ doc_off,
-                                              uint32_t ndocs, uint64_t* __restrict__ doc_tok) {
-    constexpr uint32_t W = kTokTileWords / 256u;
-    constexpr uint32_t kCap = kTokCap;
-    constexpr uint64_t TB = (uint64_t)kTokTileWords * 32u;  // bytes per token tile
-    __shared__ uint32_t lds[8];
-    __shared__ uint32_t s_t, s_d0;
-    __shared__ uint2 s_to;
-    __shared__ __attribute__((aligned(16))) uint32_t s_s[kCap + 4], s_e[kCap + 4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0u) s_t = __hip_atomic_fetch_add(counters + CNT_TOKT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const uint32_t t = s_t;
-    const uint64_t w0 = ((uint64_t)t * 256u + threadIdx.x) * W;
-    uint32_t s[W], e[W];
-    if (w0 + W <= nwords) {
-        const uint2 a = *reinterpret_cast<const uint2*>(sbits + w0);
-        const uint2 b = *reinterpret_cast<const uint2*>(ebits + w0);
-        s[0] = a.x; s[1] = a.y;
-        e[0] = b.x; e[1] = b.y;
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < W; k++) {
-            s[k] = w0 + k < nwords ? sbits[w0 + k] : 0u;
-            e[k] = w0 + k < nwords ? ebits[w0 + k] : 0u;
-        }
-    }
-    // the first document that starts in the tile (or after it): a JB_TOK1_ARY-ary lower bound
-    // over doc_off (wave 1, its loads beside the bitmap loads)
-#ifndef JB_TOK1_ARY
-#define JB_TOK1_ARY 64
-#endif
-    static_assert(JB_TOK1_ARY == 16 || JB_TOK1_ARY == 64, "k_tok1's search: 16 or 64 lanes");
-    if (wave == 1u) {
-        constexpr uint32_t AR = JB_TOK1_ARY, SH = AR == 64u ? 6u : 4u;
-        const uint64_t target = (uint64_t)t * TB;
-        const uint32_t k = lane & (AR - 1u);
-        uint32_t lo = 0, hi = ndocs + 1u;  // the answer in [lo, hi]
-        while (lo < hi) {
-            const uint32_t sx = (hi - lo + AR - 1u) >> SH;
-            const uint32_t i = lo + (k + 1u) * sx - 1u;
-            const bool before = i < hi && doc_off[i] < target;
-            const uint32_t c = (uint32_t)__popcll(__ballot(before) & (AR == 64u ? ~0ull : 0xFFFFull));
-            const uint32_t nlo = lo + c * sx;
-            if (sx == 1u || nlo >= hi) {
-                lo = min(nlo, hi);
-                break;
-            }
-            hi = min(hi, nlo + sx - 1u);
-            lo = nlo;
-        }
-        if (lane == 0u) s_d0 = lo;
-    }
-    uint32_t cs = 0, ce = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++) {
-        cs += __popc(s[k]);
-        ce += __popc(e[k]);
-    }
-    uint32_t ts, te;
-    const uint32_t xs = block_scan_u32(cs, lds, &ts);
-    const uint32_t xe = block_scan_u32(ce, lds, &te);
-    // publish the count, then look back (wave 0)
-    if (threadIdx.x == 0u)
-        __hip_atomic_store(tstat + t, ts_pack(t == 0u ? 2u : 1u, ts, te), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (wave == 0u) {
-        uint32_t px = 0, py = 0;
-        for (int64_t base = (int64_t)t - 1; base >= 0;) {
-            const int64_t j = base - (int64_t)lane;
-            uint64_t v = j >= 0 ? __hip_atomic_load(tstat + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ts_pack(2u, 0u, 0u);
-            const uint64_t incl = __ballot((v >> 62) == 2u), ready = __ballot((v >> 62) != 0u);
-            // the nearest inclusive prefix, and every tile between ready
-            const uint32_t k2 = incl ? (uint32_t)__builtin_ctzll(incl) : 64u;
-            const uint64_t need = k2 == 64u ? ~0ull : ((2ull << k2) - 1ull);
-            if ((ready & need) != need) {
-                __builtin_amdgcn_s_sleep(1);
-                continue;  // (a tile before is still counting: read again)
-            }
-            uint32_t x = lane <= k2 ? (uint32_t)(v >> 31) & 0x7FFFFFFFu : 0u;
-            uint32_t y = lane <= k2 ? (uint32_t)v & 0x7FFFFFFFu : 0u;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                x += (uint32_t)__shfl_xor((int)x, d, 64);
-                y += (uint32_t)__shfl_xor((int)y, d, 64);
-            }
-            px += x;
-            py += y;
-            if (k2 < 64u) break;
-            base -= 64;
-        }
-        if (lane == 0u) {
-            s_to = make_uint2(px, py);
-            if (t > 0u)
-                __hip_atomic_store(tstat + t, ts_pack(2u, px + ts, py + te), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-    const uint2 to = s_to;
-    if (t == ntt - 1u && threadIdx.x == 0) {  // token totals
-        counters[CNT_NTOK] = to.x + ts;
-        counters[CNT_NTOKE] = to.y + te;
-        *reinterpret_cast<uint64_t*>(counters + CNT_NWORDS) = to.x + ts;
-    }
-    // the spans (k_tok's write pass)
-    const bool staged = ts <= kCap && te <= kCap;
-    const bool v4 = (((uintptr_t)tok_start | (uintptr_t)tok_end) & 15u) == 0u;
-    const uint32_t shs = v4 ? (to.x & 3u) : 0u, she = v4 ? (to.y & 3u) : 0u;
-    uint32_t* os = staged ? s_s + shs : tok_start + to.x;
-    uint32_t* oe = staged ? s_e + she : tok_end + to.y;
-    uint32_t gs = xs, ge = xe;
-#pragma unroll
-    for (uint32_t k = 0; k < W; k++) {
-        const uint32_t base = (uint32_t)((w0 + k) << 5);
-        uint32_t m = s[k];
-        while (m) {
-            os[gs++] = base + (uint32_t)__builtin_ctz(m);
-            m &= m - 1;
-        }
-        m = e[k];
-        while (m) {
-            oe[ge++] = base + (uint32_t)__builtin_ctz(m) + 1u;
-            m &= m - 1;
-        }
-    }
-    __syncthreads();  // (the staged starts, or this workgroup's global ones, for the documents below)
-    // the documents that start in the tile (the last tile: all that are left, with the end
-    // sentinel d = ndocs): their first token is the first start >= their offset
-    {
-        const uint32_t d0 = s_d0;
-        const uint64_t hiB = t == ntt - 1u ? ~0ull : ((uint64_t)t + 1u) * TB;
-        for (uint32_t d = d0 + threadIdx.x; d <= ndocs; d += 256u) {
-            const uint64_t o = doc_off[d];
-            if (o >= hiB) break;
-            const uint32_t* st = staged ? s_s + shs : tok_start + to.x;
-            uint32_t lo = 0, hi = ts;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if ((uint64_t)st[mid] < o) lo = mid + 1;
-                else hi = mid;
-            }
-            doc_tok[d] = to.x + lo;
-        }
-    }
-    if (!staged) return;
-    if (v4) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        auto out = [&](const uint32_t* a, uint32_t sh, uint32_t n, uint32_t* g) {  // g: output at LDS index 0
-            const uint32_t lo = (sh + 3u) & ~3u, hi = (sh + n) & ~3u;  // whole vectors: [lo, hi)
-            if (lo < hi) {
-                for (uint32_t p = lo + 4u * threadIdx.x; p < hi; p += 1024u)
-                    __builtin_nontemporal_store(*reinterpret_cast<const u32x4*>(a + p), reinterpret_cast<u32x4*>(g + p));
-                if (threadIdx.x < lo - sh) __builtin_nontemporal_store(a[sh + threadIdx.x], g + sh + threadIdx.x);
-                if (threadIdx.x < sh + n - hi) __builtin_nontemporal_store(a[hi + threadIdx.x], g + hi + threadIdx.x);
-            } else if (threadIdx.x < n) {
-                __builtin_nontemporal_store(a[sh + threadIdx.x], g + sh + threadIdx.x);
-            }
-        };
-        out(s_s, shs, ts, tok_start + to.x - shs);
-        out(s_e, she, te, tok_end + to.y - she);
-        return;
-    }
-    for (uint32_t k = threadIdx.x; k < ts; k += 256u) __builtin_nontemporal_store(s_s[k], tok_start + to.x + k);
-    for (uint32_t k = threadIdx.x; k < te; k += 256u) __builtin_nontemporal_store(s_e[k], tok_end + to.y + k);
 }
 
 // ---------------------------------------------------------------------------
@@ -4837,167 +4127,6 @@ __global__ __launch_bounds__(256) void k_long(const uint8_t* __restrict__ text, 
     }
 }
 
-// Boundary-mask output (jb_cut_batch_mask): a piece's token bitmaps (bit j = byte j
-// of the piece, u32 words) into the range's u64 bitmaps at bit offset `rel`, bits
-// of other pieces untouched: a word the piece shares with its neighbours (its first
-// and last) is ORed in, the others stored.  Pieces of one range run in order on one
-// stream over bitmaps cleared at the start.  Counts the piece's token starts and
-// ends into the counters (the spans kernels do not run in this mode).
-// A pipeline run's counters and summed tile block counts, written straight into
-// mapped pinned host memory (cut_range: no copy-engine transfer on the kernels'
-// stream, where it would queue behind the bulk copies of later pieces).
-// out: u32[kSnapWords]: counters[0..CNT_CLEAR), then u64 blocks, u64 zh blocks.
-__global__ __launch_bounds__(256) void k_snap(const uint32_t* __restrict__ counters, const uint2* __restrict__ tile_cnt,
-                                              uint32_t ntiles, uint32_t* __restrict__ out) {
-    __shared__ unsigned long long red[8];
-    unsigned long long b = 0, z = 0;
-    for (uint32_t t = threadIdx.x; t < ntiles; t += 256u) {
-        const uint2 c = tile_cnt[t];
-        b += c.x;
-        z += c.y;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        b += (unsigned long long)__shfl_xor((long long)b, d, 64);
-        z += (unsigned long long)__shfl_xor((long long)z, d, 64);
-    }
-    if ((threadIdx.x & 63u) == 0) {
-        red[threadIdx.x >> 6] = b;
-        red[4 + (threadIdx.x >> 6)] = z;
-    }
-    __syncthreads();
-    if (threadIdx.x < CNT_CLEAR) out[threadIdx.x] = counters[threadIdx.x];
-    if (threadIdx.x == 0) {
-        const unsigned long long bs = red[0] + red[1] + red[2] + red[3], zs = red[4] + red[5] + red[6] + red[7];
-        out[CNT_CLEAR] = (uint32_t)bs;
-        out[CNT_CLEAR + 1] = (uint32_t)(bs >> 32);
-        out[CNT_CLEAR + 2] = (uint32_t)zs;
-        out[CNT_CLEAR + 3] = (uint32_t)(zs >> 32);
-    }
-    __threadfence_system();
-}
-
-// Zero n u32 words (instead of hipMemsetAsync, which may go to the copy engine and
-// queue there behind the host pipeline's bulk transfers).
-__global__ __launch_bounds__(256) void k_zero(uint32_t* __restrict__ p, uint64_t n, bool v4,
-                                             uint32_t* __restrict__ p2, uint32_t n2) {
-    const uint64_t stride = (uint64_t)gridDim.x * 256u, t0 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (t0 < n2) p2[t0] = 0u;  // a second, small range (n2 <= 256) in the same launch
-    const uint64_t n4 = v4 ? n / 4u : 0u;
-    uint4* p4 = reinterpret_cast<uint4*>(p);
-    for (uint64_t i = t0; i < n4; i += stride) p4[i] = make_uint4(0u, 0u, 0u, 0u);
-    for (uint64_t i = 4u * n4 + t0; i < n; i += stride) p[i] = 0u;
-}
-
-hipError_t run_zero(void* p, uint64_t bytes, hipStream_t stream, void* p2, uint32_t bytes2) {
-    const uint64_t n = bytes / 4u;  // (callers pass whole words)
-    if (!n && !bytes2) return hipSuccess;
-    const bool v4 = ((uintptr_t)p & 15u) == 0;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(2048u, (n / 4u + 255u) / 256u + 1u);
-    hipLaunchKernelGGL(k_zero, dim3(grid), dim3(256), 0, stream, reinterpret_cast<uint32_t*>(p), n, v4,
-                       reinterpret_cast<uint32_t*>(p2), bytes2 / 4u);
-    return hipGetLastError();
-}
-
-hipError_t run_snap(const Work& w, uint64_t nbytes, uint32_t* out, hipStream_t stream) {
-    const uint32_t ntiles = (uint32_t)((nbytes + kTileBytes - 1) / kTileBytes);
-    hipLaunchKernelGGL(k_snap, dim3(1), dim3(256), 0, stream, w.counters, w.tile_cnt, ntiles, out);
-    return hipGetLastError();
-}
-
-// Spans packed for the trip back to the host (jb_cut_batch's spans mode): token i as
-// one u16, the gap from the previous token's end (0 for the first) in the low 6 bits and
-// its length in the high 10, so the host link carries 2 bytes per token instead of 8 (on
-// the C_syn corpus gaps stay under 63 bytes and tokens under 1,023: 0 escapes in 4.36M
-// tokens).  A gap of 63 or more or a length of 1,023 or more is written as 0xFFFF, with
-// the token's (index, start, end) appended to a side list.  hdr[b] is the end of the token
-// before token b x kPackBlock (0 for b = 0), so the host decodes blocks of kPackBlock
-// tokens independently.
-__global__ __launch_bounds__(256) void k_span_pack(const uint32_t* __restrict__ ts, const uint32_t* __restrict__ te,
-                                                   uint32_t* __restrict__ counters, uint16_t* __restrict__ pk,
-                                                   uint32_t* __restrict__ hdr, uint4* __restrict__ side,
-                                                   uint32_t side_cap) {
-    const uint32_t nt = counters[CNT_NWORDS];  // (the u64 token count's low word: a piece has < 2^31 tokens)
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nt; i += gridDim.x * 256u) {
-        const uint32_t a = ts[i], b = te[i], p = i ? te[i - 1u] : 0u;
-        const uint32_t g = a - p, l = b - a;
-        uint32_t x = g | (l << kPackGapBits);
-        if (g >= kPackGapEsc || l >= kPackLenEsc) {
-            x = 0xFFFFu;
-            const uint32_t k = atomicAdd(counters + CNT_SIDE, 1u);
-            if (k < side_cap) side[k] = make_uint4(i, a, b, 0u);
-            else atomicOr(counters + CNT_ERR, 4u);  // (cannot happen: side_cap bounds the escapes)
-        }
-        pk[i] = (uint16_t)x;
-        if ((i & (kPackBlock - 1u)) == 0u) hdr[i / kPackBlock] = p;
-    }
-}
-
-hipError_t run_span_pack(const uint32_t* ts, const uint32_t* te, uint32_t* counters, uint16_t* pk, uint32_t* hdr,
-                         uint4* side, uint32_t side_cap, uint64_t max_tokens, hipStream_t stream) {
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(4096u, (max_tokens + 255u) / 256u));
-    hipLaunchKernelGGL(k_span_pack, dim3(grid), dim3(256), 0, stream, ts, te, counters, pk, hdr, side, side_cap);
-    return hipGetLastError();
-}
-
-constexpr uint32_t kMergeWords = 16;  // k_mask_merge: output words per thread
-__global__ __launch_bounds__(256) void k_mask_merge(const uint32_t* __restrict__ sbits,
-                                                    const uint32_t* __restrict__ ebits, uint64_t n, uint64_t rel,
-                                                    uint64_t* __restrict__ ms, uint64_t* __restrict__ me,
-                                                    uint32_t* __restrict__ counters) {
-    __shared__ uint32_t red[8];
-    const uint32_t sh = (uint32_t)(rel & 63u);
-    const uint64_t nout = (sh + n + 63u) >> 6, nw32 = (n + 31u) >> 5;
-    auto piece64 = [&](const uint32_t* b, int64_t i) -> uint64_t {  // piece bits [64i, 64i + 64)
-        if (i < 0) return 0ull;
-        const uint64_t lo = 2u * (uint64_t)i, hi = lo + 1u;
-        return (lo < nw32 ? (uint64_t)b[lo] : 0ull) | ((hi < nw32 ? (uint64_t)b[hi] : 0ull) << 32);
-    };
-    uint32_t cs = 0, ce = 0;
-    const uint64_t t0 = (uint64_t)blockIdx.x * (256u * kMergeWords) + threadIdx.x;
-#pragma unroll 4
-    for (uint32_t j = 0; j < kMergeWords; j++) {
-        const uint64_t t = t0 + 256u * j;  // (consecutive threads: consecutive words)
-        if (t >= nout) break;
-        uint64_t os = piece64(sbits, (int64_t)t), oe = piece64(ebits, (int64_t)t);
-        if (sh) {
-            os = (os << sh) | (piece64(sbits, (int64_t)t - 1) >> (64u - sh));
-            oe = (oe << sh) | (piece64(ebits, (int64_t)t - 1) >> (64u - sh));
-        }
-        const uint64_t w = (rel >> 6) + t;
-        if (t == 0 || t == nout - 1u) {
-            if (os) atomicOr(reinterpret_cast<unsigned long long*>(ms + w), (unsigned long long)os);
-            if (oe) atomicOr(reinterpret_cast<unsigned long long*>(me + w), (unsigned long long)oe);
-        } else {
-            ms[w] = os;
-            me[w] = oe;
-        }
-        cs += (uint32_t)__popcll(os);
-        ce += (uint32_t)__popcll(oe);
-    }
-    // one set of counter atomics per workgroup (one per wave serialised on three addresses)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cs += (uint32_t)__shfl_xor((int)cs, d, 64);
-        ce += (uint32_t)__shfl_xor((int)ce, d, 64);
-    }
-    const uint32_t wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0) {
-        red[wv] = cs;
-        red[4 + wv] = ce;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        cs = red[0] + red[1] + red[2] + red[3];
-        ce = red[4] + red[5] + red[6] + red[7];
-        if (cs | ce) {
-            atomicAdd(counters + CNT_NTOK, cs);
-            atomicAdd(counters + CNT_NTOKE, ce);
-            atomicAdd(reinterpret_cast<unsigned long long*>(counters + CNT_NWORDS), (unsigned long long)cs);
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------
 // k_small: a whole small batch (<= kSmallBytes of text) in one workgroup, for
 // single Cut calls (tokenizer.go:151-162; BASELINE config 1).  The eleven-kernel
@@ -5108,73 +4237,6 @@ __device__ __forceinline__ double quad_perm_f64(double x) {
     const int lo = __builtin_amdgcn_mov_dpp((int)i, CTRL, 0xF, 0xF, false);
     const int hi = __builtin_amdgcn_mov_dpp((int)(i >> 32), CTRL, 0xF, 0xF, false);
     return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-
-// viterbi_run (:668-756) + viterbi_back + cutHMM (:273-285) for the m runes with
-// ordinals [ha, ha + m) ending at byte re, by the four lanes of a quad: lane s holds
-// state s (B, M, E, S: HMMstates order, :685) and takes its two candidates
-// (stateChange, :24-29) from the other lanes with DPP, so a rune is one short
-// chain instead of four serial routes.  Lane 0 then runs the traceback and emits.
-template <class E>
-__device__ void sm_viterbi(SmallLds& s, uint32_t ha, uint32_t re, uint32_t m, E& em, uint32_t ql,
-                           uint64_t* xc = nullptr) {
-    const uint32_t rs = s.hpos[ha];
-    if (m == 1) {  // always "S" for a single rune (:672-674)
-        if (ql == 0) em.token(rs, re);
-        return;
-    }
-    // B <- (E, S), M <- (B, M), E <- (B, M), S <- (E, S)
-    const double ta = ql == 0 ? T_EB : (ql == 1 ? T_BM : (ql == 2 ? T_BE : T_ES));
-    const double tb = ql == 0 ? T_SB : (ql == 1 ? T_MM : (ql == 2 ? T_ME : T_SS));
-    double vv = (ql == 0 ? START_B : (ql == 3 ? START_S : JB_MIN_FLOAT)) + s.sem[ha][ql];
-    double en = s.sem[ha + 1u][ql];
-    uint32_t nt = 0;
-    for (uint32_t h = ha + 1u; h < ha + m; h++) {
-        const double enn = s.sem[h + 1u][ql];  // (past the run: a harmless read)
-        const double a = quad_perm_f64<2 | (0 << 2) | (0 << 4) | (2 << 6)>(vv) + ta;
-        const double b = quad_perm_f64<3 | (1 << 2) | (1 << 4) | (3 << 6)>(vv) + tb;
-        // stateTransitionRoute (:736-756): strict '>' against minFloat, code 2 = no route
-        uint32_t c = 2u;
-        double best = JB_MIN_FLOAT;
-        if (a > best) { c = 0u; best = a; }
-        if (b > best) { c = 1u; best = b; }
-        nt += (a == b && a > JB_MIN_FLOAT) ? 1u : 0u;
-        vv = best + en;
-        s.bp4[h][ql] = (uint8_t)c;
-        en = enn;
-    }
-    em.ties += nt;
-    const double vE = quad_perm_f64<0xAA>(vv), vS = quad_perm_f64<0xFF>(vv);
-    if (xc) xc[1] = __builtin_amdgcn_s_memtime();  // (JB_DEBUG sub-phase clocks: forward half done)
-    if (ql != 0) return;
-    // traceback (:715-729): stops at the first "" route, and cutHMM then labels the
-    // runes from the run start (viterbi_back)
-    uint32_t st = vE > vS ? (uint32_t)JB_E : (uint32_t)JB_S, t = m - 1u, reset = 0, h = ha + m - 1u;
-    for (;;) {
-        if (t == 0) {
-            s.sbl[h] = (uint8_t)st;
-            break;
-        }
-        const uint32_t code = s.bp4[h][st];
-        s.sbl[h] = (uint8_t)st;
-        if (code == 2u) {
-            reset = t;
-            break;
-        }
-        st = (st == JB_B || st == JB_S) ? 2u + code : code;  // B,S <- {E,S}; M,E <- {B,M}
-        --t;
-        --h;
-    }
-    if (xc) xc[2] = __builtin_amdgcn_s_memtime();  // (traceback done)
-    uint32_t ts = rs;
-    for (uint32_t k = 0; k < m - reset; k++) {
-        const uint32_t lab = s.sbl[h + k];
-        const uint32_t qa = ha + k + 1u < ha + m ? s.hpos[ha + k + 1u] : re;  // end of rune k
-        if (lab >= (uint32_t)JB_E) {
-            em.token(ts, qa);
-            ts = qa;
-        }
-    }
 }
 
 // The end of a run's viterbi (:723-729) + traceback + cutHMM, after its forward half
@@ -5563,10 +4625,6 @@ __global__ __launch_bounds__(kSmallThreads) void k_small(const uint8_t* __restri
             xc[5] = __builtin_amdgcn_s_memtime();
             clk[12] = __builtin_amdgcn_s_memrealtime();
         }
-#ifndef JB_SM_FUSED
-#define JB_SM_FUSED 1
-#endif
-#if JB_SM_FUSED
         // forward path (findDagPath, :552-562) fused with the forward half of each HMM
         // run's viterbi (cutZh, :221-255; viterbi, :668-730): a single-rune piece is one
         // Viterbi step of the run it extends (lane ql of the quad holds state ql and takes
@@ -5645,38 +4703,6 @@ __global__ __launch_bounds__(kSmallThreads) void k_small(const uint8_t* __restri
             if (ql == 0) s.err = 1u;
             continue;
         }
-#else
-        // forward path (findDagPath, :552-562) + HMM runs (cutZh, :221-255)
-        uint32_t run_h = 0, run_n = 0;
-        bool ok = true;
-        for (h = h0; h < h1;) {
-            const uint32_t L = s.sL[h], p = s.hpos[h];
-            if (L == 0) {  // tail index -1: cutDAG's slice panics in the reference
-                ok = false;
-                break;
-            }
-            const uint32_t pe = h + L < h1 ? s.hpos[h + L] : be;
-            if (!HMM) {
-                if (ql == 0) em.token(p, pe);
-            } else if (L == 1) {
-                if (run_n == 0) run_h = h;
-                run_n++;
-            } else {
-                if (run_n) {
-                    sm_viterbi(s, run_h, p, run_n, em, ql);
-                    run_n = 0;
-                }
-                if (ql == 0) em.token(p, pe);
-            }
-            h += L;
-        }
-        if (!ok) {
-            if (ql == 0) s.err = 1u;
-            continue;
-        }
-        if (t == 0) xc[0] = __builtin_amdgcn_s_memtime();  // (forward walk done)
-        if (HMM && run_n) sm_viterbi(s, run_h, be, run_n, em, ql, t == 0 ? xc : nullptr);
-#endif
         if (t == 0) clk[13] = __builtin_amdgcn_s_memrealtime();
     }
     em.flush();
@@ -5764,51 +4790,27 @@ uint32_t zh_waves_per_cu(bool hmm, bool wide) {
     return 4u * (hmm ? occ_zh<true, 4>() : occ_zh<false, 4>());
 }
 
+// The enqueue functions of this unit's kernels (jb_kstages.h): one launch each, for run_pipeline.
+void enq_docbits(const Work& w, const uint64_t* d_doc_off, uint32_t ndocs, uint64_t nbytes, uint32_t nttiles,
+                 hipStream_t stream) {
+    hipLaunchKernelGGL(k_docbits, dim3(std::max(1u, (std::max(ndocs, nttiles) + 255) / 256)), dim3(256), 0, stream,
+                       d_doc_off, ndocs, nbytes, w.docbits, w.counters, reinterpret_cast<uint64_t*>(w.ttile_cnt),
+                       nttiles);
+}
 
-#define JB_TIMED_ON(id, st, ...)                  \
-    do {                                          \
-        if (timer) timer->begin((id), (st));      \
-        __VA_ARGS__;                              \
-        if (timer) timer->end((id), (st));        \
-    } while (0)
-#define JB_TIMED(id, ...) JB_TIMED_ON(id, stream, __VA_ARGS__)
+void enq_mark_walk(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes, uint32_t ntiles,
+                   uint32_t split, uint32_t diag, hipStream_t stream) {
+    hipLaunchKernelGGL(k_mark_walk, dim3(ntiles << split), dim3(256), 0, stream, d_text, nbytes, w.docbits, im,
+                       w.lanemask, w.tile_cnt, w.erec + kErecPad, w.tile4, w.alnum16, w.sbits, w.ebits, diag,
+                       w.dbg_walk, split);
+}
 
-hipError_t run_pipeline(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes,
-                        const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, const LaunchCfg& lc,
-                        hipStream_t stream, KernelTimer* timer, const MaskOut* mask) {
-    const uint32_t diag = lc.diag;
-    const uint64_t nwords = (nbytes + 31) / 32;
-    const uint32_t ntiles = (uint32_t)((nbytes + kTileBytes - 1) / kTileBytes);
-    // k_zh work unit: a small batch gets small groups, so that enough waves share it
-    const uint32_t grp = lc.zh_group ? lc.zh_group : zh_group_for(nbytes);
-    const uint32_t nttiles = (uint32_t)((nwords + kTokTileWords - 1) / kTokTileWords);
-    // k_zh: a persistent grid, but no more 4-wave workgroups than the batch has groups
-    // the last zh_tail bytes (at most) in groups of zh_tail_group (tail_groups)
-    uint32_t g1, sgrp;
-    const uint64_t ngroups = zh_tail_groups(nbytes, grp, lc, &g1, &sgrp);
-    // the wide form (16 waves per workgroup, weights in LDS) for batches in 6 KiB groups whose
-    // weight table fits; JB_ZH_WIDE (lc.zh_wide) forces either form
-    const bool wide = im.nw1 <= kZhWtabWide && (lc.zh_wide > 0 || (lc.zh_wide < 0 && grp == kZhGroupBytes));
-    const uint32_t nw = wide ? kZhWgWide : 4u;
-    const uint32_t grid_zh = (uint32_t)std::max<uint64_t>(
-        1, std::min<uint64_t>((wide ? lc.zh_waves_wide : lc.zh_waves) / nw, (ngroups + nw - 1) / nw));
-    // No clearing pass: the document bitmap is all zeros between runs (k_nonzh clears
-    // what k_docbits set; a fresh or dirty workspace is cleared by the caller), k_docbits
-    // clears the counters and k_mark_walk the token bitmaps, tile by tile.
-    if (nbytes == 0)  // (kernels, not hipMemsetAsync: see k_zero)
-        return run_zero(w.doc_tok, (ndocs + 1) * sizeof(uint64_t), stream, w.counters, CNT_CLEAR * sizeof(uint32_t));
-    JB_TIMED(K_DOCBITS, hipLaunchKernelGGL(k_docbits, dim3(std::max(1u, (std::max(ndocs, nttiles) + 255) / 256)),
-                                           dim3(256), 0, stream, d_doc_off, ndocs, nbytes, w.docbits, w.counters,
-                                           reinterpret_cast<uint64_t*>(w.ttile_cnt), nttiles));
-    // a batch with fewer tiles than CUs: two workgroups per tile (k_mark_walk's split)
-    const uint32_t mws = lc.mw_split >= 0 ? (uint32_t)lc.mw_split : (ntiles <= lc.ncu ? 1u : 0u);
-    JB_TIMED(K_MARK_WALK, hipLaunchKernelGGL(k_mark_walk, dim3(ntiles << mws), dim3(256), 0, stream, d_text, nbytes,
-                                             w.docbits, im, w.lanemask, w.tile_cnt, w.erec + kErecPad,
-                                             w.tile4, w.alnum16, w.sbits, w.ebits, diag, w.dbg_walk, mws));
-#define JB_ZH_LAUNCH(H, N)                                                                                      \
-    JB_TIMED(K_ZH, hipLaunchKernelGGL((k_zh<H, N>), dim3(grid_zh), dim3((N) * 64), 0, stream, d_text, nbytes,       \
-                                      w.lanemask, w.tile_cnt, w.tile4, w.counters, im, w.erec + kErecPad, w.gbl,     \
-                                      w.gbest, w.sbits, w.ebits, w.longblk, w.lsegb, grp, g1, sgrp, diag, w.dbg))
+void enq_zh(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes, bool hmm, bool wide,
+            uint32_t grid, uint32_t grp, uint32_t g1, uint32_t sgrp, uint32_t diag, hipStream_t stream) {
+#define JB_ZH_LAUNCH(H, N)                                                                                          \
+    hipLaunchKernelGGL((k_zh<H, N>), dim3(grid), dim3((N) * 64), 0, stream, d_text, nbytes, w.lanemask, w.tile_cnt, \
+                       w.tile4, w.counters, im, w.erec + kErecPad, w.gbl, w.gbest, w.sbits, w.ebits, w.longblk,     \
+                       w.lsegb, grp, g1, sgrp, diag, w.dbg)
     if (hmm) {
         if (wide) JB_ZH_LAUNCH(true, kZhWgWide);
         else JB_ZH_LAUNCH(true, 4u);
@@ -5817,809 +4819,72 @@ hipError_t run_pipeline(const DevImage& im, const Work& w, const uint8_t* d_text
         else JB_ZH_LAUNCH(false, 4u);
     }
 #undef JB_ZH_LAUNCH
-    bool nz_done = false;  // (k_nonzh's work ran inside k_long)
-    {
-        // long blocks: the chain, then one lane per 64-rune segment (at most
-        // nbytes / 192 + nbytes / kZhLongMin segments), one wave per block
-        const uint64_t segs = nbytes / (3u * kSeg) + nbytes / kZhLongMin + 2u;
-        const uint32_t gseg = (uint32_t)std::min<uint64_t>(1024u, (segs + 255u) / 256u);
-        const uint32_t spec = lc.long_spec;
-        if (lc.long_fused) {
-            // one workgroup per 64 segments (k_long_spec's lanes), at most one per CU; a batch of at most
-            // JB_NZ_FUSE_MIB MiB (default 4) runs k_nonzh's work in it too (one launch less)
-            uint32_t gl = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(lc.ncu, (segs + 63u) / 64u));
-            const bool nzf = nbytes <= ((uint64_t)lc.nz_fuse_mib << 20);
-            const NzArgs nz{(uint32_t)nbytes, ntiles, ndocs, w.lanemask, w.tile_cnt, w.alnum16, w.docbits, d_doc_off};
-            if (nzf) gl = std::max(gl, (uint32_t)((nbytes + 1023u) / 1024u + 255u) / 256u);
-#define JB_LONG_LAUNCH(H, N)                                                                                           \
-    JB_TIMED(K_LONG, hipLaunchKernelGGL((k_long<H, N>), dim3(gl), dim3(256), 0, stream, d_text, im, w.erec + kErecPad, \
-                                        w.longblk, w.lsegb, w.counters, w.tile4, w.gbl, w.gbest, w.lbp, w.lmap, w.lcx, \
-                                        w.lpath, w.lflag, w.sbits, w.ebits, w.dbg, spec, nz, lc.long_wait_ticks))
-            if (hmm && nzf) JB_LONG_LAUNCH(true, true);
-            else if (hmm) JB_LONG_LAUNCH(true, false);
-            else if (nzf) JB_LONG_LAUNCH(false, true);
-            else JB_LONG_LAUNCH(false, false);
-#undef JB_LONG_LAUNCH
-            nz_done = nzf;
-        } else {
-        if (spec)
-            JB_TIMED(K_LONG_SPEC, hipLaunchKernelGGL(k_long_spec, dim3(kSpecGrid), dim3(64), 0, stream, d_text, im,
-                                                     w.erec + kErecPad, w.longblk, w.lsegb, w.counters, w.tile4, w.gbl,
-                                                     w.gbest, w.lbp, w.lmap, w.lflag, lc.long_spec));
-        if (spec && lc.long_spec != 3u) {  // the path of the decided choices (the path chain's blocks, lflag 3)
-            JB_TIMED(K_LONG_PATH, hipLaunchKernelGGL(k_long_path, dim3(kLongGrid), dim3(64), 0, stream, w.longblk,
-                                                     w.lsegb, w.counters, w.lflag, w.lbp, w.lmap, w.lcx, 3u, 3u));
-            JB_TIMED(K_LONG_PBITS, hipLaunchKernelGGL(k_long_pbits, dim3(gseg), dim3(256), 0, stream, w.longblk, w.lsegb,
-                                                      w.counters, w.lflag, w.gbl, w.lbp, w.lcx, w.lpath));
-        }
-        if (hmm)
-            JB_TIMED(K_LONG_DP, hipLaunchKernelGGL((k_long_dp<true>), dim3(kLongGrid), dim3(256), 0, stream, d_text, im,
-                                                   w.erec + kErecPad, w.gbl, w.gbest, w.longblk, w.counters, w.sbits,
-                                                   w.ebits, w.lflag, w.lsegb, w.lpath, w.dbg, spec));
-        else
-            JB_TIMED(K_LONG_DP, hipLaunchKernelGGL((k_long_dp<false>), dim3(kLongGrid), dim3(256), 0, stream, d_text, im,
-                                                   w.erec + kErecPad, w.gbl, w.gbest, w.longblk, w.counters, w.sbits,
-                                                   w.ebits, w.lflag, w.lsegb, w.lpath, w.dbg, spec));
-        JB_TIMED(K_LONG_SEG, hipLaunchKernelGGL(k_long_seg, dim3(gseg), dim3(256), 0, stream, d_text, im,
-                                                w.erec + kErecPad, w.longblk, w.lsegb, w.counters, w.lflag, w.gbest,
-                                                w.gbl, w.lbp, w.lmap));
-        JB_TIMED(K_LONG_PATH, hipLaunchKernelGGL(k_long_path, dim3(kLongGrid), dim3(64), 0, stream, w.longblk, w.lsegb,
-                                                 w.counters, w.lflag, w.lbp, w.lmap, w.lcx, 2u, 1u));
-        // (the Viterbi back-pointers go to gbest's bytes: the exit codes in lbp are read to the end)
-        uint8_t* const bp = reinterpret_cast<uint8_t*>(w.gbest);
-        if (hmm)
-            JB_TIMED(K_LONG_TAIL, hipLaunchKernelGGL((k_long_tail<true>), dim3(gseg), dim3(256), 0, stream, d_text, im,
-                                                     w.gbl, w.longblk, w.lsegb, w.lflag, w.counters, w.lbp, w.lcx, bp,
-                                                     w.sbits, w.ebits));
-        else
-            JB_TIMED(K_LONG_TAIL, hipLaunchKernelGGL((k_long_tail<false>), dim3(gseg), dim3(256), 0, stream, d_text, im,
-                                                     w.gbl, w.longblk, w.lsegb, w.lflag, w.counters, w.lbp, w.lcx, bp,
-                                                     w.sbits, w.ebits));
-        }
-    }
-    if (!nz_done) {
-        const uint32_t nw = (uint32_t)((nbytes + 1023u) / 1024u);  // alnum16 words
-        JB_TIMED(K_NONZH, hipLaunchKernelGGL(k_nonzh, dim3((nw + 255u) / 256u), dim3(256), 0, stream, d_text,
-                                             (uint32_t)nbytes, w.lanemask, w.tile_cnt, ntiles, w.alnum16, w.sbits,
-                                             w.ebits, w.docbits, d_doc_off, ndocs));
-    }
-    if (mask) {  // boundary masks instead of spans
-        const uint64_t nout = ((mask->rel & 63u) + nbytes + 63u) >> 6;
-        JB_TIMED(K_MASK_MERGE, hipLaunchKernelGGL(k_mask_merge,
-                                                  dim3((uint32_t)((nout + 256u * kMergeWords - 1u) / (256u * kMergeWords))),
-                                                  dim3(256), 0,
-                                                  stream, w.sbits, w.ebits, nbytes, mask->rel, mask->s, mask->e,
-                                                  w.counters));
-        return hipGetLastError();
-    }
-    // the span kernels in one pass for batches of at most 256 token tiles (4 MiB): at 1 GiB
-    // (65K tiles) the look-back chains cost more than the passes it saves (0.33 -> 0.84 ms)
-    if (lc.tok1 && nttiles <= 256u) {
-        JB_TIMED(K_TOK1, hipLaunchKernelGGL(k_tok1, dim3(nttiles), dim3(256), 0, stream, w.sbits, w.ebits, nwords,
-                                            nttiles, reinterpret_cast<uint64_t*>(w.ttile_cnt), w.counters, w.tok_start,
-                                            w.tok_end, d_doc_off, ndocs, w.doc_tok));
-        return hipGetLastError();
-    }
-    JB_TIMED(K_TOK_COUNT, hipLaunchKernelGGL((k_tok<false>), dim3((nttiles + 1u) / 2u), dim3(256), 0, stream, w.sbits, w.ebits,
-                                             nwords, w.ttile_cnt, w.supt, w.counters, nullptr, nullptr));
-    if (nttiles > 256u)  // (k_tok's write pass reads the sums of whole groups of 256 tiles only)
-        JB_TIMED(K_SCAN_TOK, hipLaunchKernelGGL(k_sup, dim3((nttiles + 255) / 256), dim3(256), 0, stream,
-                                                w.ttile_cnt, nttiles, w.supt));
-    JB_TIMED(K_TOK_WRITE, hipLaunchKernelGGL((k_tok<true>), dim3(nttiles), dim3(256), 0, stream, w.sbits, w.ebits,
-                                             nwords, w.ttile_cnt, w.supt, w.counters, w.tok_start, w.tok_end));
-    if (ndocs >= kDocTokWide)
-        JB_TIMED(K_DOC_TOK, hipLaunchKernelGGL(k_doc_tok<1>, dim3((ndocs + 1 + 255) / 256), dim3(256), 0, stream,
-                                               d_doc_off, ndocs, w.tok_start, w.counters, w.doc_tok));
+}
+
+void enq_long_spec(const DevImage& im, const Work& w, const uint8_t* d_text, uint32_t spec, hipStream_t stream) {
+    hipLaunchKernelGGL(k_long_spec, dim3(kSpecGrid), dim3(64), 0, stream, d_text, im, w.erec + kErecPad, w.longblk,
+                       w.lsegb, w.counters, w.tile4, w.gbl, w.gbest, w.lbp, w.lmap, w.lflag, spec);
+}
+
+void enq_long_path(const Work& w, uint32_t want, uint32_t set, hipStream_t stream) {
+    hipLaunchKernelGGL(k_long_path, dim3(kLongGrid), dim3(64), 0, stream, w.longblk, w.lsegb, w.counters, w.lflag,
+                       w.lbp, w.lmap, w.lcx, want, set);
+}
+
+void enq_long_pbits(const Work& w, uint32_t gseg, hipStream_t stream) {
+    hipLaunchKernelGGL(k_long_pbits, dim3(gseg), dim3(256), 0, stream, w.longblk, w.lsegb, w.counters, w.lflag, w.gbl,
+                       w.lbp, w.lcx, w.lpath);
+}
+
+void enq_long_dp(const DevImage& im, const Work& w, const uint8_t* d_text, bool hmm, uint32_t spec,
+                 hipStream_t stream) {
+    if (hmm)
+        hipLaunchKernelGGL((k_long_dp<true>), dim3(kLongGrid), dim3(256), 0, stream, d_text, im, w.erec + kErecPad,
+                           w.gbl, w.gbest, w.longblk, w.counters, w.sbits, w.ebits, w.lflag, w.lsegb, w.lpath, w.dbg,
+                           spec);
     else
-        JB_TIMED(K_DOC_TOK, hipLaunchKernelGGL(k_doc_tok<16>, dim3((16u * (ndocs + 1) + 255) / 256), dim3(256), 0,
-                                               stream, d_doc_off, ndocs, w.tok_start, w.counters, w.doc_tok));
-    return hipGetLastError();
+        hipLaunchKernelGGL((k_long_dp<false>), dim3(kLongGrid), dim3(256), 0, stream, d_text, im, w.erec + kErecPad,
+                           w.gbl, w.gbest, w.longblk, w.counters, w.sbits, w.ebits, w.lflag, w.lsegb, w.lpath, w.dbg,
+                           spec);
 }
 
-// ---------------------------------------------------------------------------
-// Search mode (jieba's cut_for_search on this reference's DAG): a pass over the
-// spans of a finished run.  For a Han token of n runes at bytes p_0 < ... < p_n:
-// n > 2: [p_i, p_i+2) for every i with a 2-rune edge in buildDag's DAG of the
-// token, ascending; n > 3: then [p_i, p_i+3) likewise; then the token.  Every
-// other token is copied.  An edge of rune i is read from its record erec[p_i / 3]
-// (k_mark_walk: bit L-1 of the mask = an edge of L runes; the record was built on
-// the whole Han run, so the caller keeps only grams that end inside the token); a
-// zero record (overflowed, or DevImage::plainw == 0) is answered by two trie steps
-// with dp_walk_rune's rules.  Nearly every token takes the fast form (srch_masks): no 4-byte rune
-// near it, so its runes and records sit at fixed strides and all its loads are issued at once.
-// Three launches, no waits between workgroups: k_srch_count (spans per token and
-// per tile of kSrchTile tokens), k_sup over the tile sums, k_srch_write (the tile's
-// prefix as k_tok's write pass finds it, pf_load / pf_sum; the spans); then
-// k_srch_doc maps doc_tok through the offsets.
-// Thread t of a tile owns tokens j * 256 + t (j < kSrchPer): every load and
-// store of the token arrays is coalesced, and the scan runs over (j, t) in that order.
-// ---------------------------------------------------------------------------
-constexpr uint32_t kSrchNone = 0xFFFFFFFFu;
-// the byte after the Han rune at p, or kSrchNone when no whole rune starts at p inside [.., e)
-__device__ __forceinline__ uint32_t srch_next(const uint8_t* __restrict__ text, uint32_t p, uint32_t e) {
-    if (p >= e) return kSrchNone;  // (also p == kSrchNone)
-    const uint32_t q = p + (text[p] >= 0xF0u ? 4u : 3u);
-    return q <= e ? q : kSrchNone;
-}
-__device__ __forceinline__ uint32_t srch_rune(const uint8_t* __restrict__ text, uint32_t p) {  // valid UTF-8, 3 or 4 bytes
-    const uint32_t x = ld4(text, p), b0 = x & 0xFFu;
-    const uint32_t r3 = ((b0 & 0x0Fu) << 12) | (((x >> 8) & 0x3Fu) << 6) | ((x >> 16) & 0x3Fu);
-    const uint32_t r4 = ((b0 & 0x07u) << 18) | (((x >> 8) & 0x3Fu) << 12) | (((x >> 16) & 0x3Fu) << 6) |
-                        ((x >> 24) & 0x3Fu);
-    return b0 >= 0xF0u ? r4 : r3;
-}
-// bit 0: E(i, 2), bit 1: E(i, 3) for the rune at a, whose next two runes start at b and (third
-// == true) at c, all inside the token.  rc: the rune's record.
-__device__ __forceinline__ uint32_t srch_edges(const uint8_t* __restrict__ text, const DevImage& im, uint64_t rc,
-                                               uint32_t a, uint32_t b, uint32_t c, bool third) {
-    if (rc) return (uint32_t)(rc >> 1) & 3u;
-    const uint32_t r0 = srch_rune(text, a), r1 = srch_rune(text, b);
-    if (r0 >= 0x110000u || r1 >= 0x110000u) return 0u;  // (not in a Han token)
-    const uint32_t id = rune_code(im, r0);
-    const uint64_t cc = im.cells[id];
-    if (jb_cell_check(cc) != JB_CHECK_ROOT || jb_cell_fc(cc) == JB_FC_ZERO || !jb_cell_hc(cc)) return 0u;
-    const uint32_t t1 = dat_slot(im, cc, r1);
-    const uint64_t c1 = im.cells[t1];
-    if (!dat_hit(c1, id)) return 0u;
-    uint32_t m = jb_cell_fc(c1) == JB_FC_POS ? 1u : 0u;
-    if (third && jb_cell_hc(c1)) {
-        const uint32_t r2 = srch_rune(text, c);
-        if (r2 < 0x110000u) {
-            const uint32_t t2 = dat_slot(im, c1, r2);
-            const uint64_t c2 = im.cells[t2];
-            if (dat_hit(c2, t1) && jb_cell_fc(c2) == JB_FC_POS) m |= 2u;
-        }
-    }
-    return m;
-}
-// Does a token of at least nine bytes (three runes) whose first four bytes are x start with a Han rune?
-__device__ __forceinline__ bool srch_han(uint32_t x) {
-    uint32_t w;
-    return (x & 0x80u) != 0u && han_rune(x, 4u, &w) != 0u;
-}
-// The fast form.  A token whose tiles hold no 4-byte Han rune (tile4) has rune i at s + 3 i and its
-// records at consecutive slots, so no load waits for another: the edges of its runes as two masks,
-// bit i of m2 = E(i, 2) (i <= n - 2), bit i of m3 = E(i, 3) (n > 3, i <= n - 3).  han: the token starts
-// with a Han rune (the caller's load; only then may a zero record be walked).  False: the token has more
-// than kSrchFastN runes or may hold a 4-byte rune, and takes the general form (srch_grams).
-constexpr uint32_t kSrchFastN = 32;
-__device__ __forceinline__ bool srch_masks(const uint8_t* __restrict__ text, const DevImage& im,
-                                           const uint64_t* __restrict__ erec, const uint32_t* __restrict__ tile4,
-                                           uint32_t s, uint32_t e, bool han, uint32_t& m2, uint32_t& m3) {
-    const uint32_t n = (e - s) / 3u;
-    if (n * 3u != e - s || n > kSrchFastN) return false;
-    const bool all3 = (tile4[s / kTileBytes] | tile4[(e - 1u) / kTileBytes]) == 0u;
-    const uint64_t* const rp = erec + s / 3u;
-    uint32_t a2 = 0, a3 = 0;
-    for (uint32_t i = 0; i + 1u < n; i += 4u) {  // runes i .. i+3 of 0 .. n-2
-        uint64_t r[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; k++) r[k] = rp[i + k];  // (slots past the last rune are read and dropped)
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; k++) {
-            const uint32_t q = i + k, a = s + 3u * q;
-            if (q + 1u < n) {
-                uint32_t m = (uint32_t)(r[k] >> 1) & 3u;
-                if (r[k] == 0ull) m = han && all3 ? srch_edges(text, im, 0ull, a, a + 3u, a + 6u, q + 2u < n) : 0u;
-                a2 |= (m & 1u) << q;
-                a3 |= (m >> 1) << q;
-            }
-        }
-    }
-    m2 = a2;
-    m3 = n > 3u ? a3 & ((1u << (n - 2u)) - 1u) : 0u;
-    return all3;
-}
-// The grams of one length (L = 2, 3) or both (L = 0) of the Han token [s, e), in text order:
-// f(L, from, to).  A token of n runes has 2-grams when n > 2 and 3-grams when n > 3.
-template <uint32_t L, class F>
-__device__ __forceinline__ void srch_grams(const uint8_t* __restrict__ text, const DevImage& im,
-                                           const uint64_t* __restrict__ erec, uint32_t s, uint32_t e, F&& f) {
-    uint32_t a = s, b = srch_next(text, a, e), c = srch_next(text, b, e), d = srch_next(text, c, e);
-    if (c == kSrchNone || c >= e) return;  // n <= 2
-    const bool n3 = d != kSrchNone && d < e;  // n > 3
-    if (L == 3u && !n3) return;
-    while (c != kSrchNone) {  // the rune at a has a next rune [b, c)
-        const uint32_t m = srch_edges(text, im, erec[a / 3u], a, b, c, d != kSrchNone);
-        if (L != 3u && (m & 1u)) f(2u, a, c);
-        if (L != 2u && n3 && (m & 2u) && d != kSrchNone) f(3u, a, d);
-        a = b;
-        b = c;
-        c = d;
-        d = srch_next(text, d, e);
-    }
+void enq_long_seg(const DevImage& im, const Work& w, const uint8_t* d_text, uint32_t gseg, hipStream_t stream) {
+    hipLaunchKernelGGL(k_long_seg, dim3(gseg), dim3(256), 0, stream, d_text, im, w.erec + kErecPad, w.longblk, w.lsegb,
+                       w.counters, w.lflag, w.gbest, w.gbl, w.lbp, w.lmap);
 }
 
-// (96 SGPRs at most: the image's pointers would otherwise cost the eighth wave per SIMD)
-#define JB_SRCH_ATTR __attribute__((amdgpu_num_sgpr(96)))
-__global__ __launch_bounds__(256) JB_SRCH_ATTR void k_srch_count(const uint8_t* __restrict__ text, DevImage im,
-                                                    const uint64_t* __restrict__ erec,
-                                                    const uint32_t* __restrict__ ts, const uint32_t* __restrict__ te,
-                                                    const uint32_t* __restrict__ counters, uint32_t* __restrict__ off,
-                                                    uint2* __restrict__ tile, const uint32_t* __restrict__ tile4) {
-    __shared__ uint32_t lds[8];
-    const uint32_t n = counters[CNT_NTOK], i0 = blockIdx.x * kSrchTile + threadIdx.x;
-    uint32_t sum = 0;
-    if (blockIdx.x * kSrchTile < n) {
-        uint32_t s1 = 0, e1 = 0;  // the next token's span, loaded one trip ahead
-        if (i0 < n) {
-            s1 = ts[i0];
-            e1 = te[i0];
-        }
-        for (uint32_t j = 0; j < kSrchPer; j++) {
-            const uint32_t i = i0 + j * 256u;
-            if (i >= n) break;
-            const uint32_t s = s1, e = e1;
-            if (j + 1u < kSrchPer && i + 256u < n) {
-                s1 = ts[i + 256u];
-                e1 = te[i + 256u];
-            }
-            uint32_t cnt = 1u;
-            if (e - s >= 9u) {
-                const bool han = srch_han(ld4(text, s));
-                uint32_t m2, m3;
-                const bool fast = srch_masks(text, im, erec, tile4, s, e, han, m2, m3);
-                if (han && fast) cnt += __popc(m2) + __popc(m3);
-                else if (han) srch_grams<0u>(text, im, erec, s, e, [&](uint32_t, uint32_t, uint32_t) { cnt++; });
-            }
-            off[i] = cnt;
-            sum += cnt;
-        }
-    }
-    const uint2 t = pf_sum(PrefixLoads{sum, 0u}, lds);
-    if (threadIdx.x == 0) tile[blockIdx.x] = make_uint2(t.x, 0u);  // (0 for the tiles past the last token)
+void enq_long_tail(const DevImage& im, const Work& w, const uint8_t* d_text, bool hmm, uint32_t gseg,
+                   hipStream_t stream) {
+    // (the Viterbi back-pointers go to gbest's bytes: the exit codes in lbp are read to the end)
+    uint8_t* const bp = reinterpret_cast<uint8_t*>(w.gbest);
+    if (hmm)
+        hipLaunchKernelGGL((k_long_tail<true>), dim3(gseg), dim3(256), 0, stream, d_text, im, w.gbl, w.longblk,
+                           w.lsegb, w.lflag, w.counters, w.lbp, w.lcx, bp, w.sbits, w.ebits);
+    else
+        hipLaunchKernelGGL((k_long_tail<false>), dim3(gseg), dim3(256), 0, stream, d_text, im, w.gbl, w.longblk,
+                           w.lsegb, w.lflag, w.counters, w.lbp, w.lcx, bp, w.sbits, w.ebits);
 }
 
-__global__ __launch_bounds__(256) JB_SRCH_ATTR void k_srch_write(const uint8_t* __restrict__ text, DevImage im,
-                                                    const uint64_t* __restrict__ erec,
-                                                    const uint32_t* __restrict__ ts, const uint32_t* __restrict__ te,
-                                                    uint32_t* __restrict__ counters, uint32_t* __restrict__ off,
-                                                    const uint2* __restrict__ tile, const uint2* __restrict__ sup,
-                                                    uint32_t* __restrict__ os, uint32_t* __restrict__ oe,
-                                                    uint64_t* ontok, const uint32_t* __restrict__ tile4) {
-    __shared__ uint32_t lds[8];
-    __shared__ uint32_t s_tot[kSrchPer * 4u], s_pre[kSrchPer * 4u];
-    static_assert(kSrchPer * 4u == 64u, "the (row, wave) totals are scanned by one wave");
-    const uint32_t n = counters[CNT_NTOK], t0 = blockIdx.x * kSrchTile, i0 = t0 + threadIdx.x;
-    if (t0 >= n && blockIdx.x != 0u) return;  // (the whole workgroup)
-    const PrefixLoads pl = pf_load(tile, sup, blockIdx.x);
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    uint32_t c[kSrchPer], x[kSrchPer];
-#pragma unroll
-    for (uint32_t j = 0; j < kSrchPer; j++) c[j] = i0 + j * 256u < n ? off[i0 + j * 256u] : 0u;
-#pragma unroll
-    for (uint32_t j = 0; j < kSrchPer; j++) {
-        x[j] = wave_incl_scan(c[j]);
-        if (lane == 63u) s_tot[j * 4u + wid] = x[j];
-    }
-    const uint2 tb = pf_sum(pl, lds);  // (its barriers also publish s_tot)
-    if (threadIdx.x < 64u) {
-        const uint32_t v = s_tot[threadIdx.x];
-        s_pre[threadIdx.x] = wave_incl_scan(v) - v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t j = 0; j < kSrchPer; j++)
-        if (i0 + j * 256u < n) off[i0 + j * 256u] = tb.x + s_pre[j * 4u + wid] + x[j] - c[j];
-    if (threadIdx.x == 0 && t0 + kSrchTile >= n) {  // the last tile: the expanded count
-        const uint64_t tot = (uint64_t)tb.x + s_pre[63] + s_tot[63];
-        *reinterpret_cast<uint64_t*>(counters + CNT_NSRCH) = tot;
-        *ontok = tot;
-    }
-    uint32_t s1 = 0, e1 = 0, k1 = 0;  // the next token's span and offset, loaded one trip ahead
-    if (i0 < n) {
-        s1 = ts[i0];
-        e1 = te[i0];
-        k1 = off[i0];  // (this thread's own store)
-    }
-    for (uint32_t j = 0; j < kSrchPer; j++) {
-        const uint32_t i = i0 + j * 256u;
-        if (i >= n) break;
-        const uint32_t s = s1, e = e1;
-        uint32_t k = k1;
-        if (j + 1u < kSrchPer && i + 256u < n) {
-            s1 = ts[i + 256u];
-            e1 = te[i + 256u];
-            k1 = off[i + 256u];
-        }
-        bool han = false, fast = false;
-        uint32_t m2 = 0, m3 = 0;
-        if (e - s >= 9u) {
-            han = srch_han(ld4(text, s));
-            fast = srch_masks(text, im, erec, tile4, s, e, han, m2, m3);
-        }
-        if (han && fast) {
-            for (; m2; m2 &= m2 - 1u, k++) {
-                const uint32_t a = s + 3u * (uint32_t)__builtin_ctz(m2);
-                os[k] = a;
-                oe[k] = a + 6u;
-            }
-            for (; m3; m3 &= m3 - 1u, k++) {
-                const uint32_t a = s + 3u * (uint32_t)__builtin_ctz(m3);
-                os[k] = a;
-                oe[k] = a + 9u;
-            }
-        } else if (han) {
-            srch_grams<2u>(text, im, erec, s, e, [&](uint32_t, uint32_t a, uint32_t b) {
-                os[k] = a;
-                oe[k] = b;
-                k++;
-            });
-            srch_grams<3u>(text, im, erec, s, e, [&](uint32_t, uint32_t a, uint32_t b) {
-                os[k] = a;
-                oe[k] = b;
-                k++;
-            });
-        }
-        os[k] = s;
-        oe[k] = e;
-    }
+void enq_long(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes, uint32_t ntiles,
+              const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, bool nzf, uint32_t grid, uint32_t spec,
+              uint32_t wait_ticks, hipStream_t stream) {
+    const NzArgs nz{(uint32_t)nbytes, ntiles, ndocs, w.lanemask, w.tile_cnt, w.alnum16, w.docbits, d_doc_off};
+#define JB_LONG_LAUNCH(H, N)                                                                                     \
+    hipLaunchKernelGGL((k_long<H, N>), dim3(grid), dim3(256), 0, stream, d_text, im, w.erec + kErecPad, w.longblk, \
+                       w.lsegb, w.counters, w.tile4, w.gbl, w.gbest, w.lbp, w.lmap, w.lcx, w.lpath, w.lflag,       \
+                       w.sbits, w.ebits, w.dbg, spec, nz, wait_ticks)
+    if (hmm && nzf) JB_LONG_LAUNCH(true, true);
+    else if (hmm) JB_LONG_LAUNCH(true, false);
+    else if (nzf) JB_LONG_LAUNCH(false, true);
+    else JB_LONG_LAUNCH(false, false);
+#undef JB_LONG_LAUNCH
 }
 
-// doc_tok of the expanded list: the first span of each document's first token
-__global__ __launch_bounds__(256) void k_srch_doc(const uint64_t* __restrict__ doc_tok, uint32_t ndocs,
-                                                  const uint32_t* __restrict__ counters,
-                                                  const uint32_t* __restrict__ off, uint64_t* __restrict__ out) {
-    const uint32_t d = blockIdx.x * 256u + threadIdx.x;
-    if (d > ndocs) return;
-    const uint64_t t = doc_tok[d];
-    out[d] = t < counters[CNT_NTOK] ? (uint64_t)off[t] : *reinterpret_cast<const uint64_t*>(counters + CNT_NSRCH);
-}
-
-hipError_t run_search(const DevImage& im, const Work& w, const SearchOut& so, const uint8_t* d_text, uint64_t nbytes,
-                      uint32_t ndocs, hipStream_t stream, KernelTimer* timer) {
-    if (nbytes == 0)  // (run_pipeline left the counters and the plain doc_tok all zeros)
-        return run_zero(so.doc_tok, (ndocs + 1) * sizeof(uint64_t), stream, so.ntok, sizeof(uint64_t));
-    const uint32_t ntt = (uint32_t)srch_tiles(nbytes);
-    JB_TIMED(K_SRCH_COUNT, hipLaunchKernelGGL(k_srch_count, dim3(ntt), dim3(256), 0, stream, d_text, im,
-                                              w.erec + kErecPad, w.tok_start, w.tok_end, w.counters, so.off, so.tile,
-                                              w.tile4));
-    if (ntt > 256u)  // (k_srch_write reads the sums of whole groups of 256 tiles only)
-        JB_TIMED(K_SRCH_SCAN, hipLaunchKernelGGL(k_sup, dim3((ntt + 255u) / 256u), dim3(256), 0, stream, so.tile, ntt,
-                                                 so.sup));
-    JB_TIMED(K_SRCH_WRITE, hipLaunchKernelGGL(k_srch_write, dim3(ntt), dim3(256), 0, stream, d_text, im,
-                                              w.erec + kErecPad, w.tok_start, w.tok_end, w.counters, so.off, so.tile,
-                                              so.sup, so.start, so.end, so.ntok, w.tile4));
-    JB_TIMED(K_SRCH_DOC, hipLaunchKernelGGL(k_srch_doc, dim3((ndocs + 1u + 255u) / 256u), dim3(256), 0, stream,
-                                            w.doc_tok, ndocs, w.counters, so.off, so.doc_tok));
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Full mode (jieba's cut_all on this reference's DAG): every dictionary word of
-// two or more runes in a Han block, by start then by length, and the single runes
-// that no such word accounts for.  A pass over the plain spans of a finished run
-// with hmm = 0, in the search pass's shape: k_full_count (spans per plain token and
-// per tile of kSrchTile tokens), k_sup64, k_full_write, k_full_doc.  A Han rune's
-// spans belong to the plain token that holds the rune; they may end past that
-// token but never past the Han run.  A non-Han token is copied.
-// For the rune i at byte p with record rc = erec[p / 3]: rc != 0 gives M(i) = rc & 0xFE
-// (bit L-1 = a word of L runes); rc == 0 (overflowed, or DevImage::plainw == 0) is
-// walked through the trie by dp_walk_rune's rules up to the end of the Han run,
-// which is the token's end or, past it, the next block start of k_mark_walk's lane
-// masks (found once per token, only when a walk gets that far).  A rune with M = {}
-// is emitted alone unless the nearest earlier rune of its block that has words
-// reaches past it (cov); at the head of a token that rune is found by stepping back
-// through the records, up to maxlen - 1 runes or the block's start (full_back).
-// The output may be longer than the input, so tile sums, the total and the output
-// index are 64 bits wide; spans with an index >= cap are counted and not written,
-// and CNT_ERR bit 3 reports that.
-// ---------------------------------------------------------------------------
-struct FullCtx {
-    const uint8_t* text;
-    const uint64_t* erec;
-    const uint32_t* lanemask;
-    const uint2* tile_cnt;
-    const uint32_t* tile4;
-    uint32_t ntiles, nbytes, maxlen;
-};
-constexpr uint32_t kFullUnk = 0xFFFFFFFFu;
-__device__ __forceinline__ uint32_t full_w(const uint8_t* __restrict__ text, uint32_t p) {  // width of the Han rune at p
-    return text[p] >= 0xF0u ? 4u : 3u;
-}
-// A walk's limit: lim is a byte up to which the Han run is known to go on, real once
-// `known` is set (the first block start at or after the token's end).
-struct FullLim {
-    uint32_t lim;
-    bool known;
-};
-// The words of two or more runes that start at the Han rune at p, by a trie walk:
-// f(end byte) in ascending length.  Returns the last end, 0 when there is none.
-template <class F>
-__device__ __forceinline__ uint32_t full_walk(const FullCtx& c, const DevImage& im, uint32_t p, FullLim& fl, F&& f) {
-    const uint32_t r0 = srch_rune(c.text, p);
-    uint32_t id = rune_code(im, r0);
-    uint64_t cc = im.cells[id];
-    if (jb_cell_check(cc) != JB_CHECK_ROOT || jb_cell_fc(cc) == JB_FC_ZERO) return 0u;  // (:468-471)
-    uint32_t qq = p + (r0 >= 0x10000u ? 4u : 3u), last = 0u;
-    bool go = jb_cell_hc(cc) != 0u;
-    while (go) {
-        if (qq >= fl.lim) {
-            if (!fl.known) {
-                fl.lim = block_end_at(c.lanemask, c.tile_cnt, c.ntiles, c.nbytes, fl.lim - 1u);
-                fl.known = true;
-            }
-            if (qq >= fl.lim) break;
-        }
-        const uint32_t r = srch_rune(c.text, qq);
-        const uint32_t tt = dat_slot(im, cc, r);
-        const uint64_t ch = im.cells[tt];
-        if (!dat_hit(ch, id)) break;  // (:475-478)
-        qq += r >= 0x10000u ? 4u : 3u;
-        if (jb_cell_fc(ch) == JB_FC_POS) {
-            f(qq);
-            last = qq;
-        }
-        go = jb_cell_hc(ch) != 0u;
-        id = tt;
-        cc = ch;
-    }
-    return last;
-}
-// cov for the rune at p, the first of its token: the end of the longest word of the
-// nearest earlier rune of the block that has words, 0 when there is none in reach.
-// The fast form covers the eight runes before p when no 4-byte Han rune is near: they
-// then sit at a stride of three bytes, so their records and the lane masks that bound
-// the block are loaded at once instead of rune by rune.
-__device__ __forceinline__ uint32_t full_back(const FullCtx& c, const DevImage& im, uint32_t p, FullLim& fl) {
-    uint32_t q = p, k = 1u;
-    if (p >= 32u) {
-        const uint32_t c0 = p >> 4, base = (c0 - 2u) << 4;
-        const uint32_t l0 = c.lanemask[c0], l1 = c.lanemask[c0 - 1u], l2 = c.lanemask[c0 - 2u];
-        const uint32_t t4 = c.tile4[(p - 24u) / kTileBytes] | c.tile4[(p - 1u) / kTileBytes];
-        const uint64_t* const rp = c.erec + p / 3u;
-        uint64_t r[8];
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) r[j] = rp[-(int)(j + 1u)];
-        if (t4 == 0u) {
-            // block starts at bytes base .. p (bit b = byte base + b): the nearest one bounds the steps
-            uint64_t bm = ((uint64_t)(l0 & 0xFFFFu) << 32) | ((uint64_t)(l1 & 0xFFFFu) << 16) | (uint64_t)(l2 & 0xFFFFu);
-            bm &= (2ull << (p - base)) - 1ull;
-            uint32_t steps = bm ? (p - (base + 63u - (uint32_t)__builtin_clzll(bm))) / 3u : 8u;
-            const bool open = steps >= 8u && c.maxlen > 9u;  // neither the block's start nor maxlen - 1 in these eight
-            steps = min(min(steps, 8u), c.maxlen - 1u);
-            bool zero = false;
-#pragma unroll
-            for (uint32_t j = 0; j < 8u; j++) {
-                if (j < steps && !zero) {
-                    const uint64_t rc = r[j];
-                    if (rc == 0ull) {
-                        zero = true;  // a walk: the general form goes on from this rune
-                    } else {
-                        const uint32_t m = (uint32_t)rc & 0xFEu;
-                        if (m) return p - 3u * (j + 1u) + 3u * (32u - (uint32_t)__builtin_clz(m));
-                        q = p - 3u * (j + 1u);
-                        k = j + 2u;
-                    }
-                }
-            }
-            if (!zero && !open) return 0u;
-        }
-    }
-    for (; k < c.maxlen; k++) {
-        if (q < 3u || ((c.lanemask[q >> 4] >> (q & 15u)) & 1u)) return 0u;  // the block starts at q
-        const uint32_t wp = (c.text[q - 3u] & 0xF0u) == 0xE0u ? 3u : 4u;  // (the rune before q is a Han rune)
-        if (q < wp) return 0u;
-        q -= wp;
-        const uint64_t rc = c.erec[q / 3u];
-        uint32_t last = 0u;
-        if (rc) {
-            const uint32_t m = (uint32_t)rc & 0xFEu;
-            if (m) {
-                last = q;
-                for (uint32_t L = 32u - (uint32_t)__builtin_clz(m); L; L--) last += full_w(c.text, last);
-            }
-        } else {
-            last = full_walk(c, im, q, fl, [](uint32_t) {});
-        }
-        if (last) return last;
-    }
-    return 0u;
-}
-// The full-mode spans of the plain token [s, e), in output order: f(from, to).
-template <class F>
-__device__ __forceinline__ void full_token(const FullCtx& c, const DevImage& im, uint32_t s, uint32_t e, F&& f) {
-    // every load that depends on the span alone is issued before any is used: the first bytes, the
-    // two tile flags and the records of the first four runes at a stride of three bytes (right when
-    // all3 below holds; slots that belong to no rune of the token are read and dropped)
-    const uint32_t lastb = min(e + 23u, c.nbytes - 1u);
-    const uint64_t* const rp = c.erec + s / 3u;
-    const uint32_t x0 = ld4(c.text, s);
-    const uint32_t t4 = c.tile4[s / kTileBytes] | c.tile4[lastb / kTileBytes];
-    uint64_t r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
-    uint32_t w0 = 0;
-    const bool han = e - s >= 3u && han_rune(x0, min(e - s, 4u), &w0) != 0u;
-    if (!han) {
-        f(s, e);
-        return;
-    }
-    // no 4-byte Han rune in reach (the token and the eight runes a record's words may span): runes and
-    // records sit at fixed strides, and four records are loaded at once
-    const bool all3 = t4 == 0u;
-    FullLim fl{e, false};
-    uint32_t cov = kFullUnk;
-    for (uint32_t p = s, q = 0; p < e; q++) {
-        uint64_t rc;
-        uint32_t w = 3u;
-        if (all3) {
-            if (q && (q & 3u) == 0u) {  // (slots past the token's last rune are read and dropped)
-                r0 = rp[q];
-                r1 = rp[q + 1u];
-                r2 = rp[q + 2u];
-                r3 = rp[q + 3u];
-            }
-            const uint32_t k = q & 3u;
-            rc = k == 0u ? r0 : (k == 1u ? r1 : (k == 2u ? r2 : r3));
-        } else {
-            w = full_w(c.text, p);
-            rc = c.erec[p / 3u];
-        }
-        uint32_t last = 0u;
-        if (rc) {
-            uint32_t m = (uint32_t)rc & 0xFEu;
-            if (all3) {
-                for (; m; m &= m - 1u) {
-                    last = p + 3u * ((uint32_t)__builtin_ctz(m) + 1u);
-                    f(p, last);
-                }
-            } else {
-                uint32_t qq = p + w, L = 1u;
-                for (; m; m &= m - 1u) {
-                    for (const uint32_t t = (uint32_t)__builtin_ctz(m) + 1u; L < t; L++) qq += full_w(c.text, qq);
-                    f(p, qq);
-                    last = qq;
-                }
-            }
-        } else {
-            last = full_walk(c, im, p, fl, [&](uint32_t to) { f(p, to); });
-        }
-        if (last) {
-            cov = last;
-        } else {
-            if (cov == kFullUnk) cov = full_back(c, im, p, fl);
-            if (p >= cov) f(p, p + w);
-        }
-        p += w;
-    }
-}
-
-// the sum of v over a 256-thread workgroup, 64 bits wide: three 24-bit limbs by DPP wave scans
-__device__ uint64_t wg_sum64(uint64_t v, uint64_t* lds) {
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan((uint32_t)v & 0xFFFFFFu), 63);
-    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan((uint32_t)(v >> 24) & 0xFFFFFFu), 63);
-    const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan((uint32_t)(v >> 48)), 63);
-    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = (uint64_t)a + ((uint64_t)b << 24) + ((uint64_t)h << 48);
-    __syncthreads();
-    const uint64_t out = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return out;
-}
-// k_sup and pf_load for 64-bit tile counts
-__global__ __launch_bounds__(256) void k_sup64(const uint64_t* __restrict__ cnt, uint32_t n, uint64_t* __restrict__ sup) {
-    __shared__ uint64_t lds[4];
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const uint64_t s = wg_sum64(i < n ? cnt[i] : 0ull, lds);
-    if (threadIdx.x == 0) sup[blockIdx.x] = s;
-}
-__device__ __forceinline__ uint64_t pf_load64(const uint64_t* __restrict__ cnt, const uint64_t* __restrict__ sup,
-                                              uint32_t t) {
-    uint64_t p = 0;
-    const uint32_t sn = t >> 8, r = t & 255u;
-    for (uint32_t i = threadIdx.x; i < sn; i += 256u) p += sup[i];
-    if (threadIdx.x < r) p += cnt[(t & ~255u) + threadIdx.x];
-    return p;
-}
-
-__global__ __launch_bounds__(256) JB_SRCH_ATTR void k_full_count(FullCtx c, DevImage im,
-                                                    const uint32_t* __restrict__ ts, const uint32_t* __restrict__ te,
-                                                    const uint32_t* __restrict__ counters, uint32_t* __restrict__ off,
-                                                    uint64_t* __restrict__ tile) {
-    __shared__ uint32_t lds[8];
-    const uint32_t n = counters[CNT_NTOK], i0 = blockIdx.x * kSrchTile + threadIdx.x;
-    uint32_t sum = 0;  // (a tile's tokens are dictionary words: at most 4096 x 255 runes x 254 spans)
-    if (blockIdx.x * kSrchTile < n) {
-        uint32_t s1 = 0, e1 = 0;  // the next token's span, loaded one trip ahead
-        if (i0 < n) {
-            s1 = ts[i0];
-            e1 = te[i0];
-        }
-        for (uint32_t j = 0; j < kSrchPer; j++) {
-            const uint32_t i = i0 + j * 256u;
-            if (i >= n) break;
-            const uint32_t s = s1, e = e1;
-            if (j + 1u < kSrchPer && i + 256u < n) {
-                s1 = ts[i + 256u];
-                e1 = te[i + 256u];
-            }
-            uint32_t cnt = 0u;
-            full_token(c, im, s, e, [&](uint32_t, uint32_t) { cnt++; });
-            off[i] = cnt;
-            sum += cnt;
-        }
-    }
-    const uint2 t = pf_sum(PrefixLoads{sum, 0u}, lds);
-    if (threadIdx.x == 0) tile[blockIdx.x] = t.x;  // (0 for the tiles past the last token)
-}
-
-__global__ __launch_bounds__(256) JB_SRCH_ATTR void k_full_write(FullCtx c, DevImage im,
-                                                    const uint32_t* __restrict__ ts, const uint32_t* __restrict__ te,
-                                                    uint32_t* __restrict__ counters, uint32_t* __restrict__ off,
-                                                    const uint64_t* __restrict__ tile, const uint64_t* __restrict__ sup,
-                                                    uint64_t* __restrict__ tbase, uint32_t* __restrict__ os,
-                                                    uint32_t* __restrict__ oe, uint64_t cap, uint64_t* ontok) {
-    __shared__ uint64_t lds[4];
-    __shared__ uint32_t s_tot[kSrchPer * 4u], s_pre[kSrchPer * 4u];
-    static_assert(kSrchPer * 4u == 64u, "the (row, wave) totals are scanned by one wave");
-    const uint32_t n = counters[CNT_NTOK], t0 = blockIdx.x * kSrchTile, i0 = t0 + threadIdx.x;
-    if (t0 >= n && blockIdx.x != 0u) return;  // (the whole workgroup)
-    const uint64_t pl = pf_load64(tile, sup, blockIdx.x);
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    uint32_t cn[kSrchPer], x[kSrchPer];
-#pragma unroll
-    for (uint32_t j = 0; j < kSrchPer; j++) cn[j] = i0 + j * 256u < n ? off[i0 + j * 256u] : 0u;
-#pragma unroll
-    for (uint32_t j = 0; j < kSrchPer; j++) {
-        x[j] = wave_incl_scan(cn[j]);
-        if (lane == 63u) s_tot[j * 4u + wid] = x[j];
-    }
-    const uint64_t tb = wg_sum64(pl, lds);  // (its barriers also publish s_tot)
-    if (threadIdx.x < 64u) {
-        const uint32_t v = s_tot[threadIdx.x];
-        s_pre[threadIdx.x] = wave_incl_scan(v) - v;
-    }
-    __syncthreads();
-    // off: the token's first span, counted from the tile's (tbase)
-#pragma unroll
-    for (uint32_t j = 0; j < kSrchPer; j++)
-        if (i0 + j * 256u < n) off[i0 + j * 256u] = s_pre[j * 4u + wid] + x[j] - cn[j];
-    if (threadIdx.x == 0) {
-        tbase[blockIdx.x] = tb;
-        if (t0 + kSrchTile >= n) {  // the last tile: the count of the complete list
-            const uint64_t tot = tb + s_pre[63] + s_tot[63];
-            *reinterpret_cast<uint64_t*>(counters + CNT_NSRCH) = tot;
-            *ontok = tot;
-            if (tot > cap) atomicOr(counters + CNT_ERR, 8u);
-        }
-    }
-    uint32_t s1 = 0, e1 = 0, k1 = 0;  // the next token's span and offset, loaded one trip ahead
-    if (i0 < n) {
-        s1 = ts[i0];
-        e1 = te[i0];
-        k1 = off[i0];  // (this thread's own store)
-    }
-    for (uint32_t j = 0; j < kSrchPer; j++) {
-        const uint32_t i = i0 + j * 256u;
-        if (i >= n) break;
-        const uint32_t s = s1, e = e1;
-        uint64_t k = tb + k1;
-        if (j + 1u < kSrchPer && i + 256u < n) {
-            s1 = ts[i + 256u];
-            e1 = te[i + 256u];
-            k1 = off[i + 256u];
-        }
-        full_token(c, im, s, e, [&](uint32_t a, uint32_t b) {
-            if (k < cap) {
-                os[k] = a;
-                oe[k] = b;
-            }
-            k++;
-        });
-    }
-}
-
-// doc_tok of the full-mode list: the first span of each document's first token
-__global__ __launch_bounds__(256) void k_full_doc(const uint64_t* __restrict__ doc_tok, uint32_t ndocs,
-                                                  const uint32_t* __restrict__ counters,
-                                                  const uint32_t* __restrict__ off, const uint64_t* __restrict__ tbase,
-                                                  uint64_t* __restrict__ out) {
-    const uint32_t d = blockIdx.x * 256u + threadIdx.x;
-    if (d > ndocs) return;
-    const uint64_t t = doc_tok[d];
-    out[d] = t < counters[CNT_NTOK] ? tbase[t / kSrchTile] + off[t]
-                                    : *reinterpret_cast<const uint64_t*>(counters + CNT_NSRCH);
-}
-
-hipError_t run_full(const DevImage& im, const Work& w, const FullOut& fo, const uint8_t* d_text, uint64_t nbytes,
-                    uint32_t ndocs, hipStream_t stream, KernelTimer* timer) {
-    if (nbytes == 0)  // (run_pipeline left the counters and the plain doc_tok all zeros)
-        return run_zero(fo.doc_tok, (ndocs + 1) * sizeof(uint64_t), stream, fo.ntok, sizeof(uint64_t));
-    const uint32_t ntt = (uint32_t)srch_tiles(nbytes);
-    const FullCtx c{d_text, w.erec + kErecPad, w.lanemask, w.tile_cnt, w.tile4,
-                    (uint32_t)((nbytes + kTileBytes - 1) / kTileBytes), (uint32_t)nbytes, fo.maxlen};
-    JB_TIMED(K_FULL_COUNT, hipLaunchKernelGGL(k_full_count, dim3(ntt), dim3(256), 0, stream, c, im, w.tok_start,
-                                              w.tok_end, w.counters, fo.off, fo.tile));
-    if (ntt > 256u)  // (k_full_write reads the sums of whole groups of 256 tiles only)
-        JB_TIMED(K_FULL_SCAN, hipLaunchKernelGGL(k_sup64, dim3((ntt + 255u) / 256u), dim3(256), 0, stream, fo.tile, ntt,
-                                                 fo.sup));
-    JB_TIMED(K_FULL_WRITE, hipLaunchKernelGGL(k_full_write, dim3(ntt), dim3(256), 0, stream, c, im, w.tok_start,
-                                              w.tok_end, w.counters, fo.off, fo.tile, fo.sup, fo.tbase, fo.start, fo.end,
-                                              fo.cap, fo.ntok));
-    JB_TIMED(K_FULL_DOC, hipLaunchKernelGGL(k_full_doc, dim3((ndocs + 1u + 255u) / 256u), dim3(256), 0, stream,
-                                            w.doc_tok, ndocs, w.counters, fo.off, fo.tbase, fo.doc_tok));
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Token ids: every span of a span list looked up in the caller's vocabulary (jb_vocab.h).
-// One lane per span, tiles of kIdsTile consecutive spans (coalesced span loads and id
-// stores; neighbouring spans are neighbouring text, so a wave's text reads share lines).
-// The span count is on the device, so a fixed grid loops over the tiles.  A lane reads its
-// token's bytes into registers (8, 16 or 24 of them by its length, from aligned dwords),
-// hashes them and probes: jb_vocab_find, the host lookup's code.  No atomics, no waits.
-// ---------------------------------------------------------------------------
-// Bytes [4 w, 4 w + 4) of a key of len bytes that are inside it, as a mask over the word.
-__device__ __forceinline__ uint32_t ids_word_mask(uint32_t len, uint32_t w) {
-    if (len >= 4u * w + 4u) return 0xFFFFFFFFu;
-    return len > 4u * w ? (1u << (8u * (len - 4u * w))) - 1u : 0u;
-}
-
-// The id of the span [s, e) of the text.  The spans are not trusted: one that is empty, reversed
-// or past nbytes, or longer than the longest key, is unknown without a text read; every other
-// read lies in [s & ~3, s + 28) with s < nbytes, or inside the span.
-__device__ __forceinline__ uint32_t ids_one(const uint8_t* __restrict__ text, uint32_t nbytes, const DevVocab& v,
-                                            uint32_t s, uint32_t e) {
-    if (s >= e || e > nbytes) return JB_VOCAB_UNK;
-    uint32_t len = e - s;
-    if (len > v.maxlen) return JB_VOCAB_UNK;
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(text + (s & ~3u));
-    const uint32_t sh = s & 3u;
-    uint32_t kw[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-    const uint32_t d0 = a[0], d1 = a[1], d2 = a[2];
-    kw[0] = __builtin_amdgcn_alignbyte(d1, d0, sh);
-    kw[1] = __builtin_amdgcn_alignbyte(d2, d1, sh);
-    if (len > 8u) {
-        const uint32_t d3 = a[3], d4 = a[4];
-        kw[2] = __builtin_amdgcn_alignbyte(d3, d2, sh);
-        kw[3] = __builtin_amdgcn_alignbyte(d4, d3, sh);
-        if (len > 16u) {
-            const uint32_t d5 = a[5], d6 = a[6];
-            kw[4] = __builtin_amdgcn_alignbyte(d5, d4, sh);
-            kw[5] = __builtin_amdgcn_alignbyte(d6, d5, sh);
-        }
-    }
-    // a 1-byte span whose byte is >= 0x80 is an invalid UTF-8 byte: the token is "\xEF\xBF\xBD"
-    if (len == 1u && (kw[0] & 0x80u)) {
-        kw[0] = 0x00BDBFEFu;
-        kw[1] = 0u;
-        len = 3u;
-    } else {
-#pragma unroll
-        for (uint32_t w = 0; w < 6u; w++) kw[w] &= ids_word_mask(len, w);
-    }
-    return jb_vocab_find(v, kw, text + s, len);
-}
-
-__global__ __launch_bounds__(256) JB_SRCH_ATTR void k_ids(const uint8_t* __restrict__ text, uint32_t nbytes, DevVocab v,
-                                                          const uint32_t* __restrict__ ts,
-                                                          const uint32_t* __restrict__ te,
-                                                          const uint64_t* __restrict__ ntok, uint64_t cap,
-                                                          uint32_t* __restrict__ ids) {
-    const uint64_t n = std::min(*ntok, cap), step = (uint64_t)gridDim.x * kIdsTile;
-    uint64_t i = (uint64_t)blockIdx.x * kIdsTile + threadIdx.x;
-    uint32_t s1 = 0, e1 = 0;  // the next span, loaded one trip ahead
-    if (i < n) {
-        s1 = ts[i];
-        e1 = te[i];
-    }
-    for (; i < n; i += step) {
-        const uint32_t s = s1, e = e1;
-        if (i + step < n) {
-            s1 = ts[i + step];
-            e1 = te[i + step];
-        }
-        ids[i] = ids_one(text, nbytes, v, s, e);
-    }
-}
-
-hipError_t run_ids(const DevVocab& v, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
-                   const uint32_t* d_end, const uint64_t* d_ntok, uint64_t cap, uint32_t* d_ids, uint32_t ncu,
-                   hipStream_t stream, KernelTimer* timer) {
-    if (cap == 0) return hipSuccess;  // (nothing to write)
-    const uint64_t tiles = (cap + kIdsTile - 1u) / kIdsTile;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)std::max(1u, ncu) * kIdsWgPerCu);
-    JB_TIMED(K_IDS, hipLaunchKernelGGL(k_ids, dim3(grid), dim3(256), 0, stream, d_text, (uint32_t)nbytes, v, d_start,
-                                       d_end, d_ntok, cap, d_ids));
-    return hipGetLastError();
+void enq_nonzh(const Work& w, const uint8_t* d_text, uint64_t nbytes, uint32_t ntiles, const uint64_t* d_doc_off,
+               uint32_t ndocs, hipStream_t stream) {
+    const uint32_t nw = (uint32_t)((nbytes + 1023u) / 1024u);  // alnum16 words
+    hipLaunchKernelGGL(k_nonzh, dim3((nw + 255u) / 256u), dim3(256), 0, stream, d_text, (uint32_t)nbytes, w.lanemask,
+                       w.tile_cnt, ntiles, w.alnum16, w.sbits, w.ebits, w.docbits, d_doc_off, ndocs);
 }
 
 }  // namespace jb

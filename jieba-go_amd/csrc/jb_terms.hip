@@ -34,7 +34,7 @@
 // Nothing here synchronises, allocates or reads on the host; the launch counts depend on host values.
 #include <hip/hip_runtime.h>
 
-#include "jb_kernels.h"
+#include "jb_kstages.h"
 
 #include <algorithm>
 
@@ -787,13 +787,6 @@ TermsWork terms_layout(uint64_t max_tokens, void* p) {
 }
 
 }  // namespace
-
-#define JB_TIMED(id, ...)                       \
-    do {                                        \
-        if (timer) timer->begin((id), stream);  \
-        __VA_ARGS__;                            \
-        if (timer) timer->end((id), stream);    \
-    } while (0)
 
 size_t terms_work_bytes(uint64_t max_tokens, uint32_t /*ndocs*/) { return terms_layout(max_tokens, nullptr).bytes; }
 

@@ -1,6 +1,6 @@
 // jb_vocab.h — a caller's vocabulary as a flat hash table: layout, hash and probe
 // shared by the host builder / lookup (jb_vocab.cpp) and the gfx950 kernel k_ids
-// (jb_kernels.hip), which run the same code below.
+// (jb_k_modes.hip), which run the same code below.
 //
 // The vocabulary is a list of byte strings (1..255 bytes, any content); a key's id is
 // its index in the list.  It is not the trie: the trie holds only the all-Han keys
