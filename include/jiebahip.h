@@ -457,6 +457,96 @@ int jb_idf(const uint32_t *df, uint32_t ndf, uint64_t ndocs_total, uint32_t min_
 int jb_df_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm, uint32_t *df,
                 uint32_t ndf);
 
+/* ---- TextRank keywords (jieba.analyse.textrank; the reference has only Cut) ------------------
+ * A document's words ranked by PageRank over their co-occurrence graph, on the device: the second
+ * entry point of jieba.analyse, which needs no corpus statistics (no fitted weight table).  Its
+ * inputs are those of jb_terms_device and the CSR that call wrote; no token reaches the host.
+ *
+ * The rule.  jb_textrank (host only, no ctx, no GPU) and jb_textrank_device agree to the bit.
+ *  - Id list: token k exists iff k < min(ntok, ids_cap) (the device reads *d_ntok on the device);
+ *    document d's tokens are [doc_tok[d], doc_tok[d+1]) clamped to that bound; doc_tok is
+ *    non-decreasing.
+ *  - CSR of that list, as jb_terms_device wrote it: term_id, term_off (u64[ndocs + 1],
+ *    non-decreasing) and the cap it was written with.  Both calls take the rows, they do not derive
+ *    them; term_off[ndocs] is the term count, so *d_nterms is not an argument.
+ *  - Kept tokens: token k is kept iff id != JB_ID_UNK, id < nkeep, keep[id] != 0 (keep: u8[nkeep])
+ *    and the id is found in its document's CSR row, by binary search (rows are ascending).  A
+ *    caller's own CSR that lacks the id makes the token not kept; nothing is indexed outside a row.
+ *    Tokens that are not kept still occupy their position in the window, which is how jieba counts
+ *    words that fail its pairfilter.
+ *  - Events: a pair of kept tokens k < j of one document with j - k < span.  Each adds 1 to
+ *    W[x_k][x_j] and 1 to W[x_j][x_k]; with x_k == x_j that is 2 in one cell (jieba's addEdge
+ *    appends the self edge twice).  out[a] = sum_b W[a][b], kept in 64 bits.  A term is a node iff
+ *    out > 0; n is the document's node count.
+ *  - Scale: S = 62 - bit_length(n), so n * 2^S <= 2^62; sum ws <= n holds by induction from
+ *    ws = 1/n, so no u64 sum below overflows.
+ *  - Iteration: Jacobi, in f64, no fused multiply-add.  ws[a] = 1.0 / (double)n; then iters times,
+ *    every ws of a round taken from the round before:
+ *      r[a]   = (u64) trunc((ws[a] / (double)out[a]) * 2^S)
+ *      acc[a] = sum_b W[a][b] * r[b]                              (u64 integer sum)
+ *      ws[a]  = (1.0 - 0.85) + 0.85 * ((double)acc[a] * 2^-S)     ((double)acc: to nearest even)
+ *    The sum is in integers on purpose: it does not depend on the order of its adds, so the device
+ *    uses atomics and is still identical from run to run and identical to jb_textrank.
+ *  - Score: mn and mx are the smallest and largest ws over the document's nodes;
+ *    score = (float)((ws - mn / 10.0) / (mx - mn / 10.0)), jieba's normalisation.
+ *  - Output: row d of kw_id / kw_score (ndocs x topk) holds the kw_n[d] = min(topk, n) best nodes
+ *    by the f32 score descending, ties by id ascending; the remaining slots are JB_ID_UNK and 0.0f.
+ *    Every slot of every row is written.  A document whose CSR row passes cap gets kw_n = 0, as in
+ *    jb_keywords_device.
+ *  - Limits: 2 <= span <= JB_TR_MAXSPAN (jieba: 5), 0 <= iters <= JB_TR_MAXITER (jieba: 10; with 0
+ *    the ranks are the start values), 1 <= topk <= JB_KW_MAXK: JB_EINVAL below, JB_ELIMIT above, as
+ *    the keyword calls.  JB_ELIMIT for ids_cap or cap >= 2^32 - JB_TERMS_TILE; JB_EINVAL for a null
+ *    pointer (keep may be NULL when nkeep == 0).
+ *
+ * jb_textrank_device.  d_work is a caller-owned device buffer of nwork >=
+ * jb_textrank_work_bytes(ids_cap, cap, ndocs) bytes, 8-byte aligned (JB_EINVAL otherwise, with
+ * nothing queued): 6 bytes per token (its node and the reach of its window inside its document),
+ * 28 per term (its document, out, r, acc) and 4 per document (n).  Its contents mean nothing
+ * before or after the call; concurrent calls need buffers of their own.  The contract is
+ * jb_terms_device's: the call queues its kernels on `stream` and returns; it does not synchronise,
+ * allocate, read anything on the host or use the per-device workspace, and it holds the ctx's
+ * shared lock only while queuing.  The number of launches is 4 + 2 * iters (2 when ids_cap or cap
+ * is 0), never a matter of device data.  Nothing is written outside the outputs and d_work.
+ * The push kernel has two forms with identical results (JB_TR_WINDOW, read at jb_open): 1 gathers
+ * each token's r once into an LDS tile with a halo of span - 1 and combines a workgroup's adds to
+ * one term before the global atomic (the default: 31.7 ms against 64.7 ms for the 139.5M tokens of
+ * the 1 GiB corpus with jieba's arguments, beside 6.28 ms for the plain cut step and 4.86 ms for
+ * jb_terms_device; profiles/textrank_bench.json); 0 gathers from memory and does one global atomic
+ * per token.
+ *
+ * jb_textrank_batch: host text in, ndocs x topk records and kw_n out.  It runs plain Cut -> ids ->
+ * terms -> textrank on ctx's first device through the buffers jb_keywords_batch keeps in the ctx
+ * (the work buffer is one more that only grows; concurrent calls take turns).  Requirements and
+ * errors are jb_keywords_batch's: an attached vocabulary (JB_EINVAL), a batch under 2 GiB
+ * (JB_ELIMIT), doc_off non-decreasing, and the cut's errors pass through.
+ *
+ * Deliberate differences from jieba.analyse.textrank:
+ *  - Jacobi rounds instead of jieba's in-place update in sorted-word order: the ranks are close
+ *    (the top 20 were the same 20 words on seeded Zipf documents of 50, 2,000 and 20,000 tokens),
+ *    the order is not promised to match;
+ *  - the part-of-speech, length and stop-word filters are the caller's keep mask;
+ *  - unknown ids are never nodes;
+ *  - ties are broken by id;
+ *  - fixed-point accumulation with resolution 2^-S: ws differs from plain f64 Jacobi by less than
+ *    max(out) * 2^-S / (1 - 0.85). */
+#define JB_TR_MAXSPAN 32
+#define JB_TR_MAXITER 100
+/* Host only, no ctx: non-decreasing in every argument, never 0. */
+size_t jb_textrank_work_bytes(uint64_t max_tokens, uint64_t max_terms, uint32_t ndocs);
+/* host only, no ctx, no GPU: the rule, and the reference the device kernels are pinned to */
+int jb_textrank(const uint32_t *ids, uint64_t ids_cap, const uint64_t *doc_tok, uint64_t ntok, uint32_t ndocs,
+                const uint32_t *term_id, const uint64_t *term_off, uint64_t cap, const uint8_t *keep, uint32_t nkeep,
+                uint32_t span, uint32_t iters, uint32_t topk, uint32_t *kw_id, float *kw_score, uint32_t *kw_n);
+int jb_textrank_device(jb_ctx *ctx, const uint32_t *d_ids, uint64_t ids_cap, const uint64_t *d_doc_tok,
+                       const uint64_t *d_ntok, uint32_t ndocs, const uint32_t *d_term_id, const uint64_t *d_term_off,
+                       uint64_t cap, const uint8_t *d_keep, uint32_t nkeep, uint32_t span, uint32_t iters,
+                       uint32_t topk, void *stream, uint32_t *d_kw_id, float *d_kw_score, uint32_t *d_kw_n,
+                       void *d_work, size_t nwork);
+/* kw_id / kw_score: ndocs x topk host entries each; kw_n: ndocs. */
+int jb_textrank_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm,
+                      const uint8_t *keep, uint32_t nkeep, uint32_t span, uint32_t iters, uint32_t topk,
+                      uint32_t *kw_id, float *kw_score, uint32_t *kw_n);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "jb_host.h"
+#include "jb_textrank.h"
 
 // ---------------------------------------------------------------------------
 // image
@@ -225,7 +226,7 @@ extern "C" void jb_close(jb_ctx* ctx) {
         dfree(ctx->d_vslots);
         dfree(ctx->d_vpool);
     }
-    if ((ctx->kw_buf[0] || ctx->kw_buf[1] || ctx->kw_buf[2]) && !ctx->devs.empty()) {
+    if ((ctx->kw_buf[0] || ctx->kw_buf[1] || ctx->kw_buf[2] || ctx->kw_buf[3]) && !ctx->devs.empty()) {
         (void)hipSetDevice(ctx->devs[0]->ordinal);
         for (void* p : ctx->kw_buf) dfree(p);
     }
@@ -1060,6 +1061,47 @@ extern "C" int jb_idf_device(jb_ctx* ctx, const uint32_t* d_df, uint32_t ndf, ui
 }
 
 // ---------------------------------------------------------------------------
+// TextRank keywords (jb_textrank.hip; the host rule, jb_textrank, is jb_textrank.cpp)
+// ---------------------------------------------------------------------------
+static_assert(JB_TR_MAXSPAN == kTrMaxSpan && JB_TR_MAXITER == kTrMaxIter, "the header's constants are the kernels'");
+
+extern "C" size_t jb_textrank_work_bytes(uint64_t max_tokens, uint64_t max_terms, uint32_t ndocs) {
+    return textrank_work_bytes(max_tokens, max_terms, ndocs);
+}
+
+extern "C" int jb_textrank_device(jb_ctx* ctx, const uint32_t* d_ids, uint64_t ids_cap, const uint64_t* d_doc_tok,
+                                  const uint64_t* d_ntok, uint32_t ndocs, const uint32_t* d_term_id,
+                                  const uint64_t* d_term_off, uint64_t cap, const uint8_t* d_keep, uint32_t nkeep,
+                                  uint32_t span, uint32_t iters, uint32_t topk, void* stream, uint32_t* d_kw_id,
+                                  float* d_kw_score, uint32_t* d_kw_n, void* d_work, size_t nwork) {
+    // (the limits come first: they need no ctx)
+    if (const int rc = textrank_args("jb_textrank_device", ids_cap, cap, span, iters, topk)) return rc;
+    if (!ctx || !d_doc_tok || !d_ntok || !d_term_off || !d_work || (ids_cap && !d_ids) || (cap && !d_term_id) ||
+        (nkeep && !d_keep) || (ndocs && (!d_kw_id || !d_kw_score || !d_kw_n)))
+        return fail(JB_EINVAL, "jb_textrank_device: null argument");
+    if (((uintptr_t)d_work & 7u) != 0) return fail(JB_EINVAL, "jb_textrank_device: d_work must be 8-byte aligned");
+    const size_t need = textrank_work_bytes(ids_cap, cap, ndocs);
+    if (nwork < need)
+        return fail(JB_EINVAL, "jb_textrank_device: a work buffer of %llu bytes, jb_textrank_work_bytes asks for %llu",
+                    (unsigned long long)nwork, (unsigned long long)need);
+    if (ndocs == 0) return JB_OK;
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    const bool window = d->lc.tr_window != 0;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_textrank(d_ids, ids_cap, d_doc_tok, d_ntok, ndocs, d_term_id, d_term_off, cap, d_keep, nkeep, span,
+                            iters, topk, window, d_kw_id, d_kw_score, d_kw_n, d_work, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_textrank(d_ids, ids_cap, d_doc_tok, d_ntok, ndocs, d_term_id, d_term_off, cap, d_keep, nkeep, span, iters,
+                        topk, window, d_kw_id, d_kw_score, d_kw_n, d_work, s, nullptr));
+    return JB_OK;
+}
+
+// ---------------------------------------------------------------------------
 // host text in: jb_keywords_batch, jb_df_batch
 // ---------------------------------------------------------------------------
 namespace {
@@ -1097,6 +1139,9 @@ struct BatchCsr {
     const uint64_t* term_off;            // ndocs + 1
     const uint64_t* nterms;
     uint64_t tcap;
+    const uint32_t* ids;      // tcap entries, in token order
+    const uint64_t* doc_tok;  // ndocs + 1
+    const uint64_t* ntok;
 };
 
 // The front of the host-text calls: plain Cut -> ids -> terms of one batch on a stream of the first
@@ -1161,7 +1206,7 @@ int batch_chain(jb_ctx* ctx, const char* who, const uint8_t* text, const uint64_
         if ((rc = jb_terms_device(ctx, did, tcap, dtok, dcnt, ndocs, st, dterm, dterm + tcap, tcap, dtoff, dcnt + 1,
                                   dwork, nwork)))
             return rc;
-        if ((rc = last(BatchCsr{st, dterm, dterm + tcap, dtoff, dcnt + 1, tcap}, &a))) return rc;
+        if ((rc = last(BatchCsr{st, dterm, dterm + tcap, dtoff, dcnt + 1, tcap, did, dtok, dcnt}, &a))) return rc;
         HIPCHK(hipStreamSynchronize(st));
         return JB_OK;
     };
@@ -1231,3 +1276,31 @@ extern "C" int jb_df_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc
     return rc;
 }
 
+// Host text in, TextRank keywords out: batch_chain, then jb_textrank_device with the keep mask, the
+// records and the work buffer in the ctx's fourth buffer, and the records' way back.
+extern "C" int jb_textrank_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                                 const uint8_t* keep, uint32_t nkeep, uint32_t span, uint32_t iters, uint32_t topk,
+                                 uint32_t* kw_id, float* kw_score, uint32_t* kw_n) {
+    if (const int rc = textrank_args("jb_textrank_batch", 0, 0, span, iters, topk)) return rc;
+    if (!ctx || !doc_off || (nkeep && !keep) || (ndocs && (!kw_id || !kw_score || !kw_n)))
+        return fail(JB_EINVAL, "jb_textrank_batch: null argument");
+    const size_t nrec = (size_t)ndocs * topk;
+    return batch_chain(ctx, "jb_textrank_batch", text, doc_off, ndocs, hmm, 0, [&](const BatchCsr& c, Arena*) -> int {
+        const size_t nwork = textrank_work_bytes(c.tcap, c.tcap, ndocs);
+        Arena b;
+        if (const int r = kw_arena(ctx, 3, r256(std::max<size_t>(nkeep, 1)) + r256((2 * nrec + ndocs) * 4) + r256(nwork), &b))
+            return r;
+        uint8_t* dkeep = (uint8_t*)b.take(std::max<size_t>(nkeep, 1));
+        uint32_t* dkw = (uint32_t*)b.take((2 * nrec + ndocs) * 4);  // (ids, scores, kw_n)
+        void* dwork = b.take(nwork);
+        if (nkeep) HIPCHK(hipMemcpyAsync(dkeep, keep, nkeep, hipMemcpyHostToDevice, c.st));
+        if (const int r = jb_textrank_device(ctx, c.ids, c.tcap, c.doc_tok, c.ntok, ndocs, c.term_id, c.term_off, c.tcap,
+                                             dkeep, nkeep, span, iters, topk, c.st, dkw, (float*)(dkw + nrec),
+                                             dkw + 2 * nrec, dwork, nwork))
+            return r;
+        HIPCHK(hipMemcpyAsync(kw_id, dkw, nrec * 4, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipMemcpyAsync(kw_score, dkw + nrec, nrec * 4, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipMemcpyAsync(kw_n, dkw + 2 * nrec, (size_t)ndocs * 4, hipMemcpyDeviceToHost, c.st));
+        return JB_OK;
+    });
+}

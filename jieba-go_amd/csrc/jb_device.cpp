@@ -242,6 +242,7 @@ static const uint64_t kMaxPiece = 1ull << 30;  // (a piece of several documents;
 //   JB_SMALL     host batches up to this many bytes take k_small (0: never)
 //   JB_STAMPS    (STAMPS=1 builds only) per-wave phase clocks to stderr
 //   JB_DF_COMBINE jb_df_device's kernel: 1 k_df_combine (default), 0 k_df
+//   JB_TR_WINDOW jb_textrank_device's push kernel: 1 k_tr_push_win (default), 0 k_tr_push
 static int init_launch_cfg(Device* d) {
     LaunchCfg& lc = d->lc;
     lc.zh_waves = d->ncu * std::max(zh_waves_per_cu(true, false), zh_waves_per_cu(false, false));
@@ -303,6 +304,9 @@ static int init_launch_cfg(Device* d) {
     const int dc = env_int("JB_DF_COMBINE", 1);
     if (dc < 0 || dc > 1) return fail(JB_EINVAL, "JB_DF_COMBINE=%d: want 0 or 1", dc);
     lc.df_combine = (uint32_t)dc;
+    const int tw = env_int("JB_TR_WINDOW", 1);
+    if (tw < 0 || tw > 1) return fail(JB_EINVAL, "JB_TR_WINDOW=%d: want 0 or 1", tw);
+    lc.tr_window = (uint32_t)tw;
     return JB_OK;
 }
 

@@ -125,6 +125,7 @@ enum KernelId {
     K_FULL_COUNT, K_FULL_SCAN, K_FULL_WRITE, K_FULL_DOC, K_IDS,
     K_TERMS_SORT, K_TERMS_MERGE, K_TERMS_COUNT, K_TERMS_SCAN, K_TERMS_WRITE, K_KEYWORDS,
     K_DF, K_IDF,
+    K_TR_INIT, K_TR_SETUP, K_TR_COUNT, K_TR_STEP, K_TR_PUSH, K_TR_FINAL,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -160,6 +161,8 @@ struct LaunchCfg {
     int32_t mw_split;        // k_mark_walk: 2^s workgroups per tile, each walking its share of the entries
                              // (JB_MW_SPLIT: -1 = 1 when the batch has at most one tile per CU, else 0; 0-3 fixed)
     uint32_t df_combine;     // jb_df_device: 1 k_df_combine, 0 k_df (JB_DF_COMBINE; results do not depend on it)
+    uint32_t tr_window;      // jb_textrank_device's push: 1 k_tr_push_win, 0 k_tr_push (JB_TR_WINDOW; results do not
+                             // depend on it)
 };
 
 // k_zh's group split: g1 groups of grp bytes, then groups of *sgrp bytes to the end.
@@ -273,6 +276,23 @@ hipError_t run_df(const uint32_t* d_term_id, const uint64_t* d_nterms, uint64_t 
 // Enqueue k_idf on `stream`: d_weight[id] for every id < ndf (ndf > 0) by jb_idf's rule, bit for bit.
 hipError_t run_idf(const uint32_t* d_df, uint32_t ndf, uint64_t ndocs_total, uint32_t min_df, uint32_t max_df,
                    const uint8_t* d_keep, float* d_weight, hipStream_t stream, KernelTimer* timer);
+
+// TextRank keywords (jb_textrank_device; jb_textrank.hip).  Chunk = kTrChunk consecutive tokens, one
+// workgroup each in the setup and in the windowed push, with a halo of span - 1 tokens on each side.
+constexpr uint32_t kTrChunk = 1024;
+constexpr uint32_t kTrMaxSpan = 32;   // JB_TR_MAXSPAN: the halo fits one byte of reach per side
+constexpr uint32_t kTrMaxIter = 100;  // JB_TR_MAXITER
+// Bytes of the work buffer run_textrank needs: 6 per token, 28 per term, 4 per document.  Host only.
+size_t textrank_work_bytes(uint64_t max_tokens, uint64_t max_terms, uint32_t ndocs);
+// Enqueue the TextRank kernels on `stream` (ndocs > 0, 2 <= span <= kTrMaxSpan, iters <= kTrMaxIter,
+// 1 <= topk <= kKwMaxK): 4 launches and 2 per iteration (only 2 when ids_cap or cap is 0).  `window`
+// chooses the push kernel.  d_work holds textrank_work_bytes(ids_cap, cap, ndocs) bytes, 8-byte aligned.
+// (K_TR_PUSH times whichever push kernel runs.)
+hipError_t run_textrank(const uint32_t* d_ids, uint64_t ids_cap, const uint64_t* d_doc_tok, const uint64_t* d_ntok,
+                        uint32_t ndocs, const uint32_t* d_term_id, const uint64_t* d_term_off, uint64_t cap,
+                        const uint8_t* d_keep, uint32_t nkeep, uint32_t span, uint32_t iters, uint32_t topk,
+                        bool window, uint32_t* d_kw_id, float* d_kw_score, uint32_t* d_kw_n, void* d_work,
+                        hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

@@ -410,6 +410,77 @@ func (t *Tokenizer) ExtractTags(docs []string, weights []float32, topK int, useH
 	return out
 }
 
+// Rank is one keyword of TextRank: the word's id in the attached vocabulary and its score, which is
+// 1 for a document's best word (jieba's normalisation).
+type Rank struct {
+	Id    uint32
+	Score float32
+}
+
+// TextRank is jieba.analyse.textrank over a batch of documents: per document the topK words of the
+// attached vocabulary (SetVocab) by PageRank over the co-occurrence graph of the kept tokens that
+// lie within span positions of each other, after iters Jacobi rounds, best first, ties by id.
+// jieba's values are span 5 and 10 rounds.  keep holds one byte per id and carries jieba's
+// part-of-speech, length and stop-word filters; ids past it are not kept.  No weight table is
+// needed.  Cutting (plain Cut), lookup, counting and ranking all run on the GPU; only the records
+// come back.  The rule and its differences from jieba's (Jacobi rounds, closed vocabulary, ties by
+// id, fixed-point sums) are in jiebahip.h.  With mini_dict.txt, the vocabulary abc, 今天, "�",
+// 一刹那, 刹那, 这, 天天 and keep 1 1 1 1 1 0 1, TextRank([]string{"abc abc 今天"}, keep, 3, 5,
+// 10, false) has the two nodes abc and 今天, abc first with score 1 (tests/c_abi_textrank.c).
+// Never returns nil.
+func (t *Tokenizer) TextRank(docs []string, keep []byte, topK, span, iters int, useHmm bool) [][]Rank {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	out := make([][]Rank, len(docs))
+	if len(docs) == 0 {
+		return out
+	}
+	if topK < 1 || topK > C.JB_KW_MAXK {
+		panic("jiebahip: TextRank topK out of range")
+	}
+	if span < 2 || span > C.JB_TR_MAXSPAN || iters < 0 || iters > C.JB_TR_MAXITER {
+		panic("jiebahip: TextRank span or iters out of range")
+	}
+	off := make([]uint64, len(docs)+1)
+	total := 0
+	for i, d := range docs {
+		total += len(d)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, d := range docs {
+		b = append(b, d...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	nrec := len(docs) * topK
+	id := make([]uint32, nrec)
+	score := make([]float32, nrec)
+	n := make([]uint32, len(docs))
+	var kp *C.uint8_t
+	if len(keep) > 0 {
+		kp = (*C.uint8_t)(unsafe.Pointer(&keep[0]))
+	}
+	rc := C.jb_textrank_batch(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+		C.uint32_t(len(docs)), hmm, kp, C.uint32_t(len(keep)), C.uint32_t(span), C.uint32_t(iters), C.uint32_t(topK),
+		(*C.uint32_t)(unsafe.Pointer(&id[0])), (*C.float)(unsafe.Pointer(&score[0])),
+		(*C.uint32_t)(unsafe.Pointer(&n[0])))
+	if rc != C.JB_OK {
+		// JB_EINVAL: no vocabulary attached; JB_EPANIC: the reference panics on this input
+		panic("jiebahip: " + lastError())
+	}
+	for d := range docs {
+		out[d] = make([]Rank, int(n[d]))
+		for r := range out[d] {
+			out[d][r] = Rank{id[d*topK+r], score[d*topK+r]}
+		}
+	}
+	return out
+}
+
 // IdfFit is the result of FitIdf: per id of the attached vocabulary its IDF weight and the number
 // of documents it occurs in, and the number of documents fitted on.
 type IdfFit struct {

@@ -159,6 +159,26 @@ Tokenizer::IdfFit Tokenizer::FitIdf(const std::vector<std::vector<std::string>>&
     return fit;
 }
 
+std::vector<std::vector<Tokenizer::Rank>> Tokenizer::TextRank(const std::vector<std::string>& docs,
+                                                              const std::vector<uint8_t>& keep, uint32_t topK,
+                                                              uint32_t span, uint32_t iters, bool useHmm) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& d : docs) {
+        all += d;
+        off.push_back(all.size());
+    }
+    const size_t nd = docs.size(), nrec = nd * (size_t)topK;
+    std::vector<uint32_t> id(nrec + 1), n(nd + 1);
+    std::vector<float> score(nrec + 1);
+    check(jb_textrank_batch(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)nd, useHmm ? 1 : 0, keep.data(),
+                            (uint32_t)keep.size(), span, iters, topK, id.data(), score.data(), n.data()));
+    std::vector<std::vector<Rank>> out(nd);
+    for (size_t d = 0; d < nd; d++)
+        for (uint32_t r = 0; r < n[d]; r++) out[d].push_back(Rank{id[d * topK + r], score[d * topK + r]});
+    return out;
+}
+
 std::vector<std::string> Tokenizer::CutParallel(const std::string& text, bool hmm, int, bool) {
     return Cut(text, hmm);
 }

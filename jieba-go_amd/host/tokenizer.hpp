@@ -85,6 +85,19 @@ public:
     };
     IdfFit FitIdf(const std::vector<std::vector<std::string>>& batches, bool useHmm = true, uint32_t minDf = 1,
                   uint32_t maxDf = JB_DF_NOMAX, const std::vector<uint8_t>& keep = {});
+    // TextRank keywords (jieba.analyse.textrank; jb_textrank_batch in jiebahip.h, with the rule and its
+    // differences from jieba's): per document the topK words of the attached vocabulary by PageRank over
+    // the co-occurrence graph of the kept tokens within `span` positions, `iters` Jacobi rounds, best
+    // first, ties by id.  keep holds one byte per id (jieba's part-of-speech, length and stop-word
+    // filters; ids past it are not kept).  Needs no weight table.  Ranked on the GPU: no span reaches
+    // the host.
+    struct Rank {
+        uint32_t id;
+        float score;
+    };
+    std::vector<std::vector<Rank>> TextRank(const std::vector<std::string>& docs, const std::vector<uint8_t>& keep,
+                                            uint32_t topK = 20, uint32_t span = 5, uint32_t iters = 10,
+                                            bool useHmm = true);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

@@ -26,6 +26,8 @@ JB_ID_UNK = 0xFFFFFFFF  # the id of a token that is not in the vocabulary
 JB_KW_MAXK = 64  # the largest topk of the keyword calls
 JB_TERMS_TILE = 4096  # tokens per sort tile of jb_terms_device
 JB_DF_NOMAX = 0xFFFFFFFF  # max_df of the idf calls: no upper bound
+JB_TR_MAXSPAN = 32  # the largest span of the textrank calls
+JB_TR_MAXITER = 100  # the largest iters of the textrank calls
 
 # Every symbol include/jiebahip.h declares.
 EXPORTS = [
@@ -42,6 +44,7 @@ EXPORTS = [
     "jb_ids_device", "jb_spans_ids",
     "jb_terms_work_bytes", "jb_terms_device", "jb_keywords_device", "jb_keywords_batch",
     "jb_df_device", "jb_idf_device", "jb_idf", "jb_df_batch",
+    "jb_textrank_work_bytes", "jb_textrank", "jb_textrank_device", "jb_textrank_batch",
 ]
 
 
@@ -171,6 +174,14 @@ def lib():
         L.jb_idf_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.jb_idf.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]
         L.jb_df_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint32]
+        L.jb_textrank_work_bytes.restype = C.c_size_t
+        L.jb_textrank_work_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+        L.jb_textrank.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32,
+                                  C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.jb_textrank_device.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint32,
+                                         C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t]
+        L.jb_textrank_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.c_uint32, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -708,6 +719,45 @@ class Tokenizer:
             ndocs += len(docs)
         return idf(df, ndocs, min_df, max_df, keep), df, ndocs
 
+    # -- TextRank keywords ----------------------------------------------------
+    def textrank_device(self, d_ids, ids_cap, d_doc_tok, d_ntok, ndocs, d_term_id, d_term_off, cap, d_keep, nkeep,
+                        d_kw_id, d_kw_score, d_kw_n, d_work, nwork, span=5, iters=10, topk=20, stream_ptr=0):
+        """jb_textrank_device over raw device pointers: per document the topk nodes of its co-occurrence graph
+        by PageRank.  d_work: textrank_work_bytes(ids_cap, cap, ndocs) bytes."""
+        _check(lib().jb_textrank_device(self.h, C.c_void_p(d_ids), ids_cap, C.c_void_p(d_doc_tok), C.c_void_p(d_ntok),
+                                        ndocs, C.c_void_p(d_term_id), C.c_void_p(d_term_off), cap, C.c_void_p(d_keep),
+                                        nkeep, span, iters, topk, C.c_void_p(stream_ptr), C.c_void_p(d_kw_id),
+                                        C.c_void_p(d_kw_score), C.c_void_p(d_kw_n), C.c_void_p(d_work), nwork))
+
+    def textrank_batch(self, buf, doc_off, hmm, keep, span=5, iters=10, topk=20):
+        """jb_textrank_batch: host batch -> (kw_id u32[ndocs, topk], kw_score f32, kw_n u32[ndocs])."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        k = np.ascontiguousarray(keep, dtype=np.uint8)
+        nd = len(doc_off) - 1
+        rows = max(nd, 1) * max(int(topk), 1)
+        ki, ks, kn = np.empty(rows, np.uint32), np.empty(rows, np.float32), np.empty(max(nd, 1), np.uint32)
+        _check(lib().jb_textrank_batch(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, int(hmm),
+                                       k.ctypes.data if len(k) else None, len(k), span, iters, topk, ki.ctypes.data,
+                                       ks.ctypes.data, kn.ctypes.data))
+        shape = (nd, int(topk))
+        return ki[:nd * topk].reshape(shape), ks[:nd * topk].reshape(shape), kn[:nd]
+
+    def textrank(self, texts, keep, topK=20, span=5, iters=10, hmm=True, keys=None):
+        """jieba.analyse.textrank over a list of documents (str / bytes), with the attached vocabulary and
+        the caller's keep mask (one byte per id: jieba's part-of-speech, length and stop-word filters): per
+        document a list of (key, score), best first.  `key` is the term's id, or keys[id] when the
+        vocabulary's key list is passed.  The differences from jieba's (Jacobi rounds, closed vocabulary,
+        ties by id, fixed-point sums) are in jiebahip.h."""
+        docs = [_b(t) for t in texts]
+        off = np.zeros(len(docs) + 1, np.uint64)
+        if docs:
+            off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+        buf = np.frombuffer(b"".join(docs) + b"\0", np.uint8)
+        ki, ks, kn = self.textrank_batch(buf, off, hmm, keep, span, iters, topK)
+        return [[(int(ki[d, r]) if keys is None else keys[int(ki[d, r])], float(ks[d, r])) for r in range(int(kn[d]))]
+                for d in range(len(docs))]
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -757,7 +807,7 @@ class Tokenizer:
         _check(lib().jb_profile_reset(self.h))
 
     def profile_read(self):
-        cap = 64  # (more than the library's kernels: 34)
+        cap = 64  # (more than the library's kernels: 40)
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         n = (C.c_uint64 * cap)()
@@ -863,3 +913,34 @@ def idf(df, ndocs, min_df=1, max_df=None, keep=None):
                         JB_DF_NOMAX if max_df is None else max_df, k.ctypes.data if k is not None and len(k) else None,
                         w.ctypes.data if len(w) else None))
     return w
+
+
+def textrank_work_bytes(max_tokens, max_terms, ndocs):
+    """jb_textrank_work_bytes: bytes of the work buffer jb_textrank_device needs (host only)."""
+    return lib().jb_textrank_work_bytes(max_tokens, max_terms, ndocs)
+
+
+def textrank(ids, doc_tok, term_id, term_off, keep, span=5, iters=10, topk=20, ntok=None, ids_cap=None, cap=None):
+    """jb_textrank (host only): the TextRank rule of jiebahip.h on host arrays, with the CSR rows of
+    jb_terms_device (term_id, term_off) taken from the caller -> (kw_id u32[ndocs, topk], kw_score f32,
+    kw_n u32[ndocs]).  ntok, ids_cap and cap default to the arrays' lengths."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    doc_tok = np.ascontiguousarray(doc_tok, dtype=np.uint64)
+    term_id = np.ascontiguousarray(term_id, dtype=np.uint32)
+    term_off = np.ascontiguousarray(term_off, dtype=np.uint64)
+    k = np.ascontiguousarray(keep, dtype=np.uint8)
+    nd = len(doc_tok) - 1
+    if len(term_off) != nd + 1:
+        raise ValueError("term_off: one entry per document and one more")
+    ids_cap = len(ids) if ids_cap is None else ids_cap
+    cap = len(term_id) if cap is None else cap
+    if ids_cap > len(ids) or cap > len(term_id):
+        raise ValueError("ids_cap / cap: at most the arrays' lengths")
+    rows = max(nd, 1) * max(int(topk), 1)
+    ki, ks, kn = np.empty(rows, np.uint32), np.empty(rows, np.float32), np.empty(max(nd, 1), np.uint32)
+    _check(lib().jb_textrank(ids.ctypes.data if len(ids) else None, ids_cap, doc_tok.ctypes.data,
+                             len(ids) if ntok is None else ntok, nd, term_id.ctypes.data if len(term_id) else None,
+                             term_off.ctypes.data, cap, k.ctypes.data if len(k) else None, len(k), span, iters, topk,
+                             ki.ctypes.data, ks.ctypes.data, kn.ctypes.data))
+    shape = (nd, int(topk))
+    return ki[:nd * topk].reshape(shape), ks[:nd * topk].reshape(shape), kn[:nd]

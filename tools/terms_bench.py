@@ -13,9 +13,15 @@ Then, on the CSR the terms step left on the device, the document-frequency steps
 method in the same process: the hipMemsetAsync of df, jb_df_device in both forms (JB_DF_COMBINE 0 and 1,
 the order alternated from step to step) and jb_idf_device, each beside the terms step of the same run;
 and jb_df_batch from host memory beside jb_keywords_batch.
-Writes two JSON documents (--out, and --df-out for the document-frequency rows) and prints them.
+Then, on the ids and the CSR of the first corpus (1 GiB), jb_textrank_device with jieba's arguments (span 5,
+10 rounds, top 20; the keep mask drops one-rune keys) in both forms of its push kernel (JB_TR_WINDOW 0 and
+1, the order alternated from step to step), beside the cut and terms steps of the same run, its kernels
+once more through jb_profile_read, and the two forms' records compared byte for byte.
+Writes three JSON documents (--out, --df-out for the document-frequency rows, --tr-out for the TextRank
+rows) and prints them.  --textrank-only measures the TextRank rows alone and leaves the other two files.
 
-    python tools/terms_bench.py --out profiles/terms_bench.json --df-out profiles/df_bench.json
+    python tools/terms_bench.py --out profiles/terms_bench.json --df-out profiles/df_bench.json \
+        --tr-out profiles/textrank_bench.json
 """
 import argparse
 import ctypes as C
@@ -110,7 +116,50 @@ def measure_df(torch, J, forms, hip, t_id, t_n, nterms, cap, nw, nd, t_terms, st
     return res
 
 
-def measure(torch, J, tk, d_w, nw, label, buf, off, steps, warmup, forms=None, hip=None):
+TR_SPAN, TR_ITERS = 5, 10
+
+
+def measure_textrank(torch, J, forms, d_ids, pd, pn, ntok, nd, t_id, t_off, nterms, d_keep, nkeep, t_cut, t_terms, steps,
+                     warmup):
+    """jb_textrank_device on the ids and the CSR this run left on the device, in both forms of the push
+    kernel (forms: {name: a tokenizer opened with that JB_TR_WINDOW}).  The capacities are the token count,
+    as a chain that reads nothing on the host has them."""
+    stream = torch.cuda.current_stream().cuda_stream
+    need = J.textrank_work_bytes(ntok, ntok, nd)
+    work = torch.empty(need, dtype=torch.uint8, device="cuda")
+    outs = {n: (torch.empty(nd * TOPK, dtype=torch.int32, device="cuda"), torch.empty(nd * TOPK, dtype=torch.int32, device="cuda"),
+                torch.empty(nd, dtype=torch.int32, device="cuda")) for n in forms}
+    fn = {n: (lambda t=t, o=outs[n]: t.textrank_device(d_ids.data_ptr(), ntok, pd, pn, nd, t_id.data_ptr(), t_off.data_ptr(),
+                                                        ntok, d_keep.data_ptr(), nkeep, o[0].data_ptr(), o[1].data_ptr(),
+                                                        o[2].data_ptr(), work.data_ptr(), need, TR_SPAN, TR_ITERS, TOPK, stream))
+          for n, t in forms.items()}
+    t_tr = timed_ab(torch, fn, steps, warmup)
+    names = list(forms)
+    same = all(torch.equal(a, b) for a, b in zip(outs[names[0]], outs[names[1]]))
+    prof = {}
+    for n, t in forms.items():
+        t.profile(True)
+        t.profile_reset()
+        for _ in range(steps):
+            fn[n]()
+        torch.cuda.synchronize()
+        prof[n] = {k: round(v[0] / steps, 4) for k, v in t.profile_read().items() if k.startswith("k_tr_")}
+        t.profile(False)
+    best = min(names, key=lambda n: t_tr[n]["median_ms"])
+    res = {"span": TR_SPAN, "iters": TR_ITERS, "topk": TOPK, "tokens": ntok, "nterms": nterms, "docs": nd,
+           "work_bytes": int(need), "rows_filled": int(outs[names[0]][2].sum().item()),
+           "forms_give_identical_bytes": bool(same), "faster_form": best,
+           "cut_device_hmm1_median_ms": t_cut["median_ms"], "terms_device_median_ms": t_terms["median_ms"],
+           "kernels_profile_ms_per_call": prof}
+    for n in names:
+        res["textrank_device_" + n] = t_tr[n]
+        res["textrank_" + n + "_over_cut"] = round(t_tr[n]["median_ms"] / t_cut["median_ms"], 4)
+        res["textrank_" + n + "_over_terms"] = round(t_tr[n]["median_ms"] / t_terms["median_ms"], 4)
+    del work
+    return res
+
+
+def measure(torch, J, tk, d_w, nw, label, buf, off, steps, warmup, forms=None, hip=None, tr_forms=None, d_keep=None):
     stream = torch.cuda.current_stream().cuda_stream
     nb, nd = int(off[-1]), len(off) - 1
     d_text = torch.from_numpy(np.ascontiguousarray(buf[:nb])).cuda()
@@ -174,6 +223,11 @@ def measure(torch, J, tk, d_w, nw, label, buf, off, steps, warmup, forms=None, h
     }
     if forms:
         res["df"] = measure_df(torch, J, forms, hip, t_id, t_n, nterms, ntok, nw, nd, t_terms, steps, warmup)
+    if tr_forms:
+        del work
+        res["textrank"] = measure_textrank(torch, J, tr_forms, d_ids, pd, pn, ntok, nd, t_id, t_off, nterms, d_keep, nw,
+                                           t_cut, t_terms, steps, warmup)
+        work = None
     print(f"terms_bench.py: {label} measured", file=sys.stderr, flush=True)
     del d_text, d_off, d_ids, t_id, t_cnt, work
     torch.cuda.empty_cache()
@@ -189,6 +243,9 @@ def main():
     ap.add_argument("--host-steps", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "terms_bench.json"))
     ap.add_argument("--df-out", default=os.path.join(ROOT, "profiles", "df_bench.json"))
+    ap.add_argument("--tr-out", default=os.path.join(ROOT, "profiles", "textrank_bench.json"))
+    ap.add_argument("--textrank-only", action="store_true",
+                    help="measure the first corpus and its TextRank rows alone; write --tr-out only")
     args = ap.parse_args()
 
     import torch
@@ -224,6 +281,18 @@ def main():
         del os.environ["JB_DF_COMBINE"]
     else:
         os.environ["JB_DF_COMBINE"] = old
+    # jb_textrank_device's two forms, likewise
+    tr_forms = {}
+    old = os.environ.get("JB_TR_WINDOW")
+    for name, val in (("plain", "0"), ("window", "1")):
+        os.environ["JB_TR_WINDOW"] = val
+        tr_forms[name] = J.Tokenizer(J.make_config(dict_path=dpath, emit_path=epath, kind=J.JB_DICT_PREFIX,
+                                                   size_override=J.JIEBA_SIZE, device=0))
+    if old is None:
+        del os.environ["JB_TR_WINDOW"]
+    else:
+        os.environ["JB_TR_WINDOW"] = old
+    d_keep = torch.from_numpy((w != 0).astype(np.uint8)).cuda()
     hip = C.CDLL("libamdhip64.so.7")
     hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
     out = {"device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup, "topk": TOPK,
@@ -231,12 +300,39 @@ def main():
            "batches": []}
     threads = max(1, min(16, os.cpu_count() or 1))
     big = None
+    tr_doc = {k: out[k] for k in ("device", "steps", "warmup", "vocabulary_keys")}
+    tr_doc["kept_keys"] = int((w != 0).sum())
+    tr_doc["forms"] = {"plain": "JB_TR_WINDOW=0: k_tr_push, a gather from memory and one global atomic per kept token",
+                       "window": "JB_TR_WINDOW=1: k_tr_push_win, an LDS tile with a halo and a table that combines a "
+                                 "workgroup's adds"}
+
+    def write(path, doc):
+        text = json.dumps(doc, indent=1)
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text + "\n")
+        print(text)
+
     for mib in args.sizes_mib:
         buf, off, _ = s.corpus_parallel(synth.KIND_DOCS, 0, target_bytes=int(mib * (1 << 20)), threads=threads)
-        if big is None:
+        first = big is None
+        if first:
             big = (buf, off, mib)
         out["batches"].append(measure(torch, J, tk, d_w, len(w), f"C_syn {mib:g} MiB", buf, off, args.steps, args.warmup,
-                                      forms, hip))
+                                      None if args.textrank_only else forms, hip, tr_forms if first else None, d_keep))
+        if first:
+            b = out["batches"][-1]
+            tr_doc["batches"] = [dict(batch=b["batch"], bytes=b["bytes"], **b.pop("textrank"))]
+            if args.textrank_only:
+                break
+    for t in tr_forms.values():
+        t.close()
+    write(args.tr_out, tr_doc)
+    if args.textrank_only:
+        tk.close()
+        for t in forms.values():
+            t.close()
+        return 0
     buf, off, _ = s.corpus(synth.KIND_SENTENCES, 0, max_docs=10_000, target_bytes=64 << 20)
     out["batches"].append(measure(torch, J, tk, d_w, len(w), "S10k: 10,000 sentences", buf, off, args.steps, args.warmup,
                                   forms, hip))
@@ -276,12 +372,8 @@ def main():
     df_doc["batches"] = [dict(batch=b["batch"], docs=b["docs"], tokens=b["tokens"], **b.pop("df")) for b in out["batches"]]
     df_doc["host"] = {k: host[k] for k in ("batch", "bytes", "keywords_batch_hmm1_top20", "df_batch_hmm1",
                                            "df_batch_over_keywords_batch")}
-    for path, doc in ((args.out, out), (args.df_out, df_doc)):
-        text = json.dumps(doc, indent=1)
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            f.write(text + "\n")
-        print(text)
+    write(args.out, out)
+    write(args.df_out, df_doc)
     return 0
 
 
