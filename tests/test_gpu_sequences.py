@@ -1,0 +1,642 @@
+"""GPU: one tokenizer kept open over a sequence of calls, every call checked against the shadow model of
+tests/ctx_model.py (the references of the other GPU files, and nothing of the library): spans, doc_tok,
+ids, counters, keyword records with their f32 score bits, kw_n and jb_last_stats' token count, all exact.
+What the sequences cross is the state a jb_ctx keeps between calls: the grow-only workspace and the buffers
+that follow it, the three captured graphs, the image AddWord swaps in (with full mode's look-back reach),
+the vocabulary, the four arenas of the *_batch calls, and the flags behind jb_last_stats (DESIGN.md,
+"One context over many calls")."""
+import numpy as np
+import pytest
+
+import ctx_model as M
+import full_ref as F
+import jiebahip as J
+import search_ref as R
+import synth
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 0x7A7A7A7A
+NG = 64  # canary words on each side of a caller-owned device output
+JUNK = 0x33333333  # what every output holds before a call
+X4 = "\U00020000"  # a 4-byte Han rune
+TILE = 4096  # kTileBytes
+COMBOS = (("plain", True), ("plain", False), ("search", True), ("full", False))
+
+
+# ---- comparing ----------------------------------------------------------------------------------------------
+def same_spans(got, want, label):
+    gs, ge, gd = (np.asarray(x, np.uint64) for x in got)
+    ws, we, wd = (np.asarray(x, np.uint64) for x in want)
+    if not (np.array_equal(gs, ws) and np.array_equal(ge, we)):
+        n = min(len(gs), len(ws))
+        ne = (gs[:n] != ws[:n]) | (ge[:n] != we[:n])
+        bad = int(np.argmax(ne)) if ne.any() else n
+        raise AssertionError(f"{label}: {len(gs)} vs {len(ws)} spans; first diff #{bad}: "
+                             f"gpu={list(zip(gs[bad:bad + 6].tolist(), ge[bad:bad + 6].tolist()))} "
+                             f"want={list(zip(ws[bad:bad + 6].tolist(), we[bad:bad + 6].tolist()))}")
+    assert np.array_equal(gd, wd), f"{label}: doc_tok"
+
+
+def same_bits(got, want, label):
+    for k, (g, w) in enumerate(zip(got, want)):
+        g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+        assert g.shape == w.shape and np.array_equal(g.view(np.uint32), w.view(np.uint32)), f"{label}: output {k}"
+
+
+def guarded(n, dtype):
+    import torch
+    t = torch.full((n + 2 * NG,), JUNK, dtype=dtype, device="cuda")
+    t[:NG] = GUARD
+    t[NG + n:] = GUARD
+    return t
+
+
+def inner(t, n, dtype):
+    a = t.cpu().numpy()
+    assert (a[:NG] == GUARD).all() and (a[NG + n:] == GUARD).all(), "written outside a caller-owned output"
+    return a[NG:NG + n].view(dtype)
+
+
+# ---- the driver: makes the library's call and the model's, and compares ------------------------------------
+class Dev:
+    """A batch on the device, kept for the whole sequence: a repeat finds the same pointers."""
+
+    def __init__(self, batch):
+        import torch
+        text, off = batch.rel()
+        self.nb, self.nd = batch.nbytes, batch.ndocs
+        self.text = torch.from_numpy(np.ascontiguousarray(text[:self.nb + 64])).cuda()
+        self.off = torch.from_numpy(off.astype(np.int64)).cuda()
+        self.base = int(batch.off[0])
+        self.outs = {}
+
+    def args(self):
+        return self.text.data_ptr(), self.nb, self.off.data_ptr(), self.nd
+
+
+class Driver:
+    def __init__(self, tk, model, s=None):
+        self.tk, self.m, self.s = tk, model, s
+        self.batches, self.devs = {}, {}
+        self.last = None  # the last cut: (batch, its expected spans)
+        self.stream = None
+
+    def st(self):
+        """A stream of the driver's own, for every device call: the library captures a graph only for a
+        pipeline queued on a caller's stream, never on the null stream (which is torch's current one)."""
+        import torch
+        if self.stream is None:
+            self.stream = torch.cuda.Stream()
+        torch.cuda.synchronize()  # (the uploads and fills before the call ran on torch's stream)
+        return self.stream.cuda_stream
+
+    def batch(self, b):
+        if isinstance(b, M.Batch):
+            return self.batches.setdefault(b.spec, b)
+        if b not in self.batches:
+            self.batches[b] = M.make_batch(self.s, b)
+        return self.batches[b]
+
+    def dev(self, b):
+        if b.spec not in self.devs:
+            self.devs[b.spec] = Dev(b)
+        return self.devs[b.spec]
+
+    # -- cuts
+    def cut(self, mode, hmm, route, b, reps=None, label=""):
+        """One cut; a device cut is made three times (direct, captured, replayed) unless reps says otherwise."""
+        b = self.batch(b)
+        want = self.m.cut(b, mode, hmm)
+        label = f"{label} {mode} hmm={hmm} {route} {b.spec}"
+        if route == "host":
+            tk = self.tk
+            got = tk.cut_batch_full(b.buf, b.off) if mode == "full" else (
+                tk.cut_batch_search if mode == "search" else tk.cut_batch)(b.buf, b.off, hmm)
+            same_spans(got, want, label)
+        else:
+            for rep in range(3 if reps is None else reps):
+                self._device(mode, hmm, b, want, route == "device_into", f"{label} call {rep}")
+        self.last = (b, want)
+        return want
+
+    def _device(self, mode, hmm, b, want, into, label):
+        import torch
+        tk, dv = self.tk, self.dev(b)
+        base = np.uint64(dv.base)
+        want = (want[0] - base, want[1] - base, want[2])
+        nw = len(want[0])
+        if into:
+            cap = max(nw, dv.nb, 1)
+            key = (mode, cap)
+            if key not in dv.outs:  # (kept, so that a repeat's graph key matches)
+                dv.outs[key] = (guarded(cap, torch.int32), guarded(cap, torch.int32), guarded(dv.nd + 1, torch.int64),
+                                guarded(1, torch.int64))
+            o = dv.outs[key]
+            for t in o:
+                t[NG:-NG] = JUNK
+            p = [t.data_ptr() + NG * t.element_size() for t in o]
+            st = self.st()
+            if mode == "full":
+                tk.cut_device_full_into(*dv.args(), p[0], p[1], cap, p[2], p[3], st)
+            else:
+                (tk.cut_device_search_into if mode == "search" else tk.cut_device_into)(
+                    *dv.args(), hmm, p[0], p[1], cap, p[2], p[3], st)
+            torch.cuda.synchronize()
+            tk.device_status(st)
+            n = int(inner(o[3], 1, np.uint64)[0])
+            assert n == nw, f"{label}: {n} spans, want {nw}"
+            got = (inner(o[0], cap, np.uint32)[:n], inner(o[1], cap, np.uint32)[:n], inner(o[2], dv.nd + 1, np.uint64))
+            same_spans(got, want, label)
+            return
+        st = self.st()
+        if mode == "full":
+            ps, pe, pd, pn = tk.cut_device_full(*dv.args(), st)
+        else:
+            ps, pe, pd, pn = (tk.cut_device_search if mode == "search" else tk.cut_device)(*dv.args(), hmm, st)
+        torch.cuda.synchronize()
+        code = J.JB_OK
+        try:
+            tk.device_status(st)
+        except J.JbError as e:
+            code = e.code
+        # (the ctx-owned arrays hold nbytes spans: a longer full-mode list is counted and reported)
+        assert code == (J.JB_ELIMIT if nw > dv.nb else J.JB_OK), f"{label}: status {code}"
+        n = int(J.dev_to_host(pn, 8, np.uint64)[0])
+        assert n == nw, f"{label}: {n} spans, want {nw}"
+        k = min(n, dv.nb)
+        got = (J.dev_to_host(ps, 4 * k, np.uint32), J.dev_to_host(pe, 4 * k, np.uint32),
+               J.dev_to_host(pd, 8 * (dv.nd + 1), np.uint64))
+        same_spans(got, (want[0][:k], want[1][:k], want[2]), label)
+
+    # -- ids of the last cut's spans
+    def ids(self, route, label=""):
+        import torch
+        b, (ws, we, _) = self.last
+        label = f"{label} ids {route} {b.spec}"
+        if route == "host":
+            if len(ws):
+                got = self.tk.spans_ids(b.buf, ws, we)
+                assert np.array_equal(got, self.m.ids(b.buf, ws, we, int(b.off[-1]))), label
+            return
+        dv = self.dev(b)
+        base = np.uint64(dv.base)
+        # the spans, and three the kernel must not trust: empty, reversed, past the text
+        s = np.concatenate([ws - base, np.array([3, 9, dv.nb], np.uint64)]).astype(np.uint32)
+        e = np.concatenate([we - base, np.array([3, 6, dv.nb + 3], np.uint64)]).astype(np.uint32)
+        n = len(s)
+        d_s, d_e = torch.from_numpy(s.view(np.int32)).cuda(), torch.from_numpy(e.view(np.int32)).cuda()
+        d_n = torch.tensor([n], dtype=torch.int64, device="cuda")
+        o = guarded(n, torch.int32)
+        self.tk.ids_device(dv.text.data_ptr(), dv.nb, d_s.data_ptr(), d_e.data_ptr(), d_n.data_ptr(), n,
+                           o.data_ptr() + 4 * NG, self.st())
+        torch.cuda.synchronize()
+        text = b.rel()[0]
+        assert np.array_equal(inner(o, n, np.uint32), self.m.ids(text, s, e, dv.nb)), label
+
+    # -- the *_batch calls, into outputs that start as garbage
+    def keywords(self, hmm, b, topk, label=""):
+        b = self.batch(b)
+        w = self.m.weights
+        nd = b.ndocs
+        ki, ks, kc = (np.full(nd * topk, JUNK, np.uint32) for _ in range(3))
+        kn = np.full(nd, JUNK, np.uint32)
+        J._check(J.lib().jb_keywords_batch(self.tk.h, b.buf.ctypes.data, b.off.ctypes.data, nd, int(hmm),
+                                           w.ctypes.data if len(w) else None, len(w), topk, ki.ctypes.data,
+                                           ks.ctypes.data, kc.ctypes.data, kn.ctypes.data))
+        got = (ki.reshape(nd, topk), ks.view(np.float32).reshape(nd, topk), kc.reshape(nd, topk), kn)
+        same_bits(got, self.m.keywords(b, hmm, topk), f"{label} keywords_batch hmm={hmm} {b.spec} topk={topk}")
+        return got
+
+    def df(self, hmm, b, label=""):
+        b = self.batch(b)
+        ndf = len(self.m.keys)
+        before = (np.arange(ndf, dtype=np.uint32) * np.uint32(2654435761)) >> np.uint32(8)  # (the counters are added to)
+        got = self.tk.df_batch(b.buf, b.off, hmm, before.copy())
+        assert np.array_equal(got, before + self.m.df(b, hmm, ndf)), f"{label} df_batch hmm={hmm} {b.spec}"
+        return got - before
+
+    def textrank(self, hmm, b, span=5, iters=10, topk=20, label=""):
+        b = self.batch(b)
+        k = self.m.keep
+        nd = b.ndocs
+        ki, ks = np.full(nd * topk, JUNK, np.uint32), np.full(nd * topk, JUNK, np.uint32)
+        kn = np.full(nd, JUNK, np.uint32)
+        J._check(J.lib().jb_textrank_batch(self.tk.h, b.buf.ctypes.data, b.off.ctypes.data, nd, int(hmm),
+                                           k.ctypes.data if len(k) else None, len(k), span, iters, topk,
+                                           ki.ctypes.data, ks.ctypes.data, kn.ctypes.data))
+        got = (ki.reshape(nd, topk), ks.view(np.float32).reshape(nd, topk), kn)
+        same_bits(got, self.m.textrank(b, hmm, span, iters, topk),
+                  f"{label} textrank_batch hmm={hmm} {b.spec} span={span} iters={iters} topk={topk}")
+        return got
+
+    # -- the rest
+    def add_word(self, word, freq):
+        assert self.m.reachable(word), word  # (every word these tests add becomes an edge of buildDag)
+        self.tk.AddWord(word, freq)
+        f = self.m.add_word(word, freq)
+        assert self.m.is_edge(word), word
+        assert self.tk.dict_get(word) == f and self.tk.size == self.m.o.size, (word, freq)
+
+    def set_vocab(self, keys):
+        self.tk.set_vocab(keys)
+        self.m.set_vocab(keys)
+        assert self.tk.vocab_size == len(keys)
+
+    def stats(self, label=""):
+        """jb_last_stats describes the ctx's last cut, whichever call made it."""
+        if self.m.last_tokens is not None:
+            assert self.tk.last_stats()["tokens"] == self.m.last_tokens, f"{label} last_stats"
+
+    def run(self, op):
+        k = op[0]
+        if k == "cut":
+            self.cut(op[1], op[2], op[3], op[4])
+        elif k == "add_word":
+            self.add_word(self.m.pick_word(op[1]), op[2])
+        elif k == "set_vocab":
+            self.set_vocab(self.m.vocab_keys(op[1]))
+        elif k == "ids":
+            if self.last is not None:
+                self.ids(op[1])
+        elif k == "keywords_batch":
+            self.keywords(op[1], op[2], op[3])
+        elif k == "df_batch":
+            self.df(op[1], op[2])
+        elif k == "textrank_batch":
+            self.textrank(op[1], op[2], *op[3:])
+        elif k == "last_stats":
+            self.stats()
+        else:
+            raise ValueError(op)
+
+
+# ---- fixtures -------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def syn(syn_small):
+    dp, ep, s = syn_small
+    with open(dp, "rb") as f:
+        d = f.read()
+    with open(ep, "rb") as f:
+        e = f.read()
+    return d, e, s, M.make_batch(s, M.VOCAB_SOURCE)
+
+
+@pytest.fixture(scope="module")
+def mini(mini_paths):
+    with open(mini_paths[0], encoding="utf-8") as f:
+        d = f.read()
+    with open(mini_paths[1], "rb") as f:
+        e = f.read()
+    return d if d.endswith("\n") else d + "\n", e
+
+
+def open_20k(syn):
+    d, e, s, source = syn
+    tk = J.Tokenizer(J.make_config(dict_bytes=d, emit_bytes=e))
+    return Driver(tk, M.Model(d, e, source=source), s)
+
+
+def open_text(dict_text, emit):
+    tk = J.Tokenizer(J.make_config(dict_bytes=dict_text.encode(), emit_bytes=emit))
+    return Driver(tk, M.Model(dict_text.encode(), emit))
+
+
+def at_edge(d, run, before="a", after="b"):
+    """A document of two text tiles: `before` bytes, then `run`, whose byte d lies on the edge between them."""
+    rb = run.encode()
+    pre = TILE - d
+    assert 0 < pre and pre + len(rb) < 2 * TILE
+    return before.encode() * pre + rb + b" " + after.encode() * (2 * TILE - pre - len(rb) - 1)
+
+
+def every_route(dr, b, combos=COMBOS, label=""):
+    for mode, hmm in combos:
+        for route in M.ROUTES:
+            dr.cut(mode, hmm, route, b, reps=1 if route == "device_into" else None, label=label)
+
+
+# ---- scripted sequences ---------------------------------------------------------------------------------------
+def test_add_word_reaches_every_mode(syn):
+    """A 64 KiB device batch in each mode three times (direct, captured, replayed), AddWord, the same twelve
+    calls, then the ids of the new spans: no mode may replay a graph that holds the old image."""
+    dr = open_20k(syn)
+    try:
+        m, b = dr.m, dr.batch(("small", 31, 64 << 10))
+        assert 32 << 10 < b.nbytes <= 64 << 10
+        dr.set_vocab(m.vocab_keys(0))
+        for mode, hmm in COMBOS:
+            dr.cut(mode, hmm, "device", b, label="before")
+        before = m.cut(b, "plain", True, count=False)
+        word = m.pick_word(0, b)
+        dr.add_word(word, 10_000_000)
+        after = m.cut(b, "plain", True, count=False)
+        assert len(after[0]) != len(before[0]) or not np.array_equal(after[0], before[0])  # (the reference's lists)
+        for mode, hmm in COMBOS:
+            dr.cut(mode, hmm, "device", b, label="after")
+            dr.ids("device", "after")
+            dr.ids("host", "after")
+        fs, fe, _ = m.cut(b, "full", False, count=False)
+        wb = word.encode()
+        assert any(bytes(b.buf[int(x):int(y)]) == wb for x, y in zip(fs[fe - fs == len(wb)], fe[fe - fs == len(wb)]))
+    finally:
+        dr.tk.close()
+
+
+G12 = "鼠牛虎兔龍蛇馬羊猴雞狗豬"  # (none of them in the mini dictionary)
+# Words of n distinct runes, one per n, that start at different runes and are not inside one another
+FAM = {9: G12[:9], 10: G12[1:11], 12: G12[::-1]}
+FAM2 = 10 ** 12  # the frequency of a word's first two runes (see reach_dict)
+
+
+def reach_dict(mini_text, chain):
+    """The chain of 甲 (chain: its lines) with 甲 x 11 as a key of frequency 0, the mini dictionary, and the
+    makings of three look-backs: the runes of G12 frequent, so that Cut takes them one by one, and of each
+    word of FAM its prefixes of 3 .. n - 1 runes as keys of frequency 0.  Its two-rune prefix is missing, so
+    nothing of a family can be reached and the longest reachable key has 8 runes.  AddWord of the two-rune
+    prefix opens the family; its frequency FAM2 lies where the reference's maxIndexProba (tokenizer.go:565-578,
+    which compares each item with the one before it) still takes the single rune: over the whole word's
+    weight plus n - 2 singles, under two singles."""
+    return (chain + mini_text + f"{'甲' * 11} 0\n" + "".join(f"{r} {10 ** 14}\n" for r in G12) +
+            "".join(f"{w[:k]} 0\n" for n, w in FAM.items() for k in range(3, n)))
+
+
+@pytest.mark.parametrize("chain", ["as the issue states it", "with a plain record first"])
+def test_add_word_moves_maxlen_and_the_record_limits(mini, chain):
+    """AddWord of 甲 x 9, x 10 and x 12 to a dictionary whose longest key has 8 runes: the first edge longer
+    than 8 runes, then a longest key past full_back's `maxlen > 9` branch.  After each add, search and full
+    mode through the host and both device calls, on 甲 x 200 between ASCII and a 4-byte rune around a
+    text-tile edge.
+
+    Two corrections to the issue's recipe, both asserted from Oracle.build_dag below.  With F.chain_dict(8)
+    the first 甲 of a run has 8 edges before any add, so its record is zero from the start (more than four
+    edges); the second parametrisation keeps 甲 x 2 .. x 7 as keys of frequency 0, so that 甲 has the two
+    edges {1, 8} and the add of 甲 x 9 is what turns the record zero.  And 甲 x 12 is reachable only with
+    甲 x 11 a key (AddWord adds no prefixes): the dictionary holds it with frequency 0, out of reach until
+    甲 x 9 and x 10 are keys.
+    A text of 甲 alone never looks back further than one rune, whatever maxlen is (every 甲 but the last has
+    a word), so the reach itself is checked with a second family: after 甲 x n, a word of n distinct runes
+    is added (FAM), whose last rune, a plain token of its own, finds the word n - 1 runes back, which takes
+    maxlen >= n."""
+    mini_text, emit = mini
+    lines = F.chain_dict(8) if chain == "as the issue states it" else (
+        "甲 100\n" + "".join(f"{'甲' * k} 0\n" for k in range(2, 8)) + f"{'甲' * 8} 108\n")
+    dr = open_text(reach_dict(mini_text, lines), emit)
+    try:
+        m = dr.m
+        run = "甲" * 200
+        fam = "".join(w + w[0] + X4 + "c" for w in FAM.values())
+        docs = [("a" * 5 + fam + "b " + run).encode()]  # (the head of a batch: bytes under 32)
+        docs += [at_edge(d, run + X4 + "c" + fam) for d in (1, 2, 3, 299, 300, 598, 599, 600, 601, 604, 605)]
+        docs += [at_edge(d, fam + run) for d in range(0, len(fam.encode()), 5)]
+        b = M.from_texts(("reach",), docs)
+        edges0 = m.o.build_dag(run)[0]
+        assert edges0 == (list(range(1, 9)) if chain == "as the issue states it" else [1, 8])
+        every_route(dr, b, COMBOS[2:], "before")
+        for n, w in FAM.items():
+            dr.add_word("甲" * n, 100 + n)
+            edges = m.o.build_dag(run)[0]
+            # (an edge of more than 8 runes: a zero record)
+            assert edges == edges0 + [k for k in FAM if k <= n] and max(edges) == n
+            every_route(dr, b, COMBOS[2:], f"甲 x {n}")
+            assert not m.reachable(w)
+            dr.add_word(w[:2], FAM2)
+            dr.add_word(w, 1)
+            assert m.o.build_dag(w + w[0])[0] == [1, 2, n] and m.o.cut(w + w[0], False) == list(w + w[0])
+            # (from the reference: the word's last rune is covered from n - 1 runes back, the rune behind is not)
+            assert F.expected_text(m.o, w + w[0], m.blocks) == [w[:2], w, w[0]]
+            every_route(dr, b, COMBOS[2:], f"{n} distinct runes")
+            dr.stats()
+    finally:
+        dr.tk.close()
+
+
+def test_a_fifth_edge(mini):
+    """甲 has exactly four edges in chain_dict(4); 甲 x 5 gives it a fifth, so its record turns zero and the
+    mode passes walk the trie for it (srch_edges, full_walk)."""
+    mini_text, emit = mini
+    dr = open_text(F.chain_dict(4) + mini_text, emit)
+    try:
+        m = dr.m
+        run = "甲" * 40
+        assert m.o.build_dag(run)[0] == [1, 2, 3, 4]
+        docs = [run, "今天天氣很好" + run + "，一刹那" + "甲" * 5, "甲" * 4 + "a" + "甲" * 5 + X4 + "甲" * 6]
+        docs += [at_edge(d, run + X4 + "一刹那") for d in (2, 3, 30, 60, 119, 120)]
+        b = M.from_texts(("fifth",), docs)
+        every_route(dr, b, label="four edges")
+        dr.add_word("甲" * 5, 105)
+        assert m.o.build_dag(run)[0] == [1, 2, 3, 4, 5]
+        every_route(dr, b, label="five edges")
+        dr.stats()
+    finally:
+        dr.tk.close()
+
+
+def test_a_word_with_a_four_byte_rune(mini):
+    """A word whose runes include 4-byte ones, added to a dictionary that holds its proper prefixes, cut in
+    the three modes around a text-tile edge before and after."""
+    _, emit = mini
+    word = "𠀀𠀁中𪜀"
+    lines = "𠀀 10\n𠀀𠀁 20\n𠀀𠀁中 30\n𠀁 3\n𠀁中 9\n中 50\n中𪜀 8\n𪜀 4\n"
+    dr = open_text(lines, emit)
+    try:
+        m = dr.m
+        run = "a" + word + "𠀀𠀁中" + word
+        n = len(run.encode())
+        b = M.from_texts(("x4",), [run] + [at_edge(d, run) for d in range(0, n + 1)])
+        assert m.o.get(word) is None and 4 not in m.o.build_dag(word)[0]
+        every_route(dr, b, label="before")
+        dr.add_word(word, 40)
+        assert 4 in m.o.build_dag(word)[0]
+        # (now the dictionary of the hand-worked example)
+        assert R.expected_text(m.o, "a𠀀𠀁中𪜀𠀀𠀁中", True) == R.EXAMPLES[2][1][0][1]
+        every_route(dr, b, label="after")
+    finally:
+        dr.tk.close()
+
+
+def test_frequency_change_and_suggested_frequency(syn):
+    """An existing word added again with another frequency: the dictionary's size, and with it every weight,
+    moves.  Then AddWord(w, 0), whose frequency the library suggests from its own cut of the word."""
+    dr = open_20k(syn)
+    try:
+        m, b = dr.m, dr.batch(("small", 310, 40 << 10))
+        for mode, hmm in (("plain", True), ("search", True)):
+            dr.cut(mode, hmm, "host", b, label="before")
+            dr.cut(mode, hmm, "device", b, label="before")
+        s, e, _ = m.cut(b, "plain", True, count=False)
+        two = [bytes(b.buf[int(x):int(y)]).decode("utf-8", "replace") for x, y in zip(s[e - s == 6], e[e - s == 6])]
+        word = next(w for w in two if len(w) == 2 and (m.o.get(w) or 0) > 0 and m.reachable(w))
+        size0, f0 = m.o.size, m.o.get(word)
+        dr.add_word(word, 50 * f0 + 12_345)
+        assert dr.tk.size == size0 + 50 * f0 + 12_345 == m.o.size  # (addTerm adds to the size, tokenizer.go:580-585)
+        for mode, hmm in (("plain", True), ("search", True)):
+            dr.cut(mode, hmm, "host", b, label="another frequency")
+            dr.cut(mode, hmm, "device", b, label="another frequency")
+        w2 = m.pick_word(0)
+        want, pieces = m.suggest(w2)
+        assert dr.tk.suggest_freq(w2) == want
+        dr.add_word(w2, 0)
+        assert dr.tk.dict_get(w2) == want and m.last_tokens == len(pieces)
+        dr.stats("the cut AddWord made")
+        for mode, hmm in (("plain", True), ("search", True)):
+            dr.cut(mode, hmm, "host", b, label="suggested frequency")
+            dr.cut(mode, hmm, "device", b, label="suggested frequency")
+    finally:
+        dr.tk.close()
+
+
+def test_saved_image_in_every_mode(syn, tmp_path):
+    """save after two AddWords, FromImage: the new tokenizer cuts, looks ids up and ranks as the same model."""
+    dr = open_20k(syn)
+    tk2 = None
+    try:
+        m, b = dr.m, dr.batch(("small", 520, 48 << 10))
+        dr.cut("plain", True, "device", b)
+        dr.add_word(m.pick_word(0), 10_000_000)
+        dr.cut("full", False, "device", b)
+        dr.add_word(m.pick_word(1), 0)
+        path = str(tmp_path / "two_adds.jbimg")
+        dr.tk.save(path)
+        tk2 = J.Tokenizer.FromImage(path)
+        assert tk2.size == m.o.size
+        m.last_tokens = None  # (a new ctx has cut nothing)
+        d2 = Driver(tk2, m, dr.s)
+        d2.set_vocab(m.vocab_keys(2))
+        every_route(d2, b, label="from the image")
+        d2.ids("device")
+        d2.ids("host")
+        d2.textrank(True, dr.batch(("small", 530, 36 << 10)))
+        d2.stats()
+    finally:
+        dr.tk.close()
+        if tk2 is not None:
+            tk2.close()
+
+
+def test_workspace_growth_between_captured_graphs(syn):
+    """A (8 KiB), B (300 KiB), A again on the same device buffers, C (1,500 documents of one or two runes:
+    growth by the document count alone), A again: each three times in each mode, so that every mode has a
+    captured graph when the workspace is replaced under it.
+    The issue words the first condition as "A is under the 4,096-byte minimum"; with A at 8 KiB that cannot
+    hold, and what the sequence needs is asserted instead: A is over the minimum, so the first call
+    allocates A's own size and no more, and B, over every earlier size, has to grow it."""
+    dr = open_20k(syn)
+    try:
+        buf, off, _ = dr.s.corpus(synth.KIND_SENTENCES, 40, target_bytes=8 << 10)
+        a = M.Batch(("A",), buf, off)
+        b, c = dr.batch(("grow", 50, 300 << 10)), dr.batch(("manydocs", 60, 1500))
+        assert M.WORK_MIN_BYTES < a.nbytes <= 9 << 10 and a.ndocs <= M.WORK_MIN_DOCS
+        assert b.nbytes > 250 << 10 and b.nbytes > a.nbytes and b.ndocs <= M.WORK_MIN_DOCS
+        assert c.nbytes < b.nbytes and c.ndocs == 1500 > M.WORK_MIN_DOCS
+        assert 1 <= np.diff(c.off.astype(np.int64)).min() and np.diff(c.off.astype(np.int64)).max() <= 8
+        for x in (a, b, a, c, a):
+            for mode, hmm in COMBOS:
+                dr.cut(mode, hmm, "device", x)
+            dr.stats()
+        for x in (b, a):  # (and into caller-owned arrays)
+            for mode, hmm in COMBOS:
+                dr.cut(mode, hmm, "device_into", x, reps=3)
+    finally:
+        dr.tk.close()
+
+
+def test_small_batches_follow_the_image(syn):
+    """Plain host batches of at most 4,096 bytes (k_small) between a 64 KiB host batch (the piece pipeline)
+    and a device call, with batches of empty documents among them, before and after AddWord; after every call
+    jb_last_stats reports that call's tokens."""
+    dr = open_20k(syn)
+    try:
+        m = dr.m
+        t1, t2 = dr.batch(("tiny", 900, 8)), dr.batch(("tiny", 910, 3))
+        h, d = dr.batch(("small", 920, 64 << 10)), dr.batch(("small", 930, 40 << 10))
+        none = dr.batch(("empty", 0, 4))
+        assert t1.nbytes <= M.SMALL_MAX and t2.nbytes <= M.SMALL_MAX and h.nbytes > 32 << 10
+        word = m.pick_word(0, t1)
+
+        def lap(label):
+            for hmm in (True, False):
+                for x, mode, route in ((t1, "plain", "host"), (h, "plain", "host"), (t2, "plain", "host"),
+                                       (d, "plain", "device"), (t1, "plain", "host"), (d, "search", "device"),
+                                       (t2, "plain", "host"), (h, "full", "host"), (t1, "search", "host"),
+                                       (t2, "plain", "host"), (d, "plain", "device_into"), (t1, "plain", "host"),
+                                       (none, "plain", "host"), (t2, "plain", "host"), (none, "search", "host"),
+                                       (d, "plain", "device"), (none, "plain", "device"), (h, "plain", "host"),
+                                       (none, "full", "device_into"), (t1, "plain", "host")):
+                    dr.cut(mode, hmm, route, x, reps=1, label=label)
+                    dr.stats(f"{label} after {mode} {route} {x.spec} hmm={hmm}")
+
+        lap("before")
+        before = [m.cut(x, "plain", hmm, count=False) for x in (t1, t2) for hmm in (True, False)]
+        dr.add_word(word, 10_000_000)
+        dr.stats("after AddWord")
+        after = [m.cut(x, "plain", hmm, count=False) for x in (t1, t2) for hmm in (True, False)]
+        assert any(len(x[0]) != len(y[0]) for x, y in zip(before, after))  # (the small batches' answers move)
+        lap("after")
+    finally:
+        dr.tk.close()
+
+
+def test_batch_calls_share_their_buffers(syn):
+    """keywords_batch, textrank_batch and df_batch on one ctx, in a changing order: a 200 KiB batch, one
+    3-byte document, five empty documents, the large buffer from its document 3 on (doc_off[0] != 0), a
+    smaller vocabulary with a longer longest key, AddWord, and the large batch again."""
+    dr = open_20k(syn)
+    try:
+        m = dr.m
+        big = dr.batch(("large", 1700, 200 << 10))
+        one, none = M.from_texts(("one",), ["中"]), dr.batch(("empty", 0, 5))
+        tail = M.Batch(("tail",), big.buf, big.off[3:])
+        assert big.nbytes > 150 << 10 and one.nbytes == 3 and none.nbytes == 0 and none.ndocs == 5 and int(tail.off[0]) > 0
+        v1, v2 = m.vocab_keys(0), m.vocab_keys(1)
+        assert len(v2) < len(v1) and max(map(len, v2)) > max(map(len, v1)) == 6
+        assert sum(1 for k in v2[:-1] if len(k) > 6) > 20  # (tokens of the text that only the new maxlen admits)
+
+        def calls(b, order, label):
+            out = {}
+            for k in order:
+                if k == "k":
+                    out[k] = dr.keywords(True, b, 20, label)
+                elif k == "t":
+                    out[k] = dr.textrank(True, b, label=label)
+                else:
+                    out[k] = dr.df(True, b, label)
+                dr.stats(label)
+            return out
+
+        dr.set_vocab(v1)
+        got = calls(big, "ktd", "1")
+        assert got["k"][3].max() == 20 and got["t"][2].max() == 20 and int(got["d"].sum()) > 10 * big.ndocs
+        calls(one, "tdk", "2")
+        got = calls(none, "dkt", "3")
+        assert not got["d"].any()  # the counters unchanged
+        assert not got["k"][3].any() and (got["k"][0] == J.JB_ID_UNK).all() and not got["k"][1].any()
+        assert not got["t"][2].any() and (got["t"][0] == J.JB_ID_UNK).all() and not got["t"][1].any()
+        calls(tail, "tkd", "4")
+        dr.set_vocab(v2)
+        calls(big, "dtk", "5")
+        calls(one, "kdt", "5")
+        dr.add_word(m.pick_word(0, big), 10_000_000)
+        calls(big, "kdt", "6")
+        calls(none, "tkd", "6")
+        calls(big, "tdk", "7")
+    finally:
+        dr.tk.close()
+
+
+# ---- random sequences -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", M.SEEDS)
+def test_random_sequences(syn, seed):
+    """gen_ops(seed, NSTEPS) on one tokenizer, every step against the model.  A failure names the seed, the
+    step and the ops up to it: `Driver.run` over that list replays it."""
+    ops = M.gen_ops(seed, M.NSTEPS)
+    dr = open_20k(syn)
+    try:
+        dr.set_vocab(dr.m.vocab_keys(0))
+        for i, op in enumerate(ops):
+            try:
+                dr.run(op)
+            except (AssertionError, J.JbError) as e:
+                raise AssertionError(f"seed {seed}, step {i}: {op!r}\nops = {ops[:i + 1]!r}\n{e}") from e
+    finally:
+        dr.tk.close()
