@@ -211,8 +211,12 @@ __device__ __forceinline__ uint32_t dec_lead(uint32_t x, uint32_t lim, uint32_t*
 }
 
 // The Han rune encoded by x (Go-valid, within `lim` bytes), or 0.  A 3-byte
-// form with a Han value cannot be overlong (E0) or a surrogate (ED), and a
-// 4-byte form with a Han value is >= U+16FF0, so the bit patterns suffice.
+// form with a Han value cannot be overlong (E0: below U+0800) or a surrogate
+// (ED), so its bit pattern suffices.  A 4-byte form can be overlong with a
+// Han value (F0 84 B8 80 has the value U+4E00; Go decodes four invalid
+// bytes), hence the test r >= 0x10000: every overlong F0 form lies below it
+// and no valid one does.  F5..F7 and F4 90.. lie past U+10FFFF, where
+// han_cp has nothing.
 __device__ __forceinline__ uint32_t han_rune(uint32_t x, uint32_t lim, uint32_t* w) {
     const uint32_t b0 = x & 0xFFu;
     if ((x & 0x00C0C0F0u) == 0x008080E0u) {
@@ -224,7 +228,7 @@ __device__ __forceinline__ uint32_t han_rune(uint32_t x, uint32_t lim, uint32_t*
     if ((x & 0xC0C0C0F8u) == 0x808080F0u) {
         const uint32_t r =
             ((b0 & 0x07u) << 18) | (((x >> 8) & 0x3Fu) << 12) | (((x >> 16) & 0x3Fu) << 6) | ((x >> 24) & 0x3Fu);
-        if (lim < 4u || !han_cp(r)) return 0u;
+        if (lim < 4u || r < 0x10000u || !han_cp(r)) return 0u;
         *w = 4u;
         return r;
     }
