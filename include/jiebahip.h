@@ -547,6 +547,107 @@ int jb_textrank_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off,
                       const uint8_t *keep, uint32_t nkeep, uint32_t span, uint32_t iters, uint32_t topk,
                       uint32_t *kw_id, float *kw_score, uint32_t *kw_n);
 
+/* ---- joined text (" ".join(cut(line)); the reference returns []string) ----------------------
+ * The tokens of a span list written out as delimited text, on the device: one contiguous buffer of
+ * keys, separators and document terminators, about nbytes + ntokens bytes that can go straight to a
+ * file (word2vec / fastText input, an indexer), where a span list is 8 to 16 bytes per token that the
+ * host still has to slice.  The output is a gather over a span list, not "the text with separators
+ * inserted": search and full mode emit overlapping spans, and one rule serves all three modes.
+ *
+ * The rule.  jb_join (host only, no ctx, no GPU) and jb_join_device agree to the byte.
+ *  - Inputs: text (nbytes bytes; on the device plus 64 readable padding bytes, as for jb_ids_device),
+ *    spans start / end (u32) with capacity cap, doc_tok (u64[ndocs + 1], non-decreasing), ntok (the
+ *    device reads *d_ntok on the device), sep (seplen bytes) and term (termlen bytes), each of 0 to
+ *    JB_JOIN_MAXSEP bytes.
+ *  - Token k exists iff k < min(ntok, cap).  Document d's tokens are [doc_tok[d], doc_tok[d+1])
+ *    clamped to that bound: the clamps of jb_terms_device, so full mode's over-long list is handled
+ *    the same way.  A token before doc_tok[0] or at or past doc_tok[ndocs] belongs to no document.
+ *  - The key of span [s, e) follows the jb_ids_device rule: the bytes text[s..e); EF BF BD for a
+ *    1-byte span whose byte is >= 0x80 (an invalid UTF-8 byte, the reference's "�").  The spans are
+ *    not trusted: s >= e or e > nbytes gives an empty key, and no byte of it is read.  There is no
+ *    upper length limit: a 1 MB alnum run is one token and is copied whole.
+ *  - Document d's output is key_0 sep key_1 sep ... key_{n-1} term.  The separator stands between
+ *    consecutive tokens only; the terminator follows every document, empty ones included (with n = 0
+ *    the output is term alone).
+ *  - out_doc_off (u64[ndocs + 1], out_doc_off[0] = 0) and nout = out_doc_off[ndocs] always describe
+ *    the complete output.  Bytes with index >= out_cap are not written, and nothing else is written,
+ *    in particular nothing at or past out[out_cap].  The caller checks nout <= out_cap (as in
+ *    jb_terms_device, there is no jb_device_status report).
+ *  - All offsets are 64 bits wide: full mode with replacement characters can pass 4 GiB.
+ *  - Limits: JB_EINVAL for a null pointer (sep and term may be NULL when their length is 0; start,
+ *    end and out when their capacity is 0); JB_ELIMIT for seplen or termlen above JB_JOIN_MAXSEP, for
+ *    nbytes >= 2 GiB and for cap >= 2^32 - JB_JOIN_TILE.
+ * For spans produced by the library's own cuts, a sep and term that are valid UTF-8 give valid UTF-8
+ * output: every token is whole runes, ASCII, or a replaced invalid byte.
+ *
+ * jb_join_device.  The contract is jb_terms_device's: the call queues its kernels on `stream` and
+ * returns; it does not synchronise, allocate, read anything on the host or use the per-device
+ * workspace, and it holds the ctx's shared lock only while queuing, so it is safe from several threads
+ * and streams on one ctx.  d_start / d_end / d_doc_tok / d_ntok may be the ctx-owned results of any
+ * jb_cut_device* call or the caller's own arrays.  sep and term are host pointers and travel as kernel
+ * arguments.  d_work is a caller-owned device buffer of nwork >= jb_join_work_bytes(cap, ndocs) bytes,
+ * 8-byte aligned (JB_EINVAL otherwise, with nothing queued): 16 bytes per tile of JB_JOIN_TILE tokens,
+ * 16 per document and 16 per 256 documents.  Its contents mean nothing before or after the
+ * call; concurrent calls need buffers of their own.  The number of launches is 4, whatever cap, ndocs
+ * and the device data are: k_join_count (per tile the sum of len(key) + seplen, per document the
+ * offset of its first token inside its tile), k_join_scan (tiles and documents, one workgroup, no
+ * waits between workgroups), k_join_doc (out_doc_off, *d_nout, every terminator) and k_join_write
+ * (the keys and separators).
+ * The write kernel has two forms with identical results (JB_JOIN_STAGE, read at jb_open).  0, the
+ * plain form (the default): one lane per token, which finds its document by a search over doc_tok and
+ * copies its key byte by byte.  1, the staged form: the workgroup assembles a tile's output in LDS,
+ * 24 KiB at a time, and streams it out with 16-byte stores aligned to the output address; bytes that
+ * do not fill an aligned 16-byte unit (a tile's head and tail, the bytes next to a terminator) are
+ * stored one by one, never read-modify-written, and keys of JB_JOIN_LONG bytes or more bypass the
+ * staging and are copied by the whole workgroup.  The plain form is the faster one for the 139.5M
+ * plain-mode spans of the 1 GiB corpus (3.70 ms against 5.69 ms, beside 6.25 ms for the cut step;
+ * profiles/join_bench.json) and ships; the staged form stays selectable.
+ *
+ * jb_cut_batch_join: host text in, joined text out.  It runs the cut of `mode` (JB_MODE_CUT,
+ * JB_MODE_SEARCH, JB_MODE_FULL; hmm is ignored for JB_MODE_FULL), then the join, on ctx's first
+ * device through the buffers jb_keywords_batch keeps in the ctx (the output buffer and the work buffer
+ * are two more that only grow; concurrent calls take turns), and copies back nout, out_doc_off and the
+ * nout bytes only: no span reaches the host.  In full mode, when the span list exceeds the kept span
+ * arrays, it grows them and repeats the cut, as the host full-mode call does.  Requirements and errors
+ * are jb_keywords_batch's minus the vocabulary: a batch under 2 GiB (JB_ELIMIT), doc_off
+ * non-decreasing, and the cut's errors pass through, JB_EPANIC included; JB_EINVAL for an unknown
+ * mode.  out->text (out->nbytes bytes) and out->doc_off (out->ndocs + 1) are the library's: release
+ * them with jb_joined_free.  The text is page-locked host memory, so that the copy back runs at the
+ * link's rate; pinning costs more than the call, so jb_joined_free keeps the largest block it was
+ * handed (one per process, until a jb_close) and the next call takes it: release a result before
+ * asking for the next one, and only the first call of a size pays for the pinning.
+ *
+ * Deliberate differences from " ".join(cut(line)) on the reference:
+ *  - the separator and the terminator are the caller's, 0 to 8 bytes each;
+ *  - whitespace and non-Han blocks without an alnum byte are absent, because the reference drops
+ *    them (cutNonZh, tokenizer.go:289-310): the output is not the input with separators added. */
+#define JB_JOIN_MAXSEP 8
+#define JB_JOIN_TILE 2048 /* tokens per scan tile (one workgroup) */
+#define JB_JOIN_LONG 256  /* a key of this many bytes or more takes the cooperative copy path */
+#define JB_MODE_CUT 0
+#define JB_MODE_SEARCH 1
+#define JB_MODE_FULL 2
+/* Host only, no ctx: non-decreasing in both arguments, never 0. */
+size_t jb_join_work_bytes(uint64_t max_tokens, uint32_t ndocs);
+/* host only, no ctx, no GPU: the rule, and the reference the device kernels are pinned to */
+int jb_join(const uint8_t *text, uint64_t nbytes, const uint32_t *start, const uint32_t *end, const uint64_t *doc_tok,
+            uint64_t ntok, uint64_t cap, uint32_t ndocs, const uint8_t *sep, uint32_t seplen, const uint8_t *term,
+            uint32_t termlen, uint8_t *out, uint64_t out_cap, uint64_t *out_doc_off, uint64_t *nout);
+int jb_join_device(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uint32_t *d_start,
+                   const uint32_t *d_end, const uint64_t *d_doc_tok, const uint64_t *d_ntok, uint64_t cap,
+                   uint32_t ndocs, const uint8_t *sep, uint32_t seplen, const uint8_t *term, uint32_t termlen,
+                   void *stream, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_doc_off, uint64_t *d_nout,
+                   void *d_work, size_t nwork);
+typedef struct {
+    uint8_t *text;     /* nbytes bytes: the documents' outputs, one after the other */
+    uint64_t nbytes;
+    uint64_t *doc_off; /* ndocs + 1: document d's output is text[doc_off[d] .. doc_off[d+1]) */
+    uint32_t ndocs;
+} jb_joined;
+void jb_joined_free(jb_joined *j);
+int jb_cut_batch_join(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm, int mode,
+                      const uint8_t *sep, uint32_t seplen, const uint8_t *term, uint32_t termlen, jb_joined *out);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

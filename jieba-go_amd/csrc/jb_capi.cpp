@@ -8,9 +8,12 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <iterator>
 #include <type_traits>
 
 #include "jb_host.h"
+#include "jb_join.h"
 #include "jb_textrank.h"
 
 // ---------------------------------------------------------------------------
@@ -218,15 +221,21 @@ extern "C" int jb_open(const jb_config* cfg, jb_ctx** out) {
     return jb_open_image(img, &c, out);
 }
 
+namespace {
+void joined_drop_cache();  // (the page-locked block jb_joined_free keeps, below)
+}
+
 extern "C" void jb_close(jb_ctx* ctx) {
     if (!ctx) return;
+    joined_drop_cache();
     if (ctx->vocab && !ctx->devs.empty()) {  // (k_ids may still be queued on a caller's stream)
         (void)hipSetDevice(ctx->devs[0]->ordinal);
         (void)hipDeviceSynchronize();
         dfree(ctx->d_vslots);
         dfree(ctx->d_vpool);
     }
-    if ((ctx->kw_buf[0] || ctx->kw_buf[1] || ctx->kw_buf[2] || ctx->kw_buf[3]) && !ctx->devs.empty()) {
+    if (std::any_of(std::begin(ctx->kw_buf), std::end(ctx->kw_buf), [](void* p) { return p != nullptr; }) &&
+        !ctx->devs.empty()) {
         (void)hipSetDevice(ctx->devs[0]->ordinal);
         for (void* p : ctx->kw_buf) dfree(p);
     }
@@ -1303,4 +1312,214 @@ extern "C" int jb_textrank_batch(jb_ctx* ctx, const uint8_t* text, const uint64_
         HIPCHK(hipMemcpyAsync(kw_n, dkw + 2 * nrec, (size_t)ndocs * 4, hipMemcpyDeviceToHost, c.st));
         return JB_OK;
     });
+}
+
+// ---------------------------------------------------------------------------
+// joined text (jb_join.hip; the host rule, jb_join, is jb_join.cpp)
+// ---------------------------------------------------------------------------
+static_assert(JB_JOIN_TILE == kJoinTile && JB_JOIN_LONG == kJoinLong && JB_JOIN_MAXSEP == kJoinMaxSep,
+              "the header's constants are the kernels'");
+
+extern "C" size_t jb_join_work_bytes(uint64_t max_tokens, uint32_t ndocs) { return join_work_bytes(max_tokens, ndocs); }
+
+extern "C" int jb_join_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
+                              const uint32_t* d_end, const uint64_t* d_doc_tok, const uint64_t* d_ntok, uint64_t cap,
+                              uint32_t ndocs, const uint8_t* sep, uint32_t seplen, const uint8_t* term, uint32_t termlen,
+                              void* stream, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_doc_off, uint64_t* d_nout,
+                              void* d_work, size_t nwork) {
+    // (the limits come first: they need no ctx)
+    if (const int rc = join_args("jb_join_device", nbytes, cap, sep, seplen, term, termlen)) return rc;
+    if (!ctx || !d_text || !d_doc_tok || !d_ntok || !d_out_doc_off || !d_nout || !d_work || (cap && (!d_start || !d_end)) ||
+        (out_cap && !d_out))
+        return fail(JB_EINVAL, "jb_join_device: null argument");
+    if (((uintptr_t)d_work & 7u) != 0) return fail(JB_EINVAL, "jb_join_device: d_work must be 8-byte aligned");
+    const size_t need = join_work_bytes(cap, ndocs);
+    if (nwork < need)
+        return fail(JB_EINVAL, "jb_join_device: a work buffer of %llu bytes, jb_join_work_bytes asks for %llu",
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    const bool staged = d->lc.join_stage != 0;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_join(d_text, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, sep, seplen, term, termlen, staged,
+                        d_out, out_cap, d_out_doc_off, d_nout, d_work, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_join(d_text, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, sep, seplen, term, termlen, staged, d_out,
+                    out_cap, d_out_doc_off, d_nout, d_work, s, nullptr));
+    return JB_OK;
+}
+
+// jb_joined::text is page-locked, so that the copy back runs at the link's rate and touches no fresh page.
+// Pinning a gigabyte costs far more than the whole call, so jb_joined_free keeps the largest block it was
+// handed (one per process) and the next jb_cut_batch_join takes it; jb_close lets it go.  A block starts
+// with a header that holds its capacity.
+namespace {
+constexpr size_t kJoinedHdr = 64;
+std::mutex g_joined_mu;
+uint8_t* g_joined_block = nullptr;  // (under g_joined_mu)
+size_t g_joined_cap = 0;
+
+int joined_alloc(uint64_t nbytes, uint8_t** text) {
+    uint8_t* b = nullptr;
+    {
+        std::lock_guard<std::mutex> g(g_joined_mu);
+        if (g_joined_block && g_joined_cap >= nbytes) {
+            b = g_joined_block;
+            g_joined_block = nullptr;
+        }
+    }
+    if (!b) {
+        HIPCHK(hipHostMalloc(&b, kJoinedHdr + std::max<uint64_t>(nbytes, 1), hipHostMallocDefault));
+        *(uint64_t*)b = nbytes;
+    }
+    *text = b + kJoinedHdr;
+    return JB_OK;
+}
+
+void joined_release(uint8_t* text) {
+    if (!text) return;
+    uint8_t* b = text - kJoinedHdr;
+    {
+        std::lock_guard<std::mutex> g(g_joined_mu);
+        if (!g_joined_block || g_joined_cap < *(uint64_t*)b) {
+            std::swap(b, g_joined_block);
+            g_joined_cap = *(uint64_t*)g_joined_block;
+        }
+    }
+    hfree(b);  // (the smaller of the two, or nothing)
+}
+
+void joined_drop_cache() {
+    uint8_t* b;
+    {
+        std::lock_guard<std::mutex> g(g_joined_mu);
+        b = g_joined_block;
+        g_joined_block = nullptr;
+        g_joined_cap = 0;
+    }
+    hfree(b);
+}
+}  // namespace
+
+extern "C" void jb_joined_free(jb_joined* j) {
+    if (!j) return;
+    joined_release(j->text);
+    free(j->doc_off);
+    memset(j, 0, sizeof *j);
+}
+
+// Host text in, joined text out: the cut of `mode` into the ctx's buffers [0] (and, when full mode's list
+// is longer than the batch has bytes, [1]), jb_join_device into [4] with its work buffer and offsets in
+// [5], and nout, the offsets and the nout bytes back.  The join runs again when its output was larger
+// than [4] had room for.
+extern "C" int jb_cut_batch_join(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                                 int mode, const uint8_t* sep, uint32_t seplen, const uint8_t* term, uint32_t termlen,
+                                 jb_joined* out) {
+    const char* who = "jb_cut_batch_join";
+    if (!ctx || !doc_off || !out) return fail(JB_EINVAL, "%s: null argument", who);
+    memset(out, 0, sizeof *out);
+    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
+        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
+    for (uint32_t k = 0; k < ndocs; k++)
+        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
+    const uint64_t nb = doc_off[ndocs] - doc_off[0];
+    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
+    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
+    if (const int rc = join_args(who, nb, 0, sep, seplen, term, termlen)) return rc;
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    out->doc_off = (uint64_t*)calloc((size_t)ndocs + 1, 8);
+    if (!out->doc_off) return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
+    out->ndocs = ndocs;
+    if (ndocs == 0) return JB_OK;
+    HIPCHK(hipSetDevice(ordinal));
+    std::vector<uint64_t> rel;
+    try {
+        rel.resize((size_t)ndocs + 1);
+    } catch (const std::bad_alloc&) {
+        jb_joined_free(out);
+        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
+    }
+    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
+    uint64_t cap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
+    std::lock_guard<std::mutex> kg(ctx->kw_mu);
+    hipStream_t st = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
+        Arena a;
+        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * cap * 4), &a))) return rc;
+        uint8_t* dt = (uint8_t*)a.take(nb + 64);
+        uint64_t* doff = (uint64_t*)a.take(ndoc8);
+        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
+        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the span count, the output's byte count)
+        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
+        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
+        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+        uint64_t ntok = 0;
+        for (int pass = 0;; pass++) {
+            if (mode == JB_MODE_CUT)
+                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
+            else if (mode == JB_MODE_SEARCH)
+                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
+            else
+                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + cap, cap, dtok, dcnt);
+            if (rc) return rc;
+            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
+            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
+            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > cap && pass == 0) {
+                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
+                cap = ntok;
+                Arena b;
+                if ((rc = kw_arena(ctx, 1, r256(2 * cap * 4), &b))) return rc;
+                dse = (uint32_t*)b.take(2 * cap * 4);
+                continue;
+            }
+            if (rc) return rc;
+            break;
+        }
+        if (const int r = join_args(who, nb, cap, sep, seplen, term, termlen)) return r;
+        const size_t nwork = join_work_bytes(cap, ndocs);
+        Arena w;
+        if ((rc = kw_arena(ctx, 5, r256(nwork) + r256(ndoc8), &w))) return rc;
+        void* dwork = w.take(nwork);
+        uint64_t* dooff = (uint64_t*)w.take(ndoc8);
+        // a first guess at the output's size: the text (plain mode without replaced bytes gives less), a
+        // separator per token and a terminator per document
+        uint64_t ocap = std::max<uint64_t>(ctx->kw_cap[4], nb + std::min(ntok, cap) * seplen + (uint64_t)ndocs * termlen + 256);
+        uint64_t nout = 0;
+        for (int pass = 0; pass < 2; pass++) {
+            Arena o;
+            if ((rc = kw_arena(ctx, 4, ocap, &o))) return rc;
+            if ((rc = jb_join_device(ctx, dt, nb, dse, dse + cap, dtok, dcnt, cap, ndocs, sep, seplen, term, termlen, st,
+                                     o.p, ocap, dooff, dcnt + 1, dwork, nwork)))
+                return rc;
+            HIPCHK(hipMemcpyAsync(&nout, dcnt + 1, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (nout <= ocap) break;
+            ocap = nout;  // (replaced bytes or overlapping spans: the complete size is known now)
+        }
+        if ((rc = joined_alloc(nout, &out->text))) return rc;
+        out->nbytes = nout;
+        if (nout) HIPCHK(hipMemcpyAsync(out->text, ctx->kw_buf[4], nout, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(out->doc_off, dooff, ndoc8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return JB_OK;
+    };
+    const int rc = run();
+    if (st) {
+        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
+        (void)hipStreamDestroy(st);
+    }
+    if (rc) jb_joined_free(out);
+    return rc;
 }

@@ -243,6 +243,7 @@ static const uint64_t kMaxPiece = 1ull << 30;  // (a piece of several documents;
 //   JB_STAMPS    (STAMPS=1 builds only) per-wave phase clocks to stderr
 //   JB_DF_COMBINE jb_df_device's kernel: 1 k_df_combine (default), 0 k_df
 //   JB_TR_WINDOW jb_textrank_device's push kernel: 1 k_tr_push_win (default), 0 k_tr_push
+//   JB_JOIN_STAGE jb_join_device's write kernel: 0 the plain form (default), 1 the staged form
 static int init_launch_cfg(Device* d) {
     LaunchCfg& lc = d->lc;
     lc.zh_waves = d->ncu * std::max(zh_waves_per_cu(true, false), zh_waves_per_cu(false, false));
@@ -307,6 +308,9 @@ static int init_launch_cfg(Device* d) {
     const int tw = env_int("JB_TR_WINDOW", 1);
     if (tw < 0 || tw > 1) return fail(JB_EINVAL, "JB_TR_WINDOW=%d: want 0 or 1", tw);
     lc.tr_window = (uint32_t)tw;
+    const int js = env_int("JB_JOIN_STAGE", 0);
+    if (js < 0 || js > 1) return fail(JB_EINVAL, "JB_JOIN_STAGE=%d: want 0 or 1", js);
+    lc.join_stage = (uint32_t)js;
     return JB_OK;
 }
 

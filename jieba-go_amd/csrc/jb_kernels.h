@@ -126,6 +126,7 @@ enum KernelId {
     K_TERMS_SORT, K_TERMS_MERGE, K_TERMS_COUNT, K_TERMS_SCAN, K_TERMS_WRITE, K_KEYWORDS,
     K_DF, K_IDF,
     K_TR_INIT, K_TR_SETUP, K_TR_COUNT, K_TR_STEP, K_TR_PUSH, K_TR_FINAL,
+    K_JOIN_COUNT, K_JOIN_SCAN, K_JOIN_DOC, K_JOIN_WRITE,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -163,6 +164,8 @@ struct LaunchCfg {
     uint32_t df_combine;     // jb_df_device: 1 k_df_combine, 0 k_df (JB_DF_COMBINE; results do not depend on it)
     uint32_t tr_window;      // jb_textrank_device's push: 1 k_tr_push_win, 0 k_tr_push (JB_TR_WINDOW; results do not
                              // depend on it)
+    uint32_t join_stage;     // jb_join_device's write: 0 the plain form (default), 1 the staged form (JB_JOIN_STAGE; results do
+                             // not depend on it)
 };
 
 // k_zh's group split: g1 groups of grp bytes, then groups of *sgrp bytes to the end.
@@ -293,6 +296,24 @@ hipError_t run_textrank(const uint32_t* d_ids, uint64_t ids_cap, const uint64_t*
                         const uint8_t* d_keep, uint32_t nkeep, uint32_t span, uint32_t iters, uint32_t topk,
                         bool window, uint32_t* d_kw_id, float* d_kw_score, uint32_t* d_kw_n, void* d_work,
                         hipStream_t stream, KernelTimer* timer);
+
+// Joined text (jb_join_device; jb_join.hip).  Tile = kJoinTile consecutive tokens, one workgroup each.
+constexpr uint32_t kJoinTile = 2048;    // JB_JOIN_TILE: 256 threads x 8 tokens
+constexpr uint32_t kJoinLong = 256;     // JB_JOIN_LONG: keys from here on are copied by the whole workgroup
+constexpr uint32_t kJoinStage = 24576;  // bytes of a tile's output staged in LDS at a time
+constexpr uint32_t kJoinMaxSep = 8;     // JB_JOIN_MAXSEP: separator and terminator travel as one u64 each
+// Bytes of the work buffer run_join needs: 16 per tile, 16 per document and 16 per 256 documents.  Host only.
+size_t join_work_bytes(uint64_t max_tokens, uint32_t ndocs);
+// Enqueue the four join kernels on `stream`: the keys of the tokens k < min(*d_ntok, cap), the separators
+// between a document's tokens and a terminator per document, into d_out below out_cap; d_out_doc_off
+// (ndocs + 1) and *d_nout describe the complete output.  sep / term are host pointers (seplen, termlen <=
+// kJoinMaxSep).  `staged` chooses the write kernel's form.  d_work holds join_work_bytes(cap, ndocs) bytes,
+// 8-byte aligned.  (K_JOIN_WRITE times whichever form runs.)
+hipError_t run_join(const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start, const uint32_t* d_end,
+                    const uint64_t* d_doc_tok, const uint64_t* d_ntok, uint64_t cap, uint32_t ndocs, const uint8_t* sep,
+                    uint32_t seplen, const uint8_t* term, uint32_t termlen, bool staged, uint8_t* d_out,
+                    uint64_t out_cap, uint64_t* d_out_doc_off, uint64_t* d_nout, void* d_work, hipStream_t stream,
+                    KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

@@ -481,6 +481,54 @@ func (t *Tokenizer) TextRank(docs []string, keep []byte, topK, span, iters int, 
 	return out
 }
 
+// CutJoin is strings.Join(Cut(text), sep) for every text of a batch, with the cut of mode (C.JB_MODE_CUT,
+// C.JB_MODE_SEARCH, C.JB_MODE_FULL; full mode ignores useHmm) and the join both on the GPU: only the joined
+// bytes come back, no span and no token.  sep holds at most JB_JOIN_MAXSEP (8) bytes.  An invalid byte comes
+// out as "�"; whitespace and non-Han blocks without an alnum byte are absent, as in Cut.  With mini_dict.txt,
+// CutJoin([]string{"这一刹那", ""}, " ", false, C.JB_MODE_SEARCH) is {"这 一刹 刹那 一刹那", ""}
+// (tests/c_abi_join.c).  Never returns nil.
+func (t *Tokenizer) CutJoin(texts []string, sep string, useHmm bool, mode int) []string {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	out := make([]string, len(texts))
+	if len(texts) == 0 {
+		return out
+	}
+	if len(sep) > C.JB_JOIN_MAXSEP {
+		panic("jiebahip: CutJoin separator longer than JB_JOIN_MAXSEP")
+	}
+	off := make([]uint64, len(texts)+1)
+	total := 0
+	for i, d := range texts {
+		total += len(d)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, d := range texts {
+		b = append(b, d...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	sb := append([]byte(sep), 0)
+	var j C.jb_joined
+	rc := C.jb_cut_batch_join(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+		C.uint32_t(len(texts)), hmm, C.int(mode), (*C.uint8_t)(unsafe.Pointer(&sb[0])), C.uint32_t(len(sep)), nil, 0, &j)
+	if rc != C.JB_OK {
+		// JB_EINVAL: an unknown mode; JB_EPANIC: the reference panics on this input
+		panic("jiebahip: " + lastError())
+	}
+	defer C.jb_joined_free(&j)
+	joined := C.GoBytes(unsafe.Pointer(j.text), C.int(j.nbytes))
+	ooff := unsafe.Slice((*uint64)(unsafe.Pointer(j.doc_off)), len(texts)+1)
+	for d := range texts {
+		out[d] = string(joined[ooff[d]:ooff[d+1]])
+	}
+	return out
+}
+
 // IdfFit is the result of FitIdf: per id of the attached vocabulary its IDF weight and the number
 // of documents it occurs in, and the number of documents fitted on.
 type IdfFit struct {

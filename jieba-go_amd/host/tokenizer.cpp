@@ -179,6 +179,25 @@ std::vector<std::vector<Tokenizer::Rank>> Tokenizer::TextRank(const std::vector<
     return out;
 }
 
+std::vector<std::string> Tokenizer::CutJoin(const std::vector<std::string>& docs, const std::string& sep, bool useHmm,
+                                            int mode) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& d : docs) {
+        all += d;
+        off.push_back(all.size());
+    }
+    jb_joined j;
+    check(jb_cut_batch_join(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)docs.size(), useHmm ? 1 : 0, mode,
+                            (const uint8_t*)sep.data(), (uint32_t)sep.size(), nullptr, 0, &j));
+    std::vector<std::string> out;
+    out.reserve(docs.size());
+    for (size_t d = 0; d < docs.size(); d++)
+        out.emplace_back((const char*)j.text + j.doc_off[d], (size_t)(j.doc_off[d + 1] - j.doc_off[d]));
+    jb_joined_free(&j);
+    return out;
+}
+
 std::vector<std::string> Tokenizer::CutParallel(const std::string& text, bool hmm, int, bool) {
     return Cut(text, hmm);
 }

@@ -98,6 +98,12 @@ public:
     std::vector<std::vector<Rank>> TextRank(const std::vector<std::string>& docs, const std::vector<uint8_t>& keep,
                                             uint32_t topK = 20, uint32_t span = 5, uint32_t iters = 10,
                                             bool useHmm = true);
+    // Joined text (jb_cut_batch_join in jiebahip.h): sep.join(cut(doc)) for every document of a batch, the
+    // cut of `mode` (JB_MODE_CUT, JB_MODE_SEARCH, JB_MODE_FULL; full mode ignores useHmm) and the join both
+    // on the GPU; only the joined bytes come back.  An invalid byte comes out as U+FFFD; whitespace and
+    // non-Han blocks without an alnum byte are absent, as in Cut.  sep holds at most JB_JOIN_MAXSEP bytes.
+    std::vector<std::string> CutJoin(const std::vector<std::string>& docs, const std::string& sep = " ",
+                                     bool useHmm = true, int mode = JB_MODE_CUT);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

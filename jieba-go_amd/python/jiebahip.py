@@ -28,6 +28,11 @@ JB_TERMS_TILE = 4096  # tokens per sort tile of jb_terms_device
 JB_DF_NOMAX = 0xFFFFFFFF  # max_df of the idf calls: no upper bound
 JB_TR_MAXSPAN = 32  # the largest span of the textrank calls
 JB_TR_MAXITER = 100  # the largest iters of the textrank calls
+JB_JOIN_MAXSEP = 8  # the longest separator and terminator of the join calls, bytes
+JB_JOIN_TILE = 2048  # tokens per scan tile of jb_join_device
+JB_JOIN_LONG = 256  # a key of this many bytes or more takes jb_join_device's cooperative copy
+JB_MODE_CUT, JB_MODE_SEARCH, JB_MODE_FULL = 0, 1, 2
+_MODES = {"cut": JB_MODE_CUT, "search": JB_MODE_SEARCH, "full": JB_MODE_FULL}
 
 # Every symbol include/jiebahip.h declares.
 EXPORTS = [
@@ -45,6 +50,7 @@ EXPORTS = [
     "jb_terms_work_bytes", "jb_terms_device", "jb_keywords_device", "jb_keywords_batch",
     "jb_df_device", "jb_idf_device", "jb_idf", "jb_df_batch",
     "jb_textrank_work_bytes", "jb_textrank", "jb_textrank_device", "jb_textrank_batch",
+    "jb_join_work_bytes", "jb_join", "jb_join_device", "jb_joined_free", "jb_cut_batch_join",
 ]
 
 
@@ -66,6 +72,22 @@ class jb_config(C.Structure):
 class jb_stats(C.Structure):
     _fields_ = [("tokens", C.c_uint64), ("blocks", C.c_uint64), ("zh_blocks", C.c_uint64),
                 ("long_blocks", C.c_uint64), ("viterbi_ties", C.c_uint64)]
+
+
+class jb_joined(C.Structure):
+    _fields_ = [("text", C.POINTER(C.c_uint8)), ("nbytes", C.c_uint64), ("doc_off", C.POINTER(C.c_uint64)),
+                ("ndocs", C.c_uint32)]
+
+
+class _Joined:
+    """Owner of a jb_joined: jb_joined_free when the last array over its text goes away."""
+
+    def __init__(self):
+        self.j = jb_joined()
+
+    def __del__(self):
+        if _lib is not None:
+            _lib.jb_joined_free(C.byref(self.j))
 
 
 class jb_spans(C.Structure):
@@ -182,6 +204,16 @@ def lib():
                                          C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t]
         L.jb_textrank_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                         C.c_uint32, vp, vp, vp]
+        L.jb_join_work_bytes.restype = C.c_size_t
+        L.jb_join_work_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        L.jb_join.argtypes = [vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp,
+                              C.c_uint32, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
+        L.jb_join_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp,
+                                     C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, C.c_size_t]
+        L.jb_joined_free.argtypes = [C.POINTER(jb_joined)]
+        L.jb_joined_free.restype = None
+        L.jb_cut_batch_join.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint32, vp, C.c_uint32,
+                                        C.POINTER(jb_joined)]
         _lib = L
     return _lib
 
@@ -758,6 +790,51 @@ class Tokenizer:
         return [[(int(ki[d, r]) if keys is None else keys[int(ki[d, r])], float(ks[d, r])) for r in range(int(kn[d]))]
                 for d in range(len(docs))]
 
+    # -- joined text -------------------------------------------------------
+    def join_device(self, d_text_ptr, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, sep, term, d_out, out_cap,
+                    d_out_doc_off, d_nout, d_work, nwork, stream_ptr=0):
+        """jb_join_device over raw device pointers: per document its keys joined by sep and ended by term (host
+        bytes, up to JB_JOIN_MAXSEP each) into d_out below out_cap; d_out_doc_off (u64[ndocs + 1]) and *d_nout
+        describe the complete output.  d_work: join_work_bytes(cap, ndocs) bytes."""
+        sep, term = _b(sep), _b(term)
+        _check(lib().jb_join_device(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_start), C.c_void_p(d_end),
+                                    C.c_void_p(d_doc_tok), C.c_void_p(d_ntok), cap, ndocs, sep, len(sep), term,
+                                    len(term), C.c_void_p(stream_ptr), C.c_void_p(d_out), out_cap,
+                                    C.c_void_p(d_out_doc_off), C.c_void_p(d_nout), C.c_void_p(d_work), nwork))
+
+    def cut_batch_join(self, buf, doc_off, hmm, mode="cut", sep=b" ", term=b"\n"):
+        """jb_cut_batch_join: host batch -> (joined text uint8[nout], out_doc_off u64[ndocs + 1]); mode "cut",
+        "search" or "full" (or a JB_MODE_* value; full mode ignores hmm)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        nd = len(doc_off) - 1
+        sep, term = _b(sep), _b(term)
+        if isinstance(mode, str):
+            if mode not in _MODES:
+                raise ValueError(f"mode {mode!r}: one of 'cut', 'search', 'full'")
+            mode = _MODES[mode]
+        j = _Joined()
+        _check(lib().jb_cut_batch_join(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, int(hmm), int(mode), sep,
+                                       len(sep), term, len(term), C.byref(j.j)))
+        off = np.ctypeslib.as_array(j.j.doc_off, (nd + 1,)).copy()
+        if j.j.nbytes == 0:
+            return np.empty(0, np.uint8), off
+        # the library's buffer itself, not a copy: the array keeps `j` alive, and `j` frees the buffer
+        j.__array_interface__ = {"shape": (j.j.nbytes,), "typestr": "|u1", "version": 3,
+                                 "data": (C.cast(j.j.text, C.c_void_p).value, False)}
+        return np.asarray(j), off
+
+    def cut_join(self, texts, sep=" ", term="", hmm=True, mode="cut"):
+        """sep.join(cut(text)) + term for every text (str / bytes) in one batch: a list of str, one per text."""
+        if not texts:
+            return []
+        docs = [_b(t) for t in texts]
+        buf = np.frombuffer(b"".join(docs) + b"\0", np.uint8)
+        off = np.cumsum([0] + [len(d) for d in docs]).astype(np.uint64)
+        out, ooff = self.cut_batch_join(buf, off, hmm, mode, sep, term)
+        raw = out.tobytes()
+        return [raw[int(ooff[d]):int(ooff[d + 1])].decode("utf-8") for d in range(len(docs))]
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -807,7 +884,7 @@ class Tokenizer:
         _check(lib().jb_profile_reset(self.h))
 
     def profile_read(self):
-        cap = 64  # (more than the library's kernels: 40)
+        cap = 64  # (more than the library's kernels: 44)
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         n = (C.c_uint64 * cap)()
@@ -913,6 +990,39 @@ def idf(df, ndocs, min_df=1, max_df=None, keep=None):
                         JB_DF_NOMAX if max_df is None else max_df, k.ctypes.data if k is not None and len(k) else None,
                         w.ctypes.data if len(w) else None))
     return w
+
+
+def join_work_bytes(max_tokens, ndocs):
+    """jb_join_work_bytes: bytes of the work buffer jb_join_device needs (host only)."""
+    return lib().jb_join_work_bytes(max_tokens, ndocs)
+
+
+def join(text, starts, ends, doc_tok, sep=b" ", term=b"\n", ntok=None, cap=None, nbytes=None, out_cap=None):
+    """jb_join (host only): the joined-text rule of jiebahip.h on host arrays (text bytes or a uint8 array, u32
+    spans, u64 doc_tok).  Returns (out uint8[out_cap], out_doc_off u64[ndocs + 1], nout); without out_cap the
+    output array holds exactly the nout bytes."""
+    t = np.ascontiguousarray(text, np.uint8) if isinstance(text, np.ndarray) else np.frombuffer(_b(text), np.uint8)
+    s = np.ascontiguousarray(starts, np.uint32)
+    e = np.ascontiguousarray(ends, np.uint32)
+    d = np.ascontiguousarray(doc_tok, np.uint64)
+    sep, term = _b(sep), _b(term)
+    nd = len(d) - 1
+    cap = len(s) if cap is None else cap
+    ntok = len(s) if ntok is None else ntok
+    nbytes = len(t) if nbytes is None else nbytes
+    off = np.empty(nd + 1, np.uint64)
+    n = C.c_uint64()
+
+    def call(out, ocap):
+        _check(lib().jb_join(t.ctypes.data if len(t) else None, nbytes, s.ctypes.data if len(s) else None,
+                             e.ctypes.data if len(e) else None, d.ctypes.data, ntok, cap, nd, sep, len(sep), term,
+                             len(term), out.ctypes.data if ocap else None, ocap, off.ctypes.data, C.byref(n)))
+    if out_cap is None:
+        call(np.empty(1, np.uint8), 0)
+        out_cap = n.value
+    out = np.empty(max(out_cap, 1), np.uint8)
+    call(out, out_cap)
+    return out[:out_cap], off, n.value
 
 
 def textrank_work_bytes(max_tokens, max_terms, ndocs):
