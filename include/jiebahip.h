@@ -648,6 +648,96 @@ void jb_joined_free(jb_joined *j);
 int jb_cut_batch_join(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm, int mode,
                       const uint8_t *sep, uint32_t seplen, const uint8_t *term, uint32_t termlen, jb_joined *out);
 
+/* ---- character offsets (jieba's tokenize(): (word, start, end) in characters) -----------------
+ * Every cut returns byte ranges of the UTF-8 input.  A Python caller holds str and slices by code
+ * point; Lucene, Elasticsearch, Java, C# and JavaScript index text in UTF-16 code units.  These
+ * calls turn a span list of any mode into spans in one of those units, per document, on the device:
+ * a prefix count over the text and three lookups per token (the document's start, the span's start and its end).
+ *
+ * The rule.  jb_charspans (host only, no ctx, no GPU) and jb_charspans_device agree to the bit.
+ *  - Runes.  Document d is text[doc_off[d] .. doc_off[d+1]).  It is decoded from its first byte by
+ *    Go's utf8.DecodeRune with the document's end as the limit: a sequence cut short by the end of
+ *    its document is invalid, and its lead byte is (U+FFFD, 1).  That gives the document's rune
+ *    starts, each with a width and a value.
+ *  - Units.  units(i) of a rune start i is 1 under JB_UNIT_RUNE; under JB_UNIT_UTF16 it is 2 for a
+ *    valid rune >= U+10000 and 1 otherwise.  An invalid byte counts 1, as U+FFFD.
+ *  - Position.  pos_d(p), doc_off[d] <= p <= doc_off[d+1], is the sum of units(i) over the rune
+ *    starts i of document d with i < p.  A p inside a rune is allowed (a caller's own spans may have
+ *    one): the rune that contains it is counted.
+ *  - Tokens.  Token k exists iff k < min(ntok, cap), and belongs to document d iff doc_tok[d] <= k <
+ *    doc_tok[d+1] (doc_tok u64[ndocs + 1]; the clamps of jb_join).  doc_tok must be non-decreasing for
+ *    that; if it is not, every token is still written, some of them as JB_CHAR_NONE.  A token before
+ *    doc_tok[0] or at or past doc_tok[ndocs] belongs to no document.
+ *  - Per token: cstart[k] = pos_d(start[k]) and cend[k] = pos_d(end[k]) when doc_off[d] <= start[k] <=
+ *    end[k] <= doc_off[d+1]; otherwise both are JB_CHAR_NONE (a malformed span, a span that leaves its
+ *    document, a token of no document).  The spans, doc_tok and ntok are not trusted: no text byte
+ *    outside [0, nbytes + 64) is read, every k < min(ntok, cap) is written in both arrays, and nothing
+ *    else is written.
+ *  - Per document: doc_units[d] = pos_d(doc_off[d+1]), the document's length in the unit (len(s) in
+ *    Python, s.length() in Java), for all ndocs documents.
+ *  - Offsets are per document, as jieba's tokenize gives them for one string.
+ *  - In place: cstart may be the array start, and cend the array end; each token's two inputs are read
+ *    before its two outputs are written.
+ *  - Limits: JB_EINVAL for a null pointer (arrays of capacity 0 may be NULL) and for an unknown unit;
+ *    the host form also rejects a decreasing doc_off, doc_off[0] != 0 and doc_off[ndocs] != nbytes.
+ *    JB_ELIMIT for nbytes >= 2 GiB and for cap >= 2^32 - JB_JOIN_TILE.
+ *
+ * jb_charspans_device.  The contract is jb_join_device's: the call queues its kernels on `stream` and
+ * returns; it does not synchronise, allocate, read anything on the host or use the per-device
+ * workspace, and it holds the ctx's shared lock only while queuing.  d_text has nbytes bytes plus 64
+ * readable padding bytes and is 4-byte aligned, as for jb_ids_device.  d_doc_off is the array the cut
+ * was given and is trusted, as jb_cut_device trusts it.  d_start / d_end / d_doc_tok / d_ntok may be
+ * the ctx-owned results of any jb_cut_device* call or the caller's own arrays.  d_work is a
+ * caller-owned device buffer of nwork >= jb_charspans_work_bytes(nbytes, ndocs) bytes, 8-byte aligned
+ * (JB_EINVAL otherwise, with nothing queued): per tile of JB_CHARSPANS_TILE text bytes 64 words of two
+ * bitmaps (16 bytes) and a prefix (4 bytes) each, and 8 bytes of sums, about 0.31 bytes per text byte;
+ * today it does not depend on ndocs.  Its contents mean nothing before or after the call; concurrent
+ * calls need buffers of their own.  Nothing is written outside the outputs and d_work.
+ * The number of launches is 3, whatever nbytes, ndocs, cap and the device data are: k_cs_class (per
+ * tile the bitmap of rune starts, under JB_UNIT_UTF16 the bitmap of the starts that count 2, the unit
+ * count before each 64-byte word inside the tile and the tile's sum; the document boundaries of a tile
+ * come from two searches over d_doc_off), k_cs_scan (the tile sums, one workgroup, no waits between
+ * workgroups) and k_cs_lookup (one lane per token: its document by a search over d_doc_tok, then
+ * three positions; one lane per document writes doc_units).
+ * Measured on the 1 GiB corpus (tools/charspans_bench.py, profiles/charspans_bench.json): the 139.5M
+ * plain-mode spans take 2.61 ms in runes and 2.83 ms in UTF-16 units, beside 6.24 ms for the cut step
+ * and 3.71 ms for jb_join_device in the same run; search mode's 223.7M spans 3.08 and 3.41 ms, full
+ * mode's 320.4M spans 3.53 and 3.96 ms.  k_cs_class, which reads the text, takes 1.60 ms of each and
+ * k_cs_scan 0.15 ms; the rest is the lookup, which grows with the span count.
+ *
+ * jb_cut_batch_charspans: host text in, character spans out, into caller-owned arrays (cstart, cend:
+ * cap entries; doc_tok: ndocs + 1; doc_units: ndocs).  It runs the cut of `mode` (JB_MODE_CUT,
+ * JB_MODE_SEARCH, JB_MODE_FULL; hmm is ignored for JB_MODE_FULL) and the conversion, in place on the
+ * span arrays, on ctx's first device through the buffers jb_keywords_batch keeps in the ctx (the work
+ * buffer is one more that only grows; concurrent calls take turns), and copies back the count, the two
+ * u32 arrays, doc_tok and doc_units: no byte span reaches the host.  It does not use the multi-device
+ * piece pipeline, because pieces may split a document and the offsets are per document.  The cap
+ * protocol is jb_cut_batch_into32's: *ntokens is always the complete count, and JB_ELIMIT with
+ * *ntokens set says that the arrays are too small (nothing but *ntokens is then written, and the
+ * count is compared with cap after the first cut, before anything is grown or repeated).  In full
+ * mode, when the span list fits cap but exceeds the kept span arrays, it grows them and repeats the
+ * cut.  Other
+ * requirements and errors are jb_cut_batch_join's: a batch under 2 GiB (JB_ELIMIT), doc_off
+ * non-decreasing, JB_EINVAL for an unknown mode or unit, and the cut's errors pass through, JB_EPANIC
+ * included. */
+#define JB_UNIT_RUNE 0
+#define JB_UNIT_UTF16 1
+#define JB_CHAR_NONE 0xFFFFFFFFu
+#define JB_CHARSPANS_TILE 4096 /* text bytes per tile (one workgroup) */
+/* Host only, no ctx: non-decreasing in both arguments, never 0. */
+size_t jb_charspans_work_bytes(uint64_t nbytes, uint32_t ndocs);
+/* host only, no ctx, no GPU: the rule, and the reference the device kernels are pinned to */
+int jb_charspans(const uint8_t *text, uint64_t nbytes, const uint64_t *doc_off, uint32_t ndocs, const uint32_t *start,
+                 const uint32_t *end, const uint64_t *doc_tok, uint64_t ntok, uint64_t cap, int unit, uint32_t *cstart,
+                 uint32_t *cend, uint32_t *doc_units);
+int jb_charspans_device(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uint64_t *d_doc_off, uint32_t ndocs,
+                        const uint32_t *d_start, const uint32_t *d_end, const uint64_t *d_doc_tok,
+                        const uint64_t *d_ntok, uint64_t cap, int unit, void *stream, uint32_t *d_cstart,
+                        uint32_t *d_cend, uint32_t *d_doc_units, void *d_work, size_t nwork);
+int jb_cut_batch_charspans(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm, int mode,
+                           int unit, uint32_t *cstart, uint32_t *cend, uint64_t cap, uint64_t *doc_tok,
+                           uint64_t *ntokens, uint32_t *doc_units);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

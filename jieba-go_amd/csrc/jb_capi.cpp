@@ -12,6 +12,7 @@
 #include <iterator>
 #include <type_traits>
 
+#include "jb_charspans.h"
 #include "jb_host.h"
 #include "jb_join.h"
 #include "jb_textrank.h"
@@ -1521,5 +1522,150 @@ extern "C" int jb_cut_batch_join(jb_ctx* ctx, const uint8_t* text, const uint64_
         (void)hipStreamDestroy(st);
     }
     if (rc) jb_joined_free(out);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// character offsets (jb_charspans.hip; the host rule, jb_charspans, is jb_charspans.cpp)
+// ---------------------------------------------------------------------------
+static_assert(JB_CHARSPANS_TILE == kCsTile, "the header's constant is the kernels'");
+
+extern "C" size_t jb_charspans_work_bytes(uint64_t nbytes, uint32_t ndocs) { return charspans_work_bytes(nbytes, ndocs); }
+
+extern "C" int jb_charspans_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint64_t* d_doc_off,
+                                   uint32_t ndocs, const uint32_t* d_start, const uint32_t* d_end,
+                                   const uint64_t* d_doc_tok, const uint64_t* d_ntok, uint64_t cap, int unit, void* stream,
+                                   uint32_t* d_cstart, uint32_t* d_cend, uint32_t* d_doc_units, void* d_work,
+                                   size_t nwork) {
+    // (the limits come first: they need no ctx)
+    if (const int rc = charspans_args("jb_charspans_device", nbytes, cap, unit)) return rc;
+    if (!ctx || !d_text || !d_doc_off || !d_doc_tok || !d_ntok || !d_work ||
+        (cap && (!d_start || !d_end || !d_cstart || !d_cend)) || (ndocs && !d_doc_units))
+        return fail(JB_EINVAL, "jb_charspans_device: null argument");
+    if (((uintptr_t)d_work & 7u) != 0) return fail(JB_EINVAL, "jb_charspans_device: d_work must be 8-byte aligned");
+    const size_t need = charspans_work_bytes(nbytes, ndocs);
+    if (nwork < need)
+        return fail(JB_EINVAL, "jb_charspans_device: a work buffer of %llu bytes, jb_charspans_work_bytes asks for %llu",
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    const bool utf16 = unit == JB_UNIT_UTF16;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_charspans(d_text, nbytes, d_doc_off, ndocs, d_start, d_end, d_doc_tok, d_ntok, cap, utf16, d_cstart,
+                             d_cend, d_doc_units, d_work, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_charspans(d_text, nbytes, d_doc_off, ndocs, d_start, d_end, d_doc_tok, d_ntok, cap, utf16, d_cstart, d_cend,
+                         d_doc_units, d_work, s, nullptr));
+    return JB_OK;
+}
+
+// Host text in, character spans out: the cut of `mode` into the ctx's buffers [0] (and, when full mode's
+// list is longer than the batch has bytes, [1]), jb_charspans_device in place on the span arrays with its
+// work buffer and doc_units in [6], and the count, the converted spans, doc_tok and doc_units back.
+extern "C" int jb_cut_batch_charspans(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                                      int mode, int unit, uint32_t* cstart, uint32_t* cend, uint64_t cap,
+                                      uint64_t* doc_tok, uint64_t* ntokens, uint32_t* doc_units) {
+    const char* who = "jb_cut_batch_charspans";
+    if (!ctx || !doc_off || !doc_tok || !ntokens || (cap && (!cstart || !cend)) || (ndocs && !doc_units))
+        return fail(JB_EINVAL, "%s: null argument", who);
+    *ntokens = 0;
+    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
+        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
+    for (uint32_t k = 0; k < ndocs; k++)
+        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
+    const uint64_t nb = doc_off[ndocs] - doc_off[0];
+    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
+    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
+    if (const int rc = charspans_args(who, nb, 0, unit)) return rc;
+    if (ndocs == 0) {
+        doc_tok[0] = 0;
+        return JB_OK;
+    }
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    HIPCHK(hipSetDevice(ordinal));
+    std::vector<uint64_t> rel;
+    try {
+        rel.resize((size_t)ndocs + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
+    }
+    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
+    uint64_t dcap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
+    std::lock_guard<std::mutex> kg(ctx->kw_mu);
+    hipStream_t st = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
+        Arena a;
+        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * dcap * 4), &a))) return rc;
+        uint8_t* dt = (uint8_t*)a.take(nb + 64);
+        uint64_t* doff = (uint64_t*)a.take(ndoc8);
+        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
+        uint64_t* dcnt = (uint64_t*)a.take(16);            // (the span count)
+        uint32_t* dse = (uint32_t*)a.take(2 * dcap * 4);  // (starts, ends)
+        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
+        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+        uint64_t ntok = 0;
+        for (int pass = 0;; pass++) {
+            if (mode == JB_MODE_CUT)
+                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + dcap, dcap, dtok, dcnt);
+            else if (mode == JB_MODE_SEARCH)
+                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + dcap, dcap, dtok, dcnt);
+            else
+                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + dcap, dcap, dtok, dcnt);
+            if (rc) return rc;
+            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
+            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
+            if ((rc == JB_OK || (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > dcap)) && ntok > cap) {
+                // the caller's arrays are too small: say so before a regrow and a second cut
+                *ntokens = ntok;
+                return fail(JB_ELIMIT, "%llu tokens do not fit the %llu-token output arrays", (unsigned long long)ntok,
+                            (unsigned long long)cap);
+            }
+            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > dcap && pass == 0) {
+                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
+                dcap = ntok;
+                Arena b;
+                if ((rc = kw_arena(ctx, 1, r256(2 * dcap * 4), &b))) return rc;
+                dse = (uint32_t*)b.take(2 * dcap * 4);
+                continue;
+            }
+            if (rc) return rc;
+            break;
+        }
+        *ntokens = ntok;
+        if (const int r = charspans_args(who, nb, dcap, unit)) return r;
+        const size_t nwork = charspans_work_bytes(nb, ndocs);
+        Arena w;
+        if ((rc = kw_arena(ctx, 6, r256(nwork) + r256((size_t)ndocs * 4), &w))) return rc;
+        void* dwork = w.take(nwork);
+        uint32_t* dunits = (uint32_t*)w.take((size_t)ndocs * 4);
+        if ((rc = jb_charspans_device(ctx, dt, nb, doff, ndocs, dse, dse + dcap, dtok, dcnt, dcap, unit, st, dse,
+                                      dse + dcap, dunits, dwork, nwork)))
+            return rc;
+        if (ntok) {
+            HIPCHK(hipMemcpyAsync(cstart, dse, ntok * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(cend, dse + dcap, ntok * 4, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipMemcpyAsync(doc_tok, dtok, ndoc8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(doc_units, dunits, (size_t)ndocs * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return JB_OK;
+    };
+    const int rc = run();
+    if (st) {
+        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
+        (void)hipStreamDestroy(st);
+    }
     return rc;
 }

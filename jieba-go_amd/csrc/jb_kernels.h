@@ -127,6 +127,7 @@ enum KernelId {
     K_DF, K_IDF,
     K_TR_INIT, K_TR_SETUP, K_TR_COUNT, K_TR_STEP, K_TR_PUSH, K_TR_FINAL,
     K_JOIN_COUNT, K_JOIN_SCAN, K_JOIN_DOC, K_JOIN_WRITE,
+    K_CS_CLASS, K_CS_SCAN, K_CS_LOOKUP,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -314,6 +315,21 @@ hipError_t run_join(const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_st
                     uint32_t seplen, const uint8_t* term, uint32_t termlen, bool staged, uint8_t* d_out,
                     uint64_t out_cap, uint64_t* d_out_doc_off, uint64_t* d_nout, void* d_work, hipStream_t stream,
                     KernelTimer* timer);
+
+// Character offsets (jb_charspans_device; jb_charspans.hip).  Tile = kCsTile text bytes, one workgroup each; a
+// bitmap word covers 64 text bytes.
+constexpr uint32_t kCsTile = 4096;      // JB_CHARSPANS_TILE: 256 lanes x 16 bytes, 64 bitmap words
+constexpr uint32_t kCsTokTile = 1024;   // tokens per workgroup of the lookup: 256 lanes x 4 tokens
+// Bytes of the work buffer run_charspans needs: per 64 text bytes two u64 bitmap words and a u32 prefix,
+// per tile a u32 sum and a u32 base.  It does not depend on ndocs today.  Host only.
+size_t charspans_work_bytes(uint64_t nbytes, uint32_t ndocs);
+// Enqueue the three kernels on `stream`: cstart / cend of the tokens k < min(*d_ntok, cap) (they may be
+// d_start / d_end) and doc_units (ndocs), in runes (utf16 false) or UTF-16 code units.  d_work holds
+// charspans_work_bytes(nbytes, ndocs) bytes, 8-byte aligned.
+hipError_t run_charspans(const uint8_t* d_text, uint64_t nbytes, const uint64_t* d_doc_off, uint32_t ndocs,
+                         const uint32_t* d_start, const uint32_t* d_end, const uint64_t* d_doc_tok,
+                         const uint64_t* d_ntok, uint64_t cap, bool utf16, uint32_t* d_cstart, uint32_t* d_cend,
+                         uint32_t* d_doc_units, void* d_work, hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

@@ -529,6 +529,86 @@ func (t *Tokenizer) CutJoin(texts []string, sep string, useHmm bool, mode int) [
 	return out
 }
 
+// Token is one entry of Tokenize: the word and its offsets in its text, in the unit asked for.
+type Token struct {
+	Word       string
+	Start, End int
+}
+
+// Tokenize is jieba's tokenize for every text of a batch: the tokens of mode (C.JB_MODE_CUT, C.JB_MODE_SEARCH,
+// C.JB_MODE_FULL; full mode ignores useHmm) with their offsets in runes (C.JB_UNIT_RUNE: indexes of
+// []rune(text)) or in UTF-16 code units (C.JB_UNIT_UTF16: indexes of utf16.Encode([]rune(text))).  The cut and
+// the conversion both run on the GPU (jb_cut_batch_charspans); no byte offset comes back.  An invalid byte is
+// one rune, as in a range loop over the string, and its word is "�", as in Cut.  Never returns nil.
+func (t *Tokenizer) Tokenize(texts []string, useHmm bool, mode, unit int) [][]Token {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	out := make([][]Token, len(texts))
+	if len(texts) == 0 {
+		return out
+	}
+	off := make([]uint64, len(texts)+1)
+	total := 0
+	for i, d := range texts {
+		total += len(d)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, d := range texts {
+		b = append(b, d...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	capTok := total/2 + 16
+	var cs, ce []uint32
+	tok := make([]uint64, len(texts)+1)
+	units := make([]uint32, len(texts))
+	var n C.uint64_t
+	for pass := 0; ; pass++ {
+		cs, ce = make([]uint32, capTok), make([]uint32, capTok)
+		rc := C.jb_cut_batch_charspans(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+			C.uint32_t(len(texts)), hmm, C.int(mode), C.int(unit), (*C.uint32_t)(unsafe.Pointer(&cs[0])),
+			(*C.uint32_t)(unsafe.Pointer(&ce[0])), C.uint64_t(capTok), (*C.uint64_t)(unsafe.Pointer(&tok[0])), &n,
+			(*C.uint32_t)(unsafe.Pointer(&units[0])))
+		if rc == C.JB_ELIMIT && int(n) > capTok && pass == 0 {
+			capTok = int(n) // (the arrays were too small: the count is known now)
+			continue
+		}
+		if rc != C.JB_OK {
+			// JB_EINVAL: an unknown mode or unit; JB_EPANIC: the reference panics on this input
+			panic("jiebahip: " + lastError())
+		}
+		break
+	}
+	for d, text := range texts {
+		// at[u]: the byte at which unit u of the text starts (a range loop decodes as utf8.DecodeRune does)
+		at := make([]int, int(units[d])+1)
+		u := 0
+		for i, r := range text {
+			at[u] = i
+			u++
+			if unit == C.JB_UNIT_UTF16 && r >= 0x10000 {
+				at[u] = i
+				u++
+			}
+		}
+		at[u] = len(text)
+		toks := make([]Token, 0, tok[d+1]-tok[d])
+		for k := tok[d]; k < tok[d+1]; k++ {
+			w := text[at[cs[k]]:at[ce[k]]]
+			if len(w) == 1 && w[0] >= 0x80 {
+				w = "�" // invalid UTF-8 byte, as in Cut
+			}
+			toks = append(toks, Token{w, int(cs[k]), int(ce[k])})
+		}
+		out[d] = toks
+	}
+	return out
+}
+
 // IdfFit is the result of FitIdf: per id of the attached vocabulary its IDF weight and the number
 // of documents it occurs in, and the number of documents fitted on.
 type IdfFit struct {

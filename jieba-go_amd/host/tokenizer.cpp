@@ -1,6 +1,7 @@
 // tokenizer.cpp — C++ mirror of jieba-go's Tokenizer over the C ABI.
 #include "tokenizer.hpp"
 
+#include <algorithm>
 #include <cstring>
 
 namespace jiebago {
@@ -195,6 +196,57 @@ std::vector<std::string> Tokenizer::CutJoin(const std::vector<std::string>& docs
     for (size_t d = 0; d < docs.size(); d++)
         out.emplace_back((const char*)j.text + j.doc_off[d], (size_t)(j.doc_off[d + 1] - j.doc_off[d]));
     jb_joined_free(&j);
+    return out;
+}
+
+std::vector<std::vector<Tokenizer::Token>> Tokenizer::Tokenize(const std::vector<std::string>& docs, bool useHmm, int mode,
+                                                               int unit) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& d : docs) {
+        all += d;
+        off.push_back(all.size());
+    }
+    const uint32_t nd = (uint32_t)docs.size();
+    std::vector<uint32_t> cs(std::max<size_t>(all.size() / 2, 16)), ce(cs.size()), units(nd + 1);
+    std::vector<uint64_t> tok(nd + 1);
+    uint64_t n = 0;
+    int rc = jb_cut_batch_charspans(ctx_, (const uint8_t*)all.data(), off.data(), nd, useHmm ? 1 : 0, mode, unit, cs.data(),
+                                    ce.data(), cs.size(), tok.data(), &n, units.data());
+    if (rc == JB_ELIMIT && n > cs.size()) {  // (the arrays were too small: the count is known now)
+        cs.resize(n);
+        ce.resize(n);
+        rc = jb_cut_batch_charspans(ctx_, (const uint8_t*)all.data(), off.data(), nd, useHmm ? 1 : 0, mode, unit, cs.data(),
+                                    ce.data(), cs.size(), tok.data(), &n, units.data());
+    }
+    check(rc);
+    // the words: the host form of the rule over one span per byte says which bytes start a rune (the span
+    // [i, i + 1) has a length of its own exactly there) and at which unit, so no decoder is restated here.
+    // With one span per byte, doc_off is also the spans' doc_tok.  It costs a second host pass and 8 bytes
+    // per text byte, which a mirror can afford.  In UTF-16 at[u + 1] of a surrogate pair is never set: the
+    // library's own cuts put no token bound inside a rune, so no token indexes it.
+    const size_t nb = all.size();
+    std::vector<uint32_t> bs(nb), be(nb);
+    for (size_t i = 0; i < nb; i++) {
+        bs[i] = (uint32_t)i;
+        be[i] = (uint32_t)i + 1;
+    }
+    check(jb_charspans((const uint8_t*)all.data(), nb, off.data(), nd, bs.data(), be.data(), off.data(), nb, nb, unit, bs.data(),
+                       be.data(), units.data()));
+    std::vector<std::vector<Token>> out(nd);
+    std::vector<uint32_t> at;  // at[u]: the byte of the document at which unit u starts; at[units[d]]: its length
+    for (uint32_t d = 0; d < nd; d++) {
+        const std::string& doc = docs[d];
+        at.assign((size_t)units[d] + 1, (uint32_t)doc.size());
+        for (size_t i = 0; i < doc.size(); i++) {
+            const size_t g = off[d] + i;
+            if (be[g] > bs[g]) at[bs[g]] = (uint32_t)i;
+        }
+        for (uint64_t k = tok[d]; k < tok[d + 1]; k++) {
+            if (cs[k] > ce[k] || ce[k] > units[d]) continue;  // (JB_CHAR_NONE: not from the library's own cuts)
+            out[d].push_back(Token{token_at(doc, at[cs[k]], at[ce[k]]), cs[k], ce[k]});
+        }
+    }
     return out;
 }
 

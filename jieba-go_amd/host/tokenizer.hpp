@@ -104,6 +104,17 @@ public:
     // non-Han blocks without an alnum byte are absent, as in Cut.  sep holds at most JB_JOIN_MAXSEP bytes.
     std::vector<std::string> CutJoin(const std::vector<std::string>& docs, const std::string& sep = " ",
                                      bool useHmm = true, int mode = JB_MODE_CUT);
+    // jieba's tokenize (jb_cut_batch_charspans in jiebahip.h): per document its tokens with their offsets in
+    // the document, in Unicode characters (JB_UNIT_RUNE) or UTF-16 code units (JB_UNIT_UTF16), the cut of
+    // `mode` and the conversion both on the GPU; no byte offset reaches the host.  The word is the token's
+    // bytes, U+FFFD for an invalid byte, as in Cut; start and end index the document's code points (a Python str, a Go []rune) or its UTF-16 form
+    // (a Java String), where an invalid byte counts 1.
+    struct Token {
+        std::string word;
+        uint32_t start, end;
+    };
+    std::vector<std::vector<Token>> Tokenize(const std::vector<std::string>& docs, bool useHmm = true,
+                                             int mode = JB_MODE_CUT, int unit = JB_UNIT_RUNE);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

@@ -33,6 +33,11 @@ JB_JOIN_TILE = 2048  # tokens per scan tile of jb_join_device
 JB_JOIN_LONG = 256  # a key of this many bytes or more takes jb_join_device's cooperative copy
 JB_MODE_CUT, JB_MODE_SEARCH, JB_MODE_FULL = 0, 1, 2
 _MODES = {"cut": JB_MODE_CUT, "search": JB_MODE_SEARCH, "full": JB_MODE_FULL}
+JB_UNIT_RUNE, JB_UNIT_UTF16 = 0, 1  # the units of the character-offset calls
+JB_CHAR_NONE = 0xFFFFFFFF  # a token without character offsets (malformed, outside its document, of no document)
+JB_CHARSPANS_TILE = 4096  # text bytes per tile of jb_charspans_device
+_UNITS = {"rune": JB_UNIT_RUNE, "utf16": JB_UNIT_UTF16}
+_TOKENIZE_MODES = {"default": JB_MODE_CUT, "search": JB_MODE_SEARCH, "full": JB_MODE_FULL}
 
 # Every symbol include/jiebahip.h declares.
 EXPORTS = [
@@ -51,6 +56,7 @@ EXPORTS = [
     "jb_df_device", "jb_idf_device", "jb_idf", "jb_df_batch",
     "jb_textrank_work_bytes", "jb_textrank", "jb_textrank_device", "jb_textrank_batch",
     "jb_join_work_bytes", "jb_join", "jb_join_device", "jb_joined_free", "jb_cut_batch_join",
+    "jb_charspans_work_bytes", "jb_charspans", "jb_charspans_device", "jb_cut_batch_charspans",
 ]
 
 
@@ -214,6 +220,14 @@ def lib():
         L.jb_joined_free.restype = None
         L.jb_cut_batch_join.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint32, vp, C.c_uint32,
                                         C.POINTER(jb_joined)]
+        L.jb_charspans_work_bytes.restype = C.c_size_t
+        L.jb_charspans_work_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        L.jb_charspans.argtypes = [vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp,
+                                   vp]
+        L.jb_charspans_device.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, C.c_int, vp,
+                                          vp, vp, vp, vp, C.c_size_t]
+        L.jb_cut_batch_charspans.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp,
+                                             C.POINTER(C.c_uint64), vp]
         _lib = L
     return _lib
 
@@ -835,6 +849,75 @@ class Tokenizer:
         raw = out.tobytes()
         return [raw[int(ooff[d]):int(ooff[d + 1])].decode("utf-8") for d in range(len(docs))]
 
+    # -- character offsets -------------------------------------------------
+    def charspans_device(self, d_text_ptr, nbytes, d_doc_off, ndocs, d_start, d_end, d_doc_tok, d_ntok, cap, unit,
+                         d_cstart, d_cend, d_doc_units, d_work, nwork, stream_ptr=0):
+        """jb_charspans_device over raw device pointers: the byte spans of the tokens below min(*d_ntok, cap) as
+        spans in runes or UTF-16 code units per document (unit "rune", "utf16" or a JB_UNIT_* value) into
+        d_cstart / d_cend (they may be d_start / d_end), and each document's length into d_doc_units.
+        d_work: charspans_work_bytes(nbytes, ndocs) bytes."""
+        _check(lib().jb_charspans_device(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_doc_off), ndocs,
+                                         C.c_void_p(d_start), C.c_void_p(d_end), C.c_void_p(d_doc_tok),
+                                         C.c_void_p(d_ntok), cap, _unit(unit), C.c_void_p(stream_ptr),
+                                         C.c_void_p(d_cstart), C.c_void_p(d_cend), C.c_void_p(d_doc_units),
+                                         C.c_void_p(d_work), nwork))
+
+    def cut_batch_charspans(self, buf, doc_off, hmm, mode="cut", unit="rune", out=None):
+        """jb_cut_batch_charspans: host batch -> (cstart[:n], cend[:n], doc_tok, doc_units, out), the tokens of
+        `mode` ("cut", "search", "full" or a JB_MODE_* value) as per-document spans in `unit`.  `out` = (cstart
+        u32, cend u32, doc_tok u64[ndocs + 1], doc_units u32[ndocs]) to reuse; the span arrays are grown when
+        too small."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        nd = len(doc_off) - 1
+        if isinstance(mode, str):
+            if mode not in _MODES:
+                raise ValueError(f"mode {mode!r}: one of 'cut', 'search', 'full'")
+            mode = _MODES[mode]
+        unit = _unit(unit)
+        if out is None or len(out[2]) != nd + 1:
+            cap = max(1024, int(doc_off[-1] - doc_off[0]) // 2)
+            out = (np.empty(cap, np.uint32), np.empty(cap, np.uint32), np.empty(nd + 1, np.uint64),
+                   np.empty(max(nd, 1), np.uint32))
+        n = C.c_uint64()
+        for _ in range(2):
+            rc = lib().jb_cut_batch_charspans(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, int(hmm), int(mode), unit,
+                                              out[0].ctypes.data, out[1].ctypes.data, len(out[0]), out[2].ctypes.data,
+                                              C.byref(n), out[3].ctypes.data)
+            if rc == JB_ELIMIT and n.value > len(out[0]):
+                out = (np.empty(n.value, np.uint32), np.empty(n.value, np.uint32), out[2], out[3])
+                continue
+            _check(rc)
+            break
+        k = n.value
+        return out[0][:k], out[1][:k], out[2], out[3][:nd], out
+
+    def tokenize(self, texts, mode="default", hmm=True, unit="rune"):
+        """jieba's tokenize for every text (str) of a batch: a list of [(word, start, end)] per text, with start
+        and end in Unicode characters (unit "rune": word == text[start:end], taken from the str itself) or in
+        UTF-16 code units (unit "utf16": the word is cut from the text's UTF-16 form).  mode "default", "search"
+        or "full" (which ignores hmm).  The cut and the conversion run on the GPU; no byte offset is decoded
+        here.  A str with a lone surrogate has no UTF-8 form and raises UnicodeEncodeError."""
+        if mode not in _TOKENIZE_MODES:
+            raise ValueError(f"mode {mode!r}: one of 'default', 'search', 'full'")
+        unit = _unit(unit)
+        if not texts:
+            return []
+        docs = [t.encode("utf-8") for t in texts]
+        buf = np.frombuffer(b"".join(docs) + b"\0", np.uint8)
+        off = np.cumsum([0] + [len(d) for d in docs]).astype(np.uint64)
+        cs, ce, dtok, _, _ = self.cut_batch_charspans(buf, off, hmm, _TOKENIZE_MODES[mode], unit)
+        cs, ce, dtok = cs.tolist(), ce.tolist(), dtok.tolist()
+        out = []
+        for d, t in enumerate(texts):
+            if unit == JB_UNIT_UTF16:
+                u = t.encode("utf-16-le")
+                out.append([(u[2 * cs[k]:2 * ce[k]].decode("utf-16-le"), cs[k], ce[k])
+                            for k in range(dtok[d], dtok[d + 1])])
+            else:
+                out.append([(t[cs[k]:ce[k]], cs[k], ce[k]) for k in range(dtok[d], dtok[d + 1])])
+        return out
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -884,7 +967,7 @@ class Tokenizer:
         _check(lib().jb_profile_reset(self.h))
 
     def profile_read(self):
-        cap = 64  # (more than the library's kernels: 44)
+        cap = 64  # (more than the library's kernels: 47)
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         n = (C.c_uint64 * cap)()
@@ -1023,6 +1106,44 @@ def join(text, starts, ends, doc_tok, sep=b" ", term=b"\n", ntok=None, cap=None,
     out = np.empty(max(out_cap, 1), np.uint8)
     call(out, out_cap)
     return out[:out_cap], off, n.value
+
+
+def _unit(unit):
+    if isinstance(unit, str):
+        if unit not in _UNITS:
+            raise ValueError(f"unit {unit!r}: one of 'rune', 'utf16'")
+        return _UNITS[unit]
+    return int(unit)
+
+
+def charspans_work_bytes(nbytes, ndocs):
+    """jb_charspans_work_bytes: bytes of the work buffer jb_charspans_device needs (host only)."""
+    return lib().jb_charspans_work_bytes(nbytes, ndocs)
+
+
+def charspans(text, doc_off, starts, ends, doc_tok, unit="rune", ntok=None, cap=None, nbytes=None, inplace=False):
+    """jb_charspans (host only): the character-offset rule of jiebahip.h on host arrays (text bytes or a uint8
+    array, u64 doc_off, u32 spans, u64 doc_tok).  Returns (cstart u32[cap], cend u32[cap], doc_units
+    u32[ndocs]); entries at or past min(ntok, cap) are left as JB_CHAR_NONE - 1 (0xFFFFFFFE), which the rule
+    never writes.  inplace: the outputs are the (copied) span arrays themselves."""
+    t = np.ascontiguousarray(text, np.uint8) if isinstance(text, np.ndarray) else np.frombuffer(_b(text), np.uint8)
+    o = np.ascontiguousarray(doc_off, np.uint64)
+    s = np.array(starts, np.uint32)
+    e = np.array(ends, np.uint32)
+    d = np.ascontiguousarray(doc_tok, np.uint64)
+    nd = len(o) - 1
+    cap = len(s) if cap is None else cap
+    ntok = len(s) if ntok is None else ntok
+    if inplace:
+        cs, ce = s, e
+    else:
+        cs, ce = np.full(len(s), 0xFFFFFFFE, np.uint32), np.full(len(e), 0xFFFFFFFE, np.uint32)
+    units = np.zeros(nd, np.uint32)
+    p = lambda a: a.ctypes.data if len(a) else None
+    nbytes = len(t) if nbytes is None else nbytes
+    _check(lib().jb_charspans(p(t), nbytes, o.ctypes.data, nd, p(s), p(e), d.ctypes.data, ntok, cap, _unit(unit),
+                              p(cs), p(ce), p(units)))
+    return cs, ce, units
 
 
 def textrank_work_bytes(max_tokens, max_terms, ndocs):
