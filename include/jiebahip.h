@@ -738,6 +738,96 @@ int jb_cut_batch_charspans(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc
                            int unit, uint32_t *cstart, uint32_t *cend, uint64_t cap, uint64_t *doc_tok,
                            uint64_t *ntokens, uint32_t *doc_units);
 
+/* ---- word counts and vocabulary fitting: the distinct tokens of a corpus with their counts ----
+ *
+ * Everything above that numbers tokens needs a vocabulary the caller already has.  These calls make
+ * one: distinct token strings with exact global counts are accumulated in a table on the device over
+ * any number of batches, in any cut mode, and the much smaller result is read back sorted, ready for
+ * jb_vocab_set (Counter(jieba.cut(text)), a min_count vocabulary).
+ *
+ * The rule.  jb_wc_count (host only, no ctx, no GPU) and the device table agree exactly.
+ *  - Tokens.  Token k takes part iff k < min(ntok, cap).
+ *  - Key.  A token's key is jb_ids_device's: the bytes text[start .. end); a 1-byte span whose byte is
+ *    >= 0x80 is keyed as EF BF BD.
+ *  - The spans are not trusted.  A span with start >= end or end > nbytes is bad, a key over 255 bytes
+ *    is long; neither is read or counted, each adds to a total of its own (nbad, nlong).
+ *  - Counts are u64, exact, independent of the order of the adds and the same from run to run.
+ *  - Order.  Keys come by count descending, ties by key bytes ascending (memcmp, a proper prefix
+ *    first).  min_count drops the keys below it, max_keys keeps the first max_keys of that order (0: all).
+ *  - Accounting.  The counts of all keys before those two filters, plus nbad + nlong + ndropped +
+ *    ncollided, are ntokens, the tokens that took part.  The five totals accumulate over the batches.
+ *
+ * The table is a caller-owned device buffer of jb_wc_table_bytes(nslots, pool_bytes) bytes, 32-byte
+ * aligned: nslots (a power of two >= 8; JB_ELIMIT above 2^30) slots of a 64-bit fingerprint, a u64 count
+ * and jb_vocab's 32-byte key slot, and pool_bytes (under 4 GiB) for the keys over 24 bytes.  New keys are
+ * accepted while fewer than nslots / 2 slots are taken, so size nslots at four times the distinct keys
+ * expected.  A token whose key finds no slot, or whose key of over 24 bytes finds no room in the pool,
+ * is dropped (ndropped).  Two different keys with one 64-bit fingerprint share a slot: it keeps the key
+ * whose first token comes earliest (an earlier batch before a later one), and every token of the other
+ * key adds to ncollided and to no count, so a key is never credited with another key's tokens.  With
+ * ndropped == 0 and ncollided == 0 the result is complete and exact; otherwise every reported count is
+ * a lower bound on the true one.  The accounting holds in both cases.
+ *
+ * jb_wc_table_bytes and jb_wc_work_bytes are host only, non-decreasing in their arguments and never 0
+ * (SIZE_MAX where the size does not fit; a slot count that is not valid is sized as the next valid one).
+ *
+ * jb_wc_init_device queues the kernel that empties a table (JB_EINVAL for a bad nslots, a null,
+ * misaligned or short buffer).
+ *
+ * jb_wc_add_device adds one batch's spans, of any mode or a caller's own, with jb_terms_device's contract:
+ * it queues on `stream` and returns without synchronising, allocating, reading on the host or using
+ * the per-device workspace, and takes the shared lock only while queuing.  There are three launches,
+ * or none when cap is 0, whatever the data, and no lane ever waits for another.  d_text is 4-byte
+ * aligned and readable 64 bytes past nbytes; d_ntok is a device u64; d_work holds
+ * jb_wc_work_bytes(cap) bytes (4 per token), 4-byte aligned; d_table is 32-byte aligned and ntable at
+ * least jb_wc_table_bytes(8, 0): JB_EINVAL otherwise, with nothing queued.  JB_ELIMIT for nbytes >=
+ * 2 GiB or cap >= 2^32 - 256.  No vocabulary is needed.  A buffer that jb_wc_init_device did not
+ * fill, or an ntable below what its table needs, is left untouched by the kernels; jb_wc_read then
+ * says so.  The count pass has two forms with identical results (JB_WC_COMBINE, read at jb_open): 0
+ * is one global atomic per token, 1 (the default) combines a workgroup's adds to a slot in LDS first.
+ * JB_WC_HASHBITS (read at jb_open, default 64) keeps only that many low bits of the hash in the
+ * fingerprint, so that a test can make keys collide; jb_wc_fp (host only) is the fingerprint of a key
+ * of 1 .. 255 bytes at that width (0 for arguments outside that).
+ *
+ * jb_wc_read synchronises `stream`, copies the table to the host, and sorts and filters there (the
+ * distinct keys are orders of magnitude fewer than the tokens).  The table is left unchanged, so
+ * reading part-way through is allowed.  JB_EINVAL when the buffer holds no table.  jb_wc_result_free
+ * frees the arrays (malloc'd) and zeroes the struct.
+ *
+ * jb_wc_batch: host text in.  It uploads, cuts in `mode` (JB_MODE_*; hmm is ignored for
+ * JB_MODE_FULL) on ctx's first device and adds to the table, through the buffers jb_keywords_batch
+ * keeps in the ctx; concurrent calls take turns.  Requirements and errors are jb_keywords_batch's minus
+ * the vocabulary, and JB_EINVAL for an unknown mode.  It returns when the batch is in the table.
+ *
+ * jb_device_alloc / jb_device_free: n bytes of device memory on ctx's first device (256-byte aligned),
+ * for a caller that has no binding to the HIP runtime of its own, such as the C++ and Go Tokenizers'
+ * WordCounts, to keep a table in.  JB_ENOMEM when the device has no room; jb_device_free waits for the
+ * device work that uses the block, and ignores NULL. */
+typedef struct jb_wc_result {
+    uint8_t *keys;      /* the keys back to back, in the rule's order */
+    uint64_t *key_off;  /* nkeys + 1: key i is keys[key_off[i] .. key_off[i+1]) */
+    uint64_t *counts;   /* nkeys */
+    uint64_t nkeys;
+    uint64_t nbad, nlong, ndropped, ncollided, ntokens;
+} jb_wc_result;
+
+size_t jb_wc_table_bytes(uint64_t nslots, uint64_t pool_bytes);
+size_t jb_wc_work_bytes(uint64_t max_tokens);
+uint64_t jb_wc_fp(const uint8_t *key, size_t len, uint32_t bits);
+int jb_wc_init_device(jb_ctx *ctx, void *d_table, size_t ntable, uint64_t nslots, uint64_t pool_bytes, void *stream);
+int jb_wc_add_device(jb_ctx *ctx, void *d_table, size_t ntable, const uint8_t *d_text, uint64_t nbytes,
+                     const uint32_t *d_start, const uint32_t *d_end, const uint64_t *d_ntok, uint64_t cap,
+                     void *stream, void *d_work, size_t nwork);
+int jb_wc_read(jb_ctx *ctx, const void *d_table, size_t ntable, void *stream, uint64_t min_count, uint64_t max_keys,
+               jb_wc_result *out);
+void jb_wc_result_free(jb_wc_result *r);
+int jb_wc_count(const uint8_t *text, uint64_t nbytes, const uint32_t *start, const uint32_t *end, uint64_t ntok,
+                uint64_t cap, uint64_t min_count, uint64_t max_keys, jb_wc_result *out);
+int jb_wc_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm, int mode,
+                void *d_table, size_t ntable);
+int jb_device_alloc(jb_ctx *ctx, size_t n, void **p);
+void jb_device_free(jb_ctx *ctx, void *p);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

@@ -16,6 +16,7 @@
 #include "jb_host.h"
 #include "jb_join.h"
 #include "jb_textrank.h"
+#include "jb_wc.h"
 
 // ---------------------------------------------------------------------------
 // image
@@ -1665,6 +1666,209 @@ extern "C" int jb_cut_batch_charspans(jb_ctx* ctx, const uint8_t* text, const ui
     const int rc = run();
     if (st) {
         (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
+        (void)hipStreamDestroy(st);
+    }
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// word counts (jb_wc.hip; the host rule, jb_wc_count, the reader and the size helpers are jb_wc.cpp)
+// ---------------------------------------------------------------------------
+namespace {
+
+// What every call that is handed a table checks: JB_OK, or JB_EINVAL with the thread's message set.
+int wc_table_args(const char* who, const void* d_table, size_t ntable) {
+    if (!d_table) return fail(JB_EINVAL, "%s: null table", who);
+    if (((uintptr_t)d_table & 31u) != 0) return fail(JB_EINVAL, "%s: d_table must be 32-byte aligned", who);
+    if (ntable < jb_wc_bytes(JB_WC_MIN_SLOTS, 0))
+        return fail(JB_EINVAL, "%s: a table buffer of %llu bytes, the smallest table has %llu", who,
+                    (unsigned long long)ntable, (unsigned long long)jb_wc_bytes(JB_WC_MIN_SLOTS, 0));
+    return JB_OK;
+}
+
+}  // namespace
+
+extern "C" int jb_device_alloc(jb_ctx* ctx, size_t n, void** p) {
+    if (!ctx || !p) return fail(JB_EINVAL, "jb_device_alloc: null argument");
+    *p = nullptr;
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    HIPCHK(hipSetDevice(ordinal));
+    if (hipMalloc(p, n ? n : 1) != hipSuccess) {
+        *p = nullptr;
+        return fail(JB_ENOMEM, "jb_device_alloc: no device memory for %llu bytes", (unsigned long long)n);
+    }
+    return JB_OK;
+}
+
+extern "C" void jb_device_free(jb_ctx* ctx, void* p) {
+    if (!ctx || !p) return;
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    if (hipSetDevice(ordinal) == hipSuccess) (void)hipFree(p);  // (hipFree waits for the work that uses p)
+}
+
+extern "C" int jb_wc_init_device(jb_ctx* ctx, void* d_table, size_t ntable, uint64_t nslots, uint64_t pool_bytes,
+                                 void* stream) {
+    if (!ctx) return fail(JB_EINVAL, "jb_wc_init_device: null ctx");
+    if (const int rc = wc_sizes("jb_wc_init_device", nslots, pool_bytes)) return rc;
+    if (const int rc = wc_table_args("jb_wc_init_device", d_table, ntable)) return rc;
+    if (ntable < jb_wc_bytes(nslots, pool_bytes))
+        return fail(JB_EINVAL, "jb_wc_init_device: a table buffer of %llu bytes, jb_wc_table_bytes asks for %llu",
+                    (unsigned long long)ntable, (unsigned long long)jb_wc_bytes(nslots, pool_bytes));
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    HIPCHK(run_wc_init(d_table, nslots, pool_bytes, d->ncu, (hipStream_t)stream));
+    return JB_OK;
+}
+
+extern "C" int jb_wc_add_device(jb_ctx* ctx, void* d_table, size_t ntable, const uint8_t* d_text, uint64_t nbytes,
+                                const uint32_t* d_start, const uint32_t* d_end, const uint64_t* d_ntok, uint64_t cap,
+                                void* stream, void* d_work, size_t nwork) {
+    if (!ctx || (!d_text && nbytes) || !d_ntok || (cap && (!d_start || !d_end || !d_work)))
+        return fail(JB_EINVAL, "jb_wc_add_device: null argument");
+    if (nbytes >= (1ull << 31))
+        return fail(JB_ELIMIT, "device batch of %llu bytes (limit 2 GiB)", (unsigned long long)nbytes);
+    if (cap >= (1ull << 32) - kWcTile)
+        return fail(JB_ELIMIT, "jb_wc_add_device: a span list of %llu entries (limit 2^32 - %u)", (unsigned long long)cap,
+                    kWcTile);
+    if (const int rc = wc_table_args("jb_wc_add_device", d_table, ntable)) return rc;
+    if (((uintptr_t)d_text & 3u) != 0) return fail(JB_EINVAL, "d_text must be 4-byte aligned");
+    if (((uintptr_t)d_work & 3u) != 0) return fail(JB_EINVAL, "jb_wc_add_device: d_work must be 4-byte aligned");
+    const size_t need = jb_wc_work_bytes(cap);
+    if (cap && nwork < need)
+        return fail(JB_EINVAL, "jb_wc_add_device: a work buffer of %llu bytes, jb_wc_work_bytes asks for %llu",
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    const bool combine = d->lc.wc_combine != 0;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_wc_add(d_table, ntable, d_text, nbytes, d_start, d_end, d_ntok, cap, d->lc.wc_bits, combine,
+                          (uint32_t*)d_work, d->ncu, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_wc_add(d_table, ntable, d_text, nbytes, d_start, d_end, d_ntok, cap, d->lc.wc_bits, combine,
+                      (uint32_t*)d_work, d->ncu, s, nullptr));
+    return JB_OK;
+}
+
+extern "C" int jb_wc_read(jb_ctx* ctx, const void* d_table, size_t ntable, void* stream, uint64_t min_count,
+                          uint64_t max_keys, jb_wc_result* out) {
+    if (!ctx || !out) return fail(JB_EINVAL, "jb_wc_read: null argument");
+    memset(out, 0, sizeof *out);
+    if (const int rc = wc_table_args("jb_wc_read", d_table, ntable)) return rc;
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    HIPCHK(hipSetDevice(ordinal));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    // the header says how much of the buffer the table takes
+    JbWcHeader h;
+    HIPCHK(hipMemcpy(&h, d_table, sizeof h, hipMemcpyDeviceToHost));
+    if (h.magic != JB_WC_MAGIC || wc_sizes("jb_wc_read", h.nslots, h.pool_bytes) != JB_OK ||
+        jb_wc_bytes(h.nslots, h.pool_bytes) > ntable)
+        return fail(JB_EINVAL, "jb_wc_read: the buffer holds no table (jb_wc_init_device)");
+    const size_t nb = (size_t)jb_wc_bytes(h.nslots, h.pool_bytes);
+    void* host = malloc(nb);
+    if (!host) return fail(JB_ENOMEM, "jb_wc_read: out of host memory for a table of %llu bytes", (unsigned long long)nb);
+    const hipError_t e = hipMemcpy(host, d_table, nb, hipMemcpyDeviceToHost);
+    int rc = e == hipSuccess ? wc_read_host(host, nb, min_count, max_keys, out)
+                             : fail(JB_EDEVICE, "jb_wc_read: %s", hipGetErrorString(e));
+    free(host);
+    if (rc) jb_wc_result_free(out);
+    return rc;
+}
+
+// Host text in, the batch's tokens into the table: the cut of `mode` into the ctx's buffers [0] (and, when
+// full mode's list is longer than the batch has bytes, [1]), then jb_wc_add_device with its work buffer in [7].
+extern "C" int jb_wc_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm, int mode,
+                           void* d_table, size_t ntable) {
+    const char* who = "jb_wc_batch";
+    if (!ctx || !doc_off) return fail(JB_EINVAL, "%s: null argument", who);
+    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
+        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
+    if (const int rc = wc_table_args(who, d_table, ntable)) return rc;
+    for (uint32_t k = 0; k < ndocs; k++)
+        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
+    const uint64_t nb = doc_off[ndocs] - doc_off[0];
+    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
+    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    if (ndocs == 0) return JB_OK;
+    HIPCHK(hipSetDevice(ordinal));
+    std::vector<uint64_t> rel;
+    try {
+        rel.resize((size_t)ndocs + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
+    }
+    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
+    uint64_t cap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
+    std::lock_guard<std::mutex> kg(ctx->kw_mu);
+    hipStream_t st = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
+        Arena a;
+        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * cap * 4), &a))) return rc;
+        uint8_t* dt = (uint8_t*)a.take(nb + 64);
+        uint64_t* doff = (uint64_t*)a.take(ndoc8);
+        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
+        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the span count)
+        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
+        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
+        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+        uint64_t ntok = 0;
+        for (int pass = 0;; pass++) {
+            if (mode == JB_MODE_CUT)
+                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
+            else if (mode == JB_MODE_SEARCH)
+                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
+            else
+                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + cap, cap, dtok, dcnt);
+            if (rc) return rc;
+            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
+            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
+            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > cap && pass == 0) {
+                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
+                cap = ntok;
+                Arena b;
+                if ((rc = kw_arena(ctx, 1, r256(2 * cap * 4), &b))) return rc;
+                dse = (uint32_t*)b.take(2 * cap * 4);
+                continue;
+            }
+            if (rc) return rc;
+            break;
+        }
+        const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);  // (the work buffer follows the token count)
+        const size_t nwork = jb_wc_work_bytes(tcap);
+        Arena w;
+        if ((rc = kw_arena(ctx, 7, nwork, &w))) return rc;
+        if ((rc = jb_wc_add_device(ctx, d_table, ntable, dt, nb, dse, dse + cap, dcnt, tcap, st, w.p, nwork))) return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        return JB_OK;
+    };
+    const int rc = run();
+    if (st) {
+        (void)hipStreamSynchronize(st);  // (the copy from the caller's memory may be in flight)
         (void)hipStreamDestroy(st);
     }
     return rc;

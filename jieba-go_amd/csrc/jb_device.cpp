@@ -244,6 +244,8 @@ static const uint64_t kMaxPiece = 1ull << 30;  // (a piece of several documents;
 //   JB_DF_COMBINE jb_df_device's kernel: 1 k_df_combine (default), 0 k_df
 //   JB_TR_WINDOW jb_textrank_device's push kernel: 1 k_tr_push_win (default), 0 k_tr_push
 //   JB_JOIN_STAGE jb_join_device's write kernel: 0 the plain form (default), 1 the staged form
+//   JB_WC_COMBINE jb_wc_add_device's count pass: 0 one global atomic per token, 1 combined in LDS (default)
+//   JB_WC_HASHBITS the word-count fingerprint's width, 1 .. 64 (default 64; fewer to test collisions)
 static int init_launch_cfg(Device* d) {
     LaunchCfg& lc = d->lc;
     lc.zh_waves = d->ncu * std::max(zh_waves_per_cu(true, false), zh_waves_per_cu(false, false));
@@ -311,6 +313,12 @@ static int init_launch_cfg(Device* d) {
     const int js = env_int("JB_JOIN_STAGE", 0);
     if (js < 0 || js > 1) return fail(JB_EINVAL, "JB_JOIN_STAGE=%d: want 0 or 1", js);
     lc.join_stage = (uint32_t)js;
+    const int wcc = env_int("JB_WC_COMBINE", 1);
+    if (wcc < 0 || wcc > 1) return fail(JB_EINVAL, "JB_WC_COMBINE=%d: want 0 or 1", wcc);
+    lc.wc_combine = (uint32_t)wcc;
+    const int wcb = env_int("JB_WC_HASHBITS", 64);
+    if (wcb < 1 || wcb > 64) return fail(JB_EINVAL, "JB_WC_HASHBITS=%d: want 1 .. 64", wcb);
+    lc.wc_bits = (uint32_t)wcb;
     return JB_OK;
 }
 

@@ -128,6 +128,7 @@ enum KernelId {
     K_TR_INIT, K_TR_SETUP, K_TR_COUNT, K_TR_STEP, K_TR_PUSH, K_TR_FINAL,
     K_JOIN_COUNT, K_JOIN_SCAN, K_JOIN_DOC, K_JOIN_WRITE,
     K_CS_CLASS, K_CS_SCAN, K_CS_LOOKUP,
+    K_WC_CLAIM, K_WC_STORE, K_WC_COUNT,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -167,6 +168,10 @@ struct LaunchCfg {
                              // depend on it)
     uint32_t join_stage;     // jb_join_device's write: 0 the plain form (default), 1 the staged form (JB_JOIN_STAGE; results do
                              // not depend on it)
+    uint32_t wc_combine;     // jb_wc_add_device's count pass: 0 one global atomic per token, 1 combined in LDS
+                             // (JB_WC_COMBINE; results do not depend on it)
+    uint32_t wc_bits;        // the fingerprint keeps this many low bits of the hash (JB_WC_HASHBITS: 64; fewer
+                             // only to test the collision path)
 };
 
 // k_zh's group split: g1 groups of grp bytes, then groups of *sgrp bytes to the end.
@@ -330,6 +335,19 @@ hipError_t run_charspans(const uint8_t* d_text, uint64_t nbytes, const uint64_t*
                          const uint32_t* d_start, const uint32_t* d_end, const uint64_t* d_doc_tok,
                          const uint64_t* d_ntok, uint64_t cap, bool utf16, uint32_t* d_cstart, uint32_t* d_cend,
                          uint32_t* d_doc_units, void* d_work, hipStream_t stream, KernelTimer* timer);
+
+// Word counts (jb_wc_init_device, jb_wc_add_device; jb_wc.hip, the table is jb_wc.h's).  Tile = kWcTile
+// consecutive tokens per workgroup and trip, under k_ids' fixed grid.
+constexpr uint32_t kWcTile = 256;
+// Enqueue k_wc_init on `stream`: an empty table of nslots slots (valid by wc_sizes) and pool_bytes of pool.
+hipError_t run_wc_init(void* d_table, uint64_t nslots, uint64_t pool_bytes, uint32_t ncu, hipStream_t stream);
+// Enqueue the three passes on `stream` (none when cap is 0): the tokens k < min(*d_ntok, cap) added to the
+// table at d_table (ntable bytes; a buffer that holds no table is left alone).  d_text is 4-byte aligned and
+// no byte at or past nbytes + 64 is read; d_work holds 4 bytes per token of cap.  `bits` is the
+// fingerprint's width, `combine` chooses the count pass's form.
+hipError_t run_wc_add(void* d_table, uint64_t ntable, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
+                      const uint32_t* d_end, const uint64_t* d_ntok, uint64_t cap, uint32_t bits, bool combine,
+                      uint32_t* d_work, uint32_t ncu, hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

@@ -40,7 +40,8 @@ const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_
                                          "k_terms_count", "k_terms_scan", "k_terms_write", "k_keywords", "k_df",
                                          "k_idf", "k_tr_init", "k_tr_setup", "k_tr_count", "k_tr_step", "k_tr_push",
                                          "k_tr_final", "k_join_count", "k_join_scan", "k_join_doc", "k_join_write",
-                                         "k_cs_class", "k_cs_scan", "k_cs_lookup"};
+                                         "k_cs_class", "k_cs_scan", "k_cs_lookup", "k_wc_claim", "k_wc_store",
+                                         "k_wc_count"};
 
 hipError_t run_pipeline(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes,
                         const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, const LaunchCfg& lc,

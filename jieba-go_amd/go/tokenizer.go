@@ -481,6 +481,69 @@ func (t *Tokenizer) TextRank(docs []string, keep []byte, topK, span, iters int, 
 	return out
 }
 
+// WordCount is one distinct token of a corpus with the number of times it was cut.
+type WordCount struct {
+	Word  string
+	Count uint64
+}
+
+// WordCounts counts the distinct tokens of a batch of texts, in the cut of mode (C.JB_MODE_CUT,
+// C.JB_MODE_SEARCH, C.JB_MODE_FULL; full mode ignores useHmm): the words by count descending and then by
+// bytes, without those below minCount, the first maxKeys of them (0: all).  The cut and the counting both run
+// on the GPU, in a table of nslots slots (a power of two; new words are accepted while fewer than half are
+// taken) and poolBytes for the words over 24 bytes; only the distinct words come back.  exact is false when
+// tokens were dropped for lack of room or two words shared a fingerprint: every count is a lower bound then.
+// With mini_dict.txt, WordCounts([]string{"这一刹那 abc abc"}, false, C.JB_MODE_CUT, 1, 0, 1024, 4096) is
+// {abc 2} {一刹那 1} {这 1} (tests/c_abi_wc.c).  Never returns nil.
+func (t *Tokenizer) WordCounts(texts []string, useHmm bool, mode int, minCount, maxKeys, nslots, poolBytes uint64) (words []WordCount, exact bool) {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	words = []WordCount{}
+	off := make([]uint64, len(texts)+1)
+	total := 0
+	for i, d := range texts {
+		total += len(d)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, d := range texts {
+		b = append(b, d...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	ntable := C.jb_wc_table_bytes(C.uint64_t(nslots), C.uint64_t(poolBytes))
+	var table unsafe.Pointer
+	if C.jb_device_alloc(t.ctx, ntable, &table) != C.JB_OK {
+		panic("jiebahip: " + lastError())
+	}
+	defer C.jb_device_free(t.ctx, table)
+	var r C.jb_wc_result
+	rc := C.jb_wc_init_device(t.ctx, table, ntable, C.uint64_t(nslots), C.uint64_t(poolBytes), nil)
+	if rc == C.JB_OK {
+		rc = C.jb_wc_batch(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+			C.uint32_t(len(texts)), hmm, C.int(mode), table, ntable)
+	}
+	if rc == C.JB_OK {
+		rc = C.jb_wc_read(t.ctx, table, ntable, nil, C.uint64_t(minCount), C.uint64_t(maxKeys), &r)
+	}
+	if rc != C.JB_OK {
+		// JB_EINVAL: an unknown mode or a bad nslots; JB_EPANIC: the reference panics on this input
+		panic("jiebahip: " + lastError())
+	}
+	defer C.jb_wc_result_free(&r)
+	n := int(r.nkeys)
+	koff := unsafe.Slice((*uint64)(unsafe.Pointer(r.key_off)), n+1)
+	cnt := unsafe.Slice((*uint64)(unsafe.Pointer(r.counts)), n)
+	keys := C.GoBytes(unsafe.Pointer(r.keys), C.int(koff[n]))
+	for i := 0; i < n; i++ {
+		words = append(words, WordCount{string(keys[koff[i]:koff[i+1]]), cnt[i]})
+	}
+	return words, r.ndropped == 0 && r.ncollided == 0
+}
+
 // CutJoin is strings.Join(Cut(text), sep) for every text of a batch, with the cut of mode (C.JB_MODE_CUT,
 // C.JB_MODE_SEARCH, C.JB_MODE_FULL; full mode ignores useHmm) and the join both on the GPU: only the joined
 // bytes come back, no span and no token.  sep holds at most JB_JOIN_MAXSEP (8) bytes.  An invalid byte comes

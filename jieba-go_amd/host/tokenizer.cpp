@@ -199,6 +199,38 @@ std::vector<std::string> Tokenizer::CutJoin(const std::vector<std::string>& docs
     return out;
 }
 
+std::vector<Tokenizer::WordCount> Tokenizer::WordCounts(const std::vector<std::string>& docs, bool useHmm, int mode,
+                                                        uint64_t minCount, uint64_t maxKeys, uint64_t nslots,
+                                                        uint64_t poolBytes, bool strict) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& d : docs) {
+        all += d;
+        off.push_back(all.size());
+    }
+    const size_t ntable = jb_wc_table_bytes(nslots, poolBytes);
+    void* table = nullptr;
+    check(jb_device_alloc(ctx_, ntable, &table));
+    jb_wc_result r;
+    int rc = jb_wc_init_device(ctx_, table, ntable, nslots, poolBytes, nullptr);
+    if (rc == JB_OK)
+        rc = jb_wc_batch(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)docs.size(), useHmm ? 1 : 0, mode, table,
+                         ntable);
+    if (rc == JB_OK) rc = jb_wc_read(ctx_, table, ntable, nullptr, minCount, maxKeys, &r);
+    jb_device_free(ctx_, table);
+    check(rc);
+    std::vector<WordCount> out;
+    out.reserve(r.nkeys);
+    for (uint64_t i = 0; i < r.nkeys; i++)
+        out.push_back({std::string((const char*)r.keys + r.key_off[i], (size_t)(r.key_off[i + 1] - r.key_off[i])), r.counts[i]});
+    const uint64_t dropped = r.ndropped, collided = r.ncollided;
+    jb_wc_result_free(&r);
+    if (strict && (dropped || collided))
+        throw Error(JB_ELIMIT, "WordCounts: " + std::to_string(dropped) + " tokens dropped for lack of room and " +
+                                   std::to_string(collided) + " in fingerprint collisions: the counts are lower bounds");
+    return out;
+}
+
 std::vector<std::vector<Tokenizer::Token>> Tokenizer::Tokenize(const std::vector<std::string>& docs, bool useHmm, int mode,
                                                                int unit) {
     std::string all;

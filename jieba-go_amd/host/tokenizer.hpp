@@ -115,6 +115,20 @@ public:
     };
     std::vector<std::vector<Token>> Tokenize(const std::vector<std::string>& docs, bool useHmm = true,
                                              int mode = JB_MODE_CUT, int unit = JB_UNIT_RUNE);
+    // Word counts (Counter(jieba.cut(text)); the jb_wc_* calls in jiebahip.h): the distinct tokens of the documents
+    // in the cut of `mode` with their exact counts, by count descending and then by bytes, without the words
+    // below minCount, the first maxKeys of them (0: all).  The cut and the counting run on the GPU, in a table of
+    // nslots slots (a power of two; new words are accepted while fewer than half are taken) and poolBytes for
+    // the words over 24 bytes; only the distinct words come back.  Throws Error(JB_ELIMIT) when tokens were
+    // dropped for lack of room or two words shared a fingerprint, unless strict is false: the counts are lower
+    // bounds then.  SetVocab with the words fits a vocabulary.
+    struct WordCount {
+        std::string word;
+        uint64_t count;
+    };
+    std::vector<WordCount> WordCounts(const std::vector<std::string>& docs, bool useHmm = true, int mode = JB_MODE_CUT,
+                                      uint64_t minCount = 1, uint64_t maxKeys = 0, uint64_t nslots = 1u << 20,
+                                      uint64_t poolBytes = 4u << 20, bool strict = true);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

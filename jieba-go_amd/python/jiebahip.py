@@ -57,6 +57,8 @@ EXPORTS = [
     "jb_textrank_work_bytes", "jb_textrank", "jb_textrank_device", "jb_textrank_batch",
     "jb_join_work_bytes", "jb_join", "jb_join_device", "jb_joined_free", "jb_cut_batch_join",
     "jb_charspans_work_bytes", "jb_charspans", "jb_charspans_device", "jb_cut_batch_charspans",
+    "jb_wc_table_bytes", "jb_wc_work_bytes", "jb_wc_fp", "jb_wc_init_device", "jb_wc_add_device", "jb_wc_read",
+    "jb_wc_result_free", "jb_wc_count", "jb_wc_batch", "jb_device_alloc", "jb_device_free",
 ]
 
 
@@ -94,6 +96,30 @@ class _Joined:
     def __del__(self):
         if _lib is not None:
             _lib.jb_joined_free(C.byref(self.j))
+
+
+class jb_wc_result(C.Structure):
+    _fields_ = [("keys", C.POINTER(C.c_uint8)), ("key_off", C.POINTER(C.c_uint64)), ("counts", C.POINTER(C.c_uint64)),
+                ("nkeys", C.c_uint64), ("nbad", C.c_uint64), ("nlong", C.c_uint64), ("ndropped", C.c_uint64),
+                ("ncollided", C.c_uint64), ("ntokens", C.c_uint64)]
+
+
+class WcResult:
+    """A word-count result: keys (a list of bytes, by count descending, then by bytes), counts (uint64, one per
+    key) and the five totals of the rule (bad, long, dropped, collided, tokens)."""
+
+    def __init__(self, r):
+        n = r.nkeys
+        off = np.ctypeslib.as_array(r.key_off, (n + 1,)).tolist()
+        raw = bytes(np.ctypeslib.as_array(r.keys, (max(off[n], 1),))[:off[n]])
+        self.keys = [raw[off[i]:off[i + 1]] for i in range(n)]
+        self.counts = np.ctypeslib.as_array(r.counts, (max(n, 1),))[:n].copy()
+        self.bad, self.long, self.dropped, self.collided, self.tokens = (
+            r.nbad, r.nlong, r.ndropped, r.ncollided, r.ntokens)
+
+    def __repr__(self):
+        return (f"WcResult({len(self.keys)} keys, tokens={self.tokens}, bad={self.bad}, long={self.long}, "
+                f"dropped={self.dropped}, collided={self.collided})")
 
 
 class jb_spans(C.Structure):
@@ -228,6 +254,23 @@ def lib():
                                           vp, vp, vp, vp, C.c_size_t]
         L.jb_cut_batch_charspans.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp,
                                              C.POINTER(C.c_uint64), vp]
+        L.jb_wc_table_bytes.restype = C.c_size_t
+        L.jb_wc_table_bytes.argtypes = [C.c_uint64, C.c_uint64]
+        L.jb_wc_work_bytes.restype = C.c_size_t
+        L.jb_wc_work_bytes.argtypes = [C.c_uint64]
+        L.jb_wc_fp.restype = C.c_uint64
+        L.jb_wc_fp.argtypes = [vp, C.c_size_t, C.c_uint32]
+        L.jb_wc_init_device.argtypes = [vp, vp, C.c_size_t, C.c_uint64, C.c_uint64, vp]
+        L.jb_wc_add_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, C.c_size_t]
+        L.jb_wc_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint64, C.c_uint64, C.POINTER(jb_wc_result)]
+        L.jb_wc_result_free.argtypes = [C.POINTER(jb_wc_result)]
+        L.jb_wc_result_free.restype = None
+        L.jb_wc_count.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                  C.POINTER(jb_wc_result)]
+        L.jb_wc_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, vp, C.c_size_t]
+        L.jb_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
+        L.jb_device_free.argtypes = [vp, vp]
+        L.jb_device_free.restype = None
         _lib = L
     return _lib
 
@@ -918,6 +961,82 @@ class Tokenizer:
                 out.append([(t[cs[k]:ce[k]], cs[k], ce[k]) for k in range(dtok[d], dtok[d + 1])])
         return out
 
+    # -- word counts and vocabulary fitting --------------------------------
+    def wc_init_device(self, d_table, ntable, nslots, pool_bytes, stream_ptr=0):
+        """jb_wc_init_device: an empty word-count table of nslots slots (a power of two >= 8) and pool_bytes of
+        pool in the device buffer d_table (ntable >= wc_table_bytes(nslots, pool_bytes) bytes, 32-byte aligned)."""
+        _check(lib().jb_wc_init_device(self.h, C.c_void_p(d_table), ntable, nslots, pool_bytes, C.c_void_p(stream_ptr)))
+
+    def wc_add_device(self, d_table, ntable, d_text_ptr, nbytes, d_start, d_end, d_ntok, cap, d_work, nwork,
+                      stream_ptr=0):
+        """jb_wc_add_device over raw device pointers: the tokens k < min(*d_ntok, cap) of a span list of any mode
+        added to the table; queued on the stream.  d_work: wc_work_bytes(cap) bytes."""
+        _check(lib().jb_wc_add_device(self.h, C.c_void_p(d_table), ntable, C.c_void_p(d_text_ptr), nbytes,
+                                      C.c_void_p(d_start), C.c_void_p(d_end), C.c_void_p(d_ntok), cap,
+                                      C.c_void_p(stream_ptr), C.c_void_p(d_work), nwork))
+
+    def wc_read(self, d_table, ntable, min_count=1, max_keys=0, stream_ptr=0):
+        """jb_wc_read: synchronise the stream and read the table back sorted: a WcResult.  The table stays as it is."""
+        r = jb_wc_result()
+        _check(lib().jb_wc_read(self.h, C.c_void_p(d_table), ntable, C.c_void_p(stream_ptr), min_count, max_keys,
+                                C.byref(r)))
+        try:
+            return WcResult(r)
+        finally:
+            lib().jb_wc_result_free(C.byref(r))
+
+    def wc_batch(self, buf, doc_off, hmm, d_table, ntable, mode="cut"):
+        """jb_wc_batch: a host batch cut in `mode` ("cut", "search", "full" or a JB_MODE_* value; full mode
+        ignores hmm) and added to the table."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        if isinstance(mode, str):
+            if mode not in _MODES:
+                raise ValueError(f"mode {mode!r}: one of 'cut', 'search', 'full'")
+            mode = _MODES[mode]
+        _check(lib().jb_wc_batch(self.h, buf.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1, int(hmm), int(mode),
+                                 C.c_void_p(d_table), ntable))
+
+    def word_counts(self, batches, mode="cut", hmm=True, min_count=1, max_keys=0, nslots=1 << 22,
+                    pool_bytes=16 << 20, strict=True):
+        """Counter(cut(text)) over a corpus given as an iterable of batches, each a list of documents (str /
+        bytes): (keys, counts), the distinct tokens as bytes by count descending, then by bytes, with their
+        uint64 counts.  The counting runs on the GPU in a table of nslots slots (new keys are accepted while
+        fewer than half are taken) and pool_bytes for keys over 24 bytes.  When tokens were dropped for lack of
+        room or two keys shared a fingerprint, the counts are lower bounds: JbError, unless strict is False."""
+        r = self._word_counts(batches, mode, hmm, min_count, max_keys, nslots, pool_bytes, strict)
+        return r.keys, r.counts
+
+    def _word_counts(self, batches, mode, hmm, min_count, max_keys, nslots, pool_bytes, strict):
+        ntable = wc_table_bytes(nslots, pool_bytes)
+        d_table = C.c_void_p()
+        _check(lib().jb_device_alloc(self.h, ntable, C.byref(d_table)))
+        try:
+            self.wc_init_device(d_table.value, ntable, nslots, pool_bytes)
+            for batch in batches:
+                docs = [_b(t) for t in batch]
+                if not docs:
+                    continue
+                off = np.zeros(len(docs) + 1, np.uint64)
+                off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+                self.wc_batch(np.frombuffer(b"".join(docs) + b"\0", np.uint8), off, hmm, d_table.value, ntable, mode)
+            r = self.wc_read(d_table.value, ntable, min_count, max_keys)
+        finally:
+            lib().jb_device_free(self.h, d_table)
+        if strict and (r.dropped or r.collided):
+            raise JbError(JB_ELIMIT, f"word_counts: {r.dropped} tokens dropped for lack of room and {r.collided} in "
+                                     f"fingerprint collisions: the counts are lower bounds (raise nslots / "
+                                     f"pool_bytes, or pass strict=False)")
+        return r
+
+    def fit_vocab(self, batches, mode="cut", hmm=True, min_count=1, max_keys=0, nslots=1 << 22, pool_bytes=16 << 20,
+                  strict=True):
+        """word_counts, then set_vocab with the keys (a key's id is its rank): (keys, counts).  Afterwards ids,
+        terms, IDF and keywords run on the corpus with no token string having reached the host."""
+        keys, counts = self.word_counts(batches, mode, hmm, min_count, max_keys, nslots, pool_bytes, strict)
+        self.set_vocab(keys)
+        return keys, counts
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -1106,6 +1225,40 @@ def join(text, starts, ends, doc_tok, sep=b" ", term=b"\n", ntok=None, cap=None,
     out = np.empty(max(out_cap, 1), np.uint8)
     call(out, out_cap)
     return out[:out_cap], off, n.value
+
+
+def wc_table_bytes(nslots, pool_bytes):
+    """jb_wc_table_bytes: bytes of a word-count table of nslots slots and pool_bytes of pool (host only)."""
+    return lib().jb_wc_table_bytes(nslots, pool_bytes)
+
+
+def wc_work_bytes(max_tokens):
+    """jb_wc_work_bytes: bytes of the work buffer jb_wc_add_device needs (host only)."""
+    return lib().jb_wc_work_bytes(max_tokens)
+
+
+def wc_fp(key, bits=64):
+    """jb_wc_fp (host only): the fingerprint of a key (1 .. 255 bytes) that keeps the hash's low `bits` bits."""
+    k = _b(key)
+    return lib().jb_wc_fp(k, len(k), bits)
+
+
+def wc_count(text, starts, ends, ntok=None, cap=None, nbytes=None, min_count=1, max_keys=0):
+    """jb_wc_count (host only): the word-count rule of jiebahip.h on host arrays (text bytes or a uint8 array,
+    u32 spans): a WcResult."""
+    t = np.ascontiguousarray(text, np.uint8) if isinstance(text, np.ndarray) else np.frombuffer(_b(text), np.uint8)
+    s = np.ascontiguousarray(starts, np.uint32)
+    e = np.ascontiguousarray(ends, np.uint32)
+    cap = len(s) if cap is None else cap
+    ntok = len(s) if ntok is None else ntok
+    nbytes = len(t) if nbytes is None else nbytes
+    r = jb_wc_result()
+    _check(lib().jb_wc_count(t.ctypes.data if len(t) else None, nbytes, s.ctypes.data if len(s) else None,
+                             e.ctypes.data if len(e) else None, ntok, cap, min_count, max_keys, C.byref(r)))
+    try:
+        return WcResult(r)
+    finally:
+        lib().jb_wc_result_free(C.byref(r))
 
 
 def _unit(unit):
