@@ -1,27 +1,35 @@
 """A shadow model of one long-lived tokenizer, and a generator of call sequences: a helper, not a test.
 
 Model answers every call of a sequence from the references the suite already trusts (Oracle.cut_batch,
-search_ref, full_ref, vocab_ref, terms_ref, df_ref, textrank_ref) and keeps what a jb_ctx keeps between
-calls: the dictionary (an Oracle that add_word changes), the vocabulary (a Python dict) with its keep mask
-and weights, and the token count jb_last_stats owes the caller.  It never calls the library.
+search_ref, full_ref, vocab_ref, terms_ref, df_ref, textrank_ref, join_ref, charspans_ref, wc_ref) and keeps
+what a jb_ctx keeps between calls: the dictionary (an Oracle that add_word changes), the vocabulary (a Python
+dict) with its keep mask and weights, and the token count jb_last_stats owes the caller; and what a caller
+keeps beside it, the word-count table (a Counter that only grows).  It never calls the library.
 
 gen_ops(seed, nsteps) draws a sequence of plain tuples (see OPS); make_batch turns a tuple's batch
 specification into text.  coverage(ops) says which of the transitions between calls a sequence contains;
 test_ctx_model.py pins the seeds that test_gpu_sequences.py runs to the ones that contain them all.
+gen_ops2 / coverage2 / SEEDS2 are the same over OPS2, which adds the calls of joined text, character offsets
+and word counts; gen_ops' own output is pinned by a digest in test_ctx_model.py.
 """
 import random
 import re
 
+from collections import Counter
+
 import numpy as np
 
+import charspans_ref as CR
 import df_ref as DR
 import full_ref as F
+import join_ref as JR
 import oracle as O
 import search_ref as R
 import synth
 import terms_ref as TR
 import textrank_ref as KR
 import vocab_ref as V
+import wc_ref as W
 
 UNK = V.UNK
 MODES = ("plain", "search", "full")
@@ -37,6 +45,17 @@ VOCAB_SOURCE = ("small", 1700, 40 << 10)  # the batch whose tokens the vocabular
 # covered(): swap one for a seed that misses a transition and that test fails.
 SEEDS = (6, 24, 38)
 NSTEPS = 40
+# The second op set: the calls of joined text, character offsets and word counts among the older ones.
+NEW_BATCH_OPS = ("join_batch", "charspans_batch", "wc_batch")
+ALL_BATCH_OPS = BATCH_OPS + NEW_BATCH_OPS
+OPS2 = OPS + NEW_BATCH_OPS + ("join", "charspans", "wc_read")
+UNITS = {"rune": CR.RUNE, "utf16": CR.UTF16}
+LIB_MODE = {"plain": "cut", "search": "search", "full": "full"}  # the binding's names of MODES
+SEEDS2 = (1308, 1931, 3045)  # gen_ops2(seed, NSTEPS2); held to covered2() by test_ctx_model.py
+NSTEPS2 = 60
+# The word-count table of a sequence (one for all its wc_batch calls); test_ctx_model.py asserts from the
+# model that no sequence fills a quarter of the slots or half of the pool.
+WC_NSLOTS, WC_POOL = 1 << 18, 1 << 20
 
 
 # ---- batches ---------------------------------------------------------------------------------------------
@@ -122,6 +141,8 @@ class Model:
         self._fresh()
         self._cache = {}
         self._pool = None
+        self.wc = Counter()  # the word-count table: wc_ref's keys, only ever added to
+        self.wc_bad = self.wc_long = self.wc_tokens = 0
 
     def _fresh(self):
         self.grams = R.Grams(self.o)
@@ -247,9 +268,67 @@ class Model:
             self._cache[key] = KR.textrank(ids, d, tid, toff, self.keep, span, iters, topk)
         return self._cache[key]
 
+    # -- joined text, character offsets, word counts: join_ref, charspans_ref and wc_ref over the model's spans
+    def join(self, batch, mode, hmm, sep, term):
+        """jb_cut_batch_join -> (the output's bytes, out_doc_off as a list)."""
+        hmm = bool(hmm) and mode != "full"
+        s, e, d = self.cut(batch, mode, hmm)
+        key = (batch.spec, "join", mode, hmm, self.version, sep, term)
+        if key not in self._cache:
+            self._cache[key] = JR.join_ref(batch.buf[:int(batch.off[-1])], s, e, d, sep, term)
+        return self._cache[key]
+
+    def charspans(self, batch, mode, hmm, unit):
+        """jb_cut_batch_charspans -> (cstart, cend, doc_tok, doc_units)."""
+        hmm = bool(hmm) and mode != "full"
+        s, e, d = self.cut(batch, mode, hmm)
+        key = (batch.spec, "charspans", mode, hmm, self.version, unit)
+        if key not in self._cache:
+            cs, ce, un = CR.charspans_ref(batch.buf[:int(batch.off[-1])], batch.off, s, e, d, UNITS[unit])
+            self._cache[key] = (np.array(cs, np.uint32), np.array(ce, np.uint32), d, np.array(un, np.uint32))
+        return self._cache[key]
+
+    def wc_add(self, text, starts, ends, ntok=None, cap=None, nbytes=None):
+        """jb_wc_add_device: the spans' keys into the table."""
+        r = W.wc_ref(text, starts, ends, ntok, cap, nbytes)
+        self.wc.update(r.all)
+        self.wc_bad += r.bad
+        self.wc_long += r.long
+        self.wc_tokens += r.tokens
+
+    def wc_batch(self, batch, mode, hmm):
+        """jb_wc_batch: the batch's tokens in the mode into the table, with the dictionary as it is now."""
+        s, e, _ = self.cut(batch, mode, hmm)
+        self.wc_add(batch.buf[:int(batch.off[-1])], s, e)
+
+    def wc_result(self):
+        """What jb_wc_read owes the caller: a wc_ref.Ref of the whole table, in the rule's order."""
+        items = W.order(self.wc)
+        return W.Ref([k for k, _ in items], [v for _, v in items], self.wc_bad, self.wc_long, self.wc_tokens, dict(self.wc))
+
+    def wc_size(self):
+        """(distinct keys, their bytes together): what the table has to hold."""
+        return len(self.wc), sum(len(k) for k in self.wc)
+
 
 # ---- the op generator ---------------------------------------------------------------------------------------
-def gen_ops(seed, nsteps):
+def gen_ops2(seed, nsteps):
+    """gen_ops over OPS2: the same deck with three of each of the six new kinds in it:
+    ("join_batch", mode, hmm, spec, sep, term)           sep, term of join_ref.SEPS
+    ("join", sep, term)                                  jb_join_device on the last device cut's spans
+    ("charspans_batch", mode, hmm, spec, unit, reuse)    unit of UNITS; reuse: into the previous call's span arrays
+    ("charspans", unit, inplace)                         jb_charspans_device on the last device cut's spans
+    ("wc_batch", mode, hmm, spec), ("wc_read",)          one table per sequence
+    The six *_batch kinds alternate together between a batch over 4,096 bytes and one under."""
+    return gen_ops(seed, nsteps, OPS2)
+
+
+def spec_at(op):
+    """The batch specification of a cut or a *_batch op."""
+    return op[4] if op[0] == "cut" else op[3] if op[0] in NEW_BATCH_OPS else op[2]
+
+
+def gen_ops(seed, nsteps, op_set=OPS):
     """nsteps plain tuples:
     ("cut", mode, hmm, route, spec)           mode of MODES, route of ROUTES, spec for make_batch
     ("add_word", k, freq)                     Model.pick_word(k); three of them
@@ -295,7 +374,7 @@ def gen_ops(seed, nsteps):
 
     # The deck: three of every kind but "cut", cuts for the rest, shuffled; the cuts' classes and the *_batch
     # calls' sizes come from decks of their own, so that every class and both orders of size occur.
-    kinds = [k for k in OPS if k != "cut"] * 3
+    kinds = [k for k in op_set if k != "cut"] * 3
     assert nsteps >= len(kinds) + 14
     kinds += ["cut"] * (nsteps - len(kinds))
     rng.shuffle(kinds)
@@ -304,6 +383,10 @@ def gen_ops(seed, nsteps):
     rng.shuffle(cut_cls)
     big = rng.random() < 0.5  # the *_batch calls alternate between a batch over 4,096 bytes and one under
     forced = None  # after one add_word: a tiny plain host cut, then the other two modes
+    if op_set is not OPS:  # (decks of the new kinds' flags; the first set draws nothing here)
+        reuse, inplace = [False, True, True], [True, True, False]
+        rng.shuffle(reuse)
+        rng.shuffle(inplace)
     for kind in kinds:
         if kind == "add_word":
             ops.append((kind, nadd, (10_000_000, 0, 777)[nadd % 3]))
@@ -325,7 +408,7 @@ def gen_ops(seed, nsteps):
             if route != "host" and sp not in dev_specs and sp[0] != "grow":
                 dev_specs.append(sp)
             ops.append((kind, mode, hmm and mode != "full", route, sp))
-        elif kind in BATCH_OPS:
+        elif kind in ALL_BATCH_OPS:
             sp = spec_of(rng.choice(("small", "large", "large", "offset")) if big else rng.choice(("tiny", "tiny", "empty")))
             big = not big
             hmm = rng.random() < 0.5
@@ -333,8 +416,21 @@ def gen_ops(seed, nsteps):
                 ops.append((kind, hmm, sp, rng.choice((1, 5, 20))))
             elif kind == "df_batch":
                 ops.append((kind, hmm, sp))
-            else:
+            elif kind == "textrank_batch":
                 ops.append((kind, hmm, sp, rng.choice((2, 5)), rng.choice((3, 10)), rng.choice((5, 20))))
+            else:
+                mode = rng.choice(MODES)
+                hmm = hmm and mode != "full"
+                if kind == "join_batch":
+                    ops.append((kind, mode, hmm, sp, rng.choice(JR.SEPS), rng.choice(JR.SEPS)))
+                elif kind == "charspans_batch":
+                    ops.append((kind, mode, hmm, sp, rng.choice(sorted(UNITS)), reuse.pop()))
+                else:
+                    ops.append((kind, mode, hmm, sp))
+        elif kind == "join":
+            ops.append((kind, rng.choice(JR.SEPS), rng.choice(JR.SEPS)))
+        elif kind == "charspans":
+            ops.append((kind, rng.choice(sorted(UNITS)), inplace.pop()))
         elif kind == "ids":
             ops.append((kind, rng.choice(("host", "device"))))
         elif kind == "set_vocab":
@@ -400,6 +496,80 @@ def coverage(ops):
             out[op[0] + (":tiny_then_large" if big else ":large_then_tiny")] = True
         prev = big
     return out
+
+
+def dev_state(ops):
+    """Per op, what Driver holds as the last device cut when the op runs: None, or the route of that cut.
+    A device cut stays the last one until another call cuts (a host cut, a *_batch call) or AddWord
+    replaces the image; ids, join, charspans, set_vocab, wc_read and last_stats leave it."""
+    out, cur = [], None
+    for op in ops:
+        out.append(cur)
+        if op[0] == "cut":
+            cur = op[3] if op[3] != "host" else None
+        elif op[0] in ALL_BATCH_OPS or op[0] == "add_word":
+            cur = None
+    return out
+
+
+def coverage2(ops):
+    """coverage() of a sequence over OPS2, with the conditions of the new kinds."""
+    old = coverage([op for op in ops if op[0] in OPS])
+    out = {k: v for k, v in old.items() if ":" not in k}
+    out["kinds"] = {k: sum(1 for op in ops if op[0] == k) for k in OPS2}
+    for op in ops:
+        if op[0] in NEW_BATCH_OPS and op[3][0] in out["classes"]:
+            out["classes"][op[3][0]] += 1
+    # the six *_batch kinds share the arenas: each on both transitions of size among all of them, each new
+    # kind directly after an older one and each older one directly after a new one
+    for k in ALL_BATCH_OPS:
+        out[k + ":large_then_tiny"] = out[k + ":tiny_then_large"] = False
+        out[k + (":after_old" if k in NEW_BATCH_OPS else ":after_new")] = False
+    prev = None
+    for op in ops:
+        if op[0] not in ALL_BATCH_OPS:
+            continue
+        big, new = _large(spec_at(op)[0]), op[0] in NEW_BATCH_OPS
+        if prev is not None:
+            if prev[0] != big:
+                out[op[0] + (":tiny_then_large" if big else ":large_then_tiny")] = True
+            if prev[1] != new:
+                out[op[0] + (":after_old" if new else ":after_new")] = True
+        prev = (big, new)
+    # a wc_batch on each side of an add_word, with a wc_read after both
+    out["wc_around_add"] = False
+    state = 0  # 1: a wc_batch, 2: then an add_word, 3: then a wc_batch
+    for op in ops:
+        if op[0] == "wc_batch" and state in (0, 2):
+            state += 1
+        elif op[0] == "add_word" and state == 1:
+            state = 2
+        elif op[0] == "wc_read" and state == 3:
+            out["wc_around_add"] = True
+    # an in-place charspans on the ctx-owned arrays of a device cut (Driver repeats that cut afterwards)
+    out["charspans_inplace_on_ctx_arrays"] = any(
+        op[0] == "charspans" and op[2] and st == "device" for op, st in zip(ops, dev_state(ops)))
+    # a charspans_batch with reuse whose span arrays are too small: those of a call on at most 4,096 bytes
+    # (at most 4,096 entries, grown or not), handed to a large batch (over 64 KiB: more tokens than that)
+    out["charspans_reuse_too_small"] = False
+    cap_small = False  # whether the kept arrays are known to have at most 4,096 entries
+    for op in ops:
+        if op[0] != "charspans_batch":
+            continue
+        small = op[3][0] in ("tiny", "empty") and op[1] != "full"
+        if not op[5]:
+            cap_small = small
+        elif cap_small and op[3][0] == "large":
+            out["charspans_reuse_too_small"], cap_small = True, False
+        else:
+            cap_small = cap_small and small
+    return out
+
+
+def covered2(ops, min_kind=3, min_class=2):
+    c = coverage2(ops)
+    return (all(v >= min_kind for v in c["kinds"].values()) and all(v >= min_class for v in c["classes"].values()) and
+            all(v for k, v in c.items() if k not in ("kinds", "classes")))
 
 
 def covered(ops, min_kind=3, min_class=2):

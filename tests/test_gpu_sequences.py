@@ -4,15 +4,24 @@ ids, counters, keyword records with their f32 score bits, kw_n and jb_last_stats
 What the sequences cross is the state a jb_ctx keeps between calls: the grow-only workspace and the buffers
 that follow it, the three captured graphs, the image AddWord swaps in (with full mode's look-back reach),
 the vocabulary, the four arenas of the *_batch calls, and the flags behind jb_last_stats (DESIGN.md,
-"One context over many calls")."""
+"One context over many calls").  The second half does the same for joined text, character offsets and word
+counts: their batch calls carve the same arenas in another layout (and four more), move the span arrays into
+the ids/terms arena when a full-mode list outgrows its batch, overwrite span arrays in place, hand out a
+pinned block that one process-wide cache recycles, and add to a table the caller keeps; join_ref,
+charspans_ref and wc_ref over the model's spans answer them, byte for byte."""
+import gc
+
 import numpy as np
 import pytest
 
+import charspans_ref as CR
 import ctx_model as M
 import full_ref as F
 import jiebahip as J
+import join_ref as JR
 import search_ref as R
 import synth
+import wc_ref as W
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +67,20 @@ def inner(t, n, dtype):
     return a[NG:NG + n].view(dtype)
 
 
+def guarded_bytes(n):
+    import torch
+    t = torch.full((n + 2 * NG,), JUNK & 0xFF, dtype=torch.uint8, device="cuda")
+    t[:NG] = GUARD & 0xFF
+    t[NG + n:] = GUARD & 0xFF
+    return t
+
+
+def inner_bytes(t, n):
+    a = t.cpu().numpy()
+    assert (a[:NG] == GUARD & 0xFF).all() and (a[NG + n:] == GUARD & 0xFF).all(), "written outside a caller-owned output"
+    return a[NG:NG + n]
+
+
 # ---- the driver: makes the library's call and the model's, and compares ------------------------------------
 class Dev:
     """A batch on the device, kept for the whole sequence: a repeat finds the same pointers."""
@@ -76,11 +99,17 @@ class Dev:
 
 
 class Driver:
-    def __init__(self, tk, model, s=None):
+    def __init__(self, tk, model, s=None, wc_sizes=(M.WC_NSLOTS, M.WC_POOL)):
         self.tk, self.m, self.s = tk, model, s
         self.batches, self.devs = {}, {}
         self.last = None  # the last cut: (batch, its expected spans)
         self.stream = None
+        # the last device cut while no other call has cut since (ctx_model.dev_state): where its spans lie
+        self.lastdev = None
+        self.wc_sizes, self.table = wc_sizes, None  # one word-count table for the driver's life
+        self.cs_out, self.cs_cap = None, None  # the arrays of the last charspans_batch, and their size
+        self.calls = []  # (kind, bytes of the batch) of every *_batch call
+        self.too_small = self.restored = 0  # charspans_batch retries; cuts repeated after an in-place charspans
 
     def st(self):
         """A stream of the driver's own, for every device call: the library captures a graph only for a
@@ -111,6 +140,7 @@ class Driver:
         label = f"{label} {mode} hmm={hmm} {route} {b.spec}"
         if route == "host":
             tk = self.tk
+            self.lastdev = None
             got = tk.cut_batch_full(b.buf, b.off) if mode == "full" else (
                 tk.cut_batch_search if mode == "search" else tk.cut_batch)(b.buf, b.off, hmm)
             same_spans(got, want, label)
@@ -148,6 +178,7 @@ class Driver:
             assert n == nw, f"{label}: {n} spans, want {nw}"
             got = (inner(o[0], cap, np.uint32)[:n], inner(o[1], cap, np.uint32)[:n], inner(o[2], dv.nd + 1, np.uint64))
             same_spans(got, want, label)
+            self.lastdev = dict(b=b, mode=mode, hmm=hmm, into=True, ptrs=tuple(p), cap=cap, outs=o)
             return
         st = self.st()
         if mode == "full":
@@ -168,6 +199,7 @@ class Driver:
         got = (J.dev_to_host(ps, 4 * k, np.uint32), J.dev_to_host(pe, 4 * k, np.uint32),
                J.dev_to_host(pd, 8 * (dv.nd + 1), np.uint64))
         same_spans(got, (want[0][:k], want[1][:k], want[2]), label)
+        self.lastdev = dict(b=b, mode=mode, hmm=hmm, into=False, ptrs=(ps, pe, pd, pn), cap=dv.nb, outs=None)
 
     # -- ids of the last cut's spans
     def ids(self, route, label=""):
@@ -197,6 +229,8 @@ class Driver:
     # -- the *_batch calls, into outputs that start as garbage
     def keywords(self, hmm, b, topk, label=""):
         b = self.batch(b)
+        self.lastdev = None
+        self.calls.append(("keywords_batch", b.nbytes))
         w = self.m.weights
         nd = b.ndocs
         ki, ks, kc = (np.full(nd * topk, JUNK, np.uint32) for _ in range(3))
@@ -210,6 +244,8 @@ class Driver:
 
     def df(self, hmm, b, label=""):
         b = self.batch(b)
+        self.lastdev = None
+        self.calls.append(("df_batch", b.nbytes))
         ndf = len(self.m.keys)
         before = (np.arange(ndf, dtype=np.uint32) * np.uint32(2654435761)) >> np.uint32(8)  # (the counters are added to)
         got = self.tk.df_batch(b.buf, b.off, hmm, before.copy())
@@ -218,6 +254,8 @@ class Driver:
 
     def textrank(self, hmm, b, span=5, iters=10, topk=20, label=""):
         b = self.batch(b)
+        self.lastdev = None
+        self.calls.append(("textrank_batch", b.nbytes))
         k = self.m.keep
         nd = b.ndocs
         ki, ks = np.full(nd * topk, JUNK, np.uint32), np.full(nd * topk, JUNK, np.uint32)
@@ -230,9 +268,211 @@ class Driver:
                   f"{label} textrank_batch hmm={hmm} {b.spec} span={span} iters={iters} topk={topk}")
         return got
 
+    # -- joined text, character offsets and word counts of a host batch
+    def join_batch(self, mode, hmm, b, sep, term, label="", buf=None):
+        """jb_cut_batch_join; buf: the batch's bytes at another host address.  Returns the library's array."""
+        b = self.batch(b)
+        self.lastdev = None
+        self.calls.append(("join_batch", b.nbytes))
+        want, woff = self.m.join(b, mode, hmm, sep, term)
+        if self.tk is None:
+            return None
+        label = f"{label} join_batch {mode} hmm={hmm} {b.spec} sep={sep!r} term={term!r}"
+        got, off = self.tk.cut_batch_join(b.buf if buf is None else buf, b.off, hmm, M.LIB_MODE[mode], sep, term)
+        assert off.tolist() == woff, f"{label}: out_doc_off"
+        assert got.tobytes() == want, f"{label}: {len(got)} bytes, want {len(want)}"
+        return got
+
+    def charspans_batch(self, mode, hmm, b, unit, reuse, label="", buf=None):
+        """jb_cut_batch_charspans through Tokenizer.cut_batch_charspans; reuse: into the span arrays of the call
+        before, which the binding replaces after JB_ELIMIT when they are too small."""
+        b = self.batch(b)
+        self.lastdev = None
+        self.calls.append(("charspans_batch", b.nbytes))
+        wcs, wce, wd, wun = self.m.charspans(b, mode, hmm, unit)
+        # the binding's rule: new arrays of max(1024, bytes / 2) entries unless it is handed some, and after
+        # JB_ELIMIT arrays of exactly the count
+        cap = self.cs_cap if reuse and self.cs_cap is not None else max(1024, b.nbytes // 2)
+        if reuse and self.cs_cap is not None and len(wcs) > cap:
+            self.too_small += 1
+        self.cs_cap = max(cap, len(wcs))
+        if self.tk is None:
+            return
+        label = f"{label} charspans_batch {mode} hmm={hmm} {b.spec} {unit} reuse={reuse}"
+        nd, n, out = b.ndocs, len(wcs), None
+        if reuse and self.cs_out is not None:
+            out = (self.cs_out[0], self.cs_out[1], np.full(nd + 1, JUNK, np.uint64), np.full(max(nd, 1), JUNK, np.uint32))
+            out[0][:] = JUNK
+            out[1][:] = JUNK
+        cs, ce, tok, un, kept = self.tk.cut_batch_charspans(b.buf if buf is None else buf, b.off, hmm, M.LIB_MODE[mode],
+                                                            unit, out)
+        if out is not None:
+            assert (kept[0] is out[0]) == (n <= len(out[0])), f"{label}: {n} tokens, arrays of {len(out[0])}"
+            if n > len(out[0]):
+                assert len(kept[0]) == len(kept[1]) == n, label
+            else:  # (nothing past the count is written)
+                assert (out[0][n:] == JUNK).all() and (out[1][n:] == JUNK).all(), f"{label}: written past the count"
+        assert np.array_equal(tok, wd), f"{label}: doc_tok"
+        assert np.array_equal(cs, wcs) and np.array_equal(ce, wce), f"{label}: offsets"
+        assert np.array_equal(un, wun), f"{label}: doc_units"
+        assert len(kept[0]) == self.cs_cap, f"{label}: arrays of {len(kept[0])}, want {self.cs_cap}"
+        self.cs_out = kept
+
+    def wc_table(self):
+        """The driver's table between canaries: (pointer, bytes)."""
+        import torch
+        if self.table is None:
+            nslots, pool = self.wc_sizes
+            n = J.wc_table_bytes(nslots, pool)
+            t = guarded_bytes(n)
+            assert (t.data_ptr() + NG) % 32 == 0
+            self.tk.wc_init_device(t.data_ptr() + NG, n, nslots, pool, self.st())
+            torch.cuda.synchronize()
+            self.table = (t, n)
+        return self.table[0].data_ptr() + NG, self.table[1]
+
+    def wc_batch(self, mode, hmm, b, label="", buf=None):
+        b = self.batch(b)
+        self.lastdev = None
+        self.calls.append(("wc_batch", b.nbytes))
+        self.m.wc_batch(b, mode, hmm)
+        if self.tk is None:
+            return
+        ptr, n = self.wc_table()
+        self.tk.wc_batch(b.buf if buf is None else buf, b.off, hmm, ptr, n, M.LIB_MODE[mode])
+
+    def wc_read(self, label=""):
+        """jb_wc_read against the model's Counter: keys, counts, order and the five totals; nothing dropped."""
+        import torch
+        if self.tk is None:
+            return None
+        ptr, n = self.wc_table()
+        got = self.tk.wc_read(ptr, n, 1, 0, self.st())
+        torch.cuda.synchronize()
+        t = self.table[0]
+        assert (t[:NG].cpu().numpy() == GUARD & 0xFF).all() and (t[NG + n:].cpu().numpy() == GUARD & 0xFF).all(), \
+            "written outside the table"
+        assert got.dropped == 0 and got.collided == 0, f"{label} wc_read: {got!r}"
+        diff = W.same(got, self.m.wc_result())
+        assert diff is None, f"{label} wc_read: {diff}"
+        return got
+
+    # -- jb_join_device, jb_charspans_device and jb_wc_add_device on the last cut's spans
+    def spans_host(self):
+        """(batch, starts, ends, doc_tok, ntok, cap) of the span list those calls are given, relative to the
+        batch's first byte: the last device cut's arrays while they hold (lastdev), else the last cut's spans
+        with three the kernels must not trust behind them, as Driver.ids uploads them."""
+        if self.lastdev is not None:
+            b, cap = self.lastdev["b"], self.lastdev["cap"]
+            ws, we, wd = self.m.cut(b, self.lastdev["mode"], self.lastdev["hmm"], count=False)
+            base = np.uint64(int(b.off[0]))
+            return b, (ws - base)[:cap].astype(np.uint32), (we - base)[:cap].astype(np.uint32), wd, len(ws), cap
+        if self.last is None:
+            return None
+        b, (ws, we, wd) = self.last
+        base = np.uint64(int(b.off[0]))
+        s = np.concatenate([ws - base, np.array([3, 9, b.nbytes], np.uint64)]).astype(np.uint32)
+        e = np.concatenate([we - base, np.array([3, 6, b.nbytes + 3], np.uint64)]).astype(np.uint32)
+        return b, s, e, wd, len(s), len(s)
+
+    def spans_dev(self, s, e, wd, ntok):
+        """Device pointers (start, end, doc_tok, ntok) of spans_host's list, and what keeps them alive."""
+        import torch
+        if self.lastdev is not None:
+            return self.lastdev["ptrs"], self.lastdev["outs"]
+        n = len(s)
+        keep = (guarded(n, torch.int32), guarded(n, torch.int32), torch.from_numpy(wd.astype(np.int64)).cuda(),
+                torch.tensor([ntok], dtype=torch.int64, device="cuda"))
+        keep[0][NG:NG + n] = torch.from_numpy(s.view(np.int32).copy()).cuda()
+        keep[1][NG:NG + n] = torch.from_numpy(e.view(np.int32).copy()).cuda()
+        return (keep[0].data_ptr() + 4 * NG, keep[1].data_ptr() + 4 * NG, keep[2].data_ptr(), keep[3].data_ptr()), keep
+
+    def join(self, sep, term, label=""):
+        import torch
+        src = self.spans_host()
+        if src is None or self.tk is None:
+            return
+        b, s, e, wd, ntok, cap = src
+        dv = self.dev(b)
+        label = f"{label} join {b.spec} sep={sep!r} term={term!r}"
+        want, woff = JR.join_ref(b.rel()[0][:dv.nb], s, e, wd, sep, term, ntok, cap, dv.nb)
+        ptrs, keep = self.spans_dev(s, e, wd, ntok)
+        nwork = J.join_work_bytes(cap, dv.nd)
+        out, ooff, nout, work = (guarded_bytes(len(want)), guarded(dv.nd + 1, torch.int64), guarded(1, torch.int64),
+                                 guarded_bytes(nwork))
+        self.tk.join_device(dv.text.data_ptr(), dv.nb, ptrs[0], ptrs[1], ptrs[2], ptrs[3], cap, dv.nd, sep, term,
+                            out.data_ptr() + NG, len(want), ooff.data_ptr() + 8 * NG, nout.data_ptr() + 8 * NG,
+                            work.data_ptr() + NG, nwork, self.st())
+        torch.cuda.synchronize()
+        inner_bytes(work, nwork)
+        assert int(inner(nout, 1, np.uint64)[0]) == len(want), f"{label}: nout"
+        assert inner(ooff, dv.nd + 1, np.uint64).tolist() == woff, f"{label}: out_doc_off"
+        assert inner_bytes(out, len(want)).tobytes() == want, f"{label}: bytes"
+
+    def charspans(self, unit, inplace, label=""):
+        """jb_charspans_device; in place it overwrites the span arrays, and when those were a device cut's the
+        same cut is made again afterwards: byte spans must be back."""
+        import torch
+        src = self.spans_host()
+        if src is None or self.tk is None:
+            self.restored += self.tk is None and inplace and self.lastdev is not None
+            return
+        b, s, e, wd, ntok, cap = src
+        dv = self.dev(b)
+        label = f"{label} charspans {b.spec} {unit} inplace={inplace}"
+        n = min(ntok, cap)
+        wcs, wce, wun = CR.charspans_ref(b.rel()[0][:dv.nb], b.rel()[1], s, e, wd, M.UNITS[unit], ntok, cap)
+        ptrs, keep = self.spans_dev(s, e, wd, ntok)
+        nwork = J.charspans_work_bytes(dv.nb, dv.nd)
+        units, work = guarded(dv.nd, torch.int32), guarded_bytes(nwork)
+        if inplace:
+            pcs, pce = ptrs[0], ptrs[1]
+        else:
+            ocs, oce = guarded(cap, torch.int32), guarded(cap, torch.int32)
+            pcs, pce = ocs.data_ptr() + 4 * NG, oce.data_ptr() + 4 * NG
+        self.tk.charspans_device(dv.text.data_ptr(), dv.nb, dv.off.data_ptr(), dv.nd, ptrs[0], ptrs[1], ptrs[2], ptrs[3],
+                                 cap, unit, pcs, pce, units.data_ptr() + 4 * NG, work.data_ptr() + NG, nwork, self.st())
+        torch.cuda.synchronize()
+        inner_bytes(work, nwork)
+        assert inner(units, dv.nd, np.uint32).tolist() == wun, f"{label}: doc_units"
+        if not inplace:
+            gcs, gce = inner(ocs, cap, np.uint32), inner(oce, cap, np.uint32)
+            assert (gcs[n:] == JUNK).all() and (gce[n:] == JUNK).all(), f"{label}: written past the count"
+        elif keep is None:  # (the ctx-owned arrays)
+            gcs, gce = J.dev_to_host(ptrs[0], 4 * n, np.uint32), J.dev_to_host(ptrs[1], 4 * n, np.uint32)
+        else:
+            gcs, gce = inner(keep[0], len(keep[0]) - 2 * NG, np.uint32), inner(keep[1], len(keep[1]) - 2 * NG, np.uint32)
+        assert gcs[:n].tolist() == wcs and gce[:n].tolist() == wce, f"{label}: offsets"
+        if inplace and self.lastdev is not None:
+            ld = self.lastdev
+            self._device(ld["mode"], ld["hmm"], b, self.m.cut(b, ld["mode"], ld["hmm"], count=False), ld["into"],
+                         f"{label}: the cut again")
+            self.restored += 1
+
+    def wc_add(self, label=""):
+        """jb_wc_add_device on the last cut's spans, into the driver's table."""
+        import torch
+        src = self.spans_host()
+        if src is None:
+            return
+        b, s, e, wd, ntok, cap = src
+        self.m.wc_add(b.rel()[0][:b.nbytes], s, e, ntok, cap, b.nbytes)
+        if self.tk is None:
+            return
+        dv = self.dev(b)
+        ptrs, keep = self.spans_dev(s, e, wd, ntok)
+        ptr, nt = self.wc_table()
+        nwork = J.wc_work_bytes(cap)
+        work = guarded_bytes(nwork)
+        self.tk.wc_add_device(ptr, nt, dv.text.data_ptr(), dv.nb, ptrs[0], ptrs[1], ptrs[3], cap, work.data_ptr() + NG,
+                              nwork, self.st())
+        torch.cuda.synchronize()
+        inner_bytes(work, nwork)
+
     # -- the rest
     def add_word(self, word, freq):
         assert self.m.reachable(word), word  # (every word these tests add becomes an edge of buildDag)
+        self.lastdev = None
         self.tk.AddWord(word, freq)
         f = self.m.add_word(word, freq)
         assert self.m.is_edge(word), word
@@ -267,8 +507,64 @@ class Driver:
             self.textrank(op[1], op[2], *op[3:])
         elif k == "last_stats":
             self.stats()
+        elif k == "join_batch":
+            self.join_batch(*op[1:])
+        elif k == "join":
+            self.join(op[1], op[2])
+        elif k == "charspans_batch":
+            self.charspans_batch(*op[1:])
+        elif k == "charspans":
+            self.charspans(op[1], op[2])
+        elif k == "wc_batch":
+            self.wc_batch(op[1], op[2], op[3])
+        elif k == "wc_read":
+            self.wc_read()
         else:
             raise ValueError(op)
+
+
+class DryDriver(Driver):
+    """A Driver without a library: the model's side of every call and nothing else.  test_ctx_model.py runs the
+    scripts below through it on the CPU, to see what their word-count tables have to hold."""
+
+    def __init__(self, model, s=None):
+        super().__init__(None, model, s)
+
+    def cut(self, mode, hmm, route, b, reps=None, label=""):
+        b = self.batch(b)
+        want = self.m.cut(b, mode, hmm)
+        self.last = (b, want)
+        into = route == "device_into"
+        self.lastdev = None if route == "host" else dict(
+            b=b, mode=mode, hmm=hmm, into=into, ptrs=None, outs=None,
+            cap=max(len(want[0]), b.nbytes, 1) if into else b.nbytes)
+        return want
+
+    def _batch_call(self, kind, b):
+        self.lastdev = None
+        self.calls.append((kind, self.batch(b).nbytes))
+
+    def ids(self, route, label=""):
+        pass
+
+    def keywords(self, hmm, b, topk, label=""):
+        self._batch_call("keywords_batch", b)
+
+    def df(self, hmm, b, label=""):
+        self._batch_call("df_batch", b)
+
+    def textrank(self, hmm, b, span=5, iters=10, topk=20, label=""):
+        self._batch_call("textrank_batch", b)
+
+    def add_word(self, word, freq):
+        self.lastdev = None
+        self.m.add_word(word, freq)
+
+    def set_vocab(self, keys):
+        self.m.set_vocab(keys)
+
+    def stats(self, label=""):
+        pass
 
 
 # ---- fixtures -------------------------------------------------------------------------------------------------
@@ -291,15 +587,24 @@ def mini(mini_paths):
     return d if d.endswith("\n") else d + "\n", e
 
 
-def open_20k(syn):
+def open_20k(syn, wc_sizes=(M.WC_NSLOTS, M.WC_POOL)):
     d, e, s, source = syn
     tk = J.Tokenizer(J.make_config(dict_bytes=d, emit_bytes=e))
-    return Driver(tk, M.Model(d, e, source=source), s)
+    return Driver(tk, M.Model(d, e, source=source), s, wc_sizes)
 
 
-def open_text(dict_text, emit):
+def open_text(dict_text, emit, wc_sizes=(M.WC_NSLOTS, M.WC_POOL)):
     tk = J.Tokenizer(J.make_config(dict_bytes=dict_text.encode(), emit_bytes=emit))
-    return Driver(tk, M.Model(dict_text.encode(), emit))
+    return Driver(tk, M.Model(dict_text.encode(), emit), None, wc_sizes)
+
+
+def dry_20k(syn):
+    d, e, s, source = syn
+    return DryDriver(M.Model(d, e, source=source), s)
+
+
+def dry_text(dict_text, emit):
+    return DryDriver(M.Model(dict_text.encode(), emit))
 
 
 def at_edge(d, run, before="a", after="b"):
@@ -638,5 +943,344 @@ def test_random_sequences(syn, seed):
                 dr.run(op)
             except (AssertionError, J.JbError) as e:
                 raise AssertionError(f"seed {seed}, step {i}: {op!r}\nops = {ops[:i + 1]!r}\n{e}") from e
+    finally:
+        dr.tk.close()
+
+
+# ---- joined text, character offsets and word counts among the older calls --------------------------------------
+# Each script takes a Driver and makes the calls; the test opens a tokenizer for it.  test_ctx_model.py runs the
+# scripts that fill a word-count table through a DryDriver first: the table must never be what limits a test.
+def arena_order(first, second):
+    """19 kinds, alternately of `first` and of `second` (three kinds each): every ordered pair of one of
+    `first` followed by one of `second`, and every pair the other way round, is a neighbouring pair."""
+    seq = []
+    for shift in range(3):
+        for i in range(3):
+            seq += [first[i], second[(i + shift) % 3]]
+    return seq + [first[0]]
+
+
+def arena_pairs(calls):
+    """{(kind, next kind, tiny_then_large)} of the neighbouring *_batch calls that cross 4,096 bytes."""
+    return {(k0, k1, n1 > M.SMALL_MAX) for (k0, n0), (k1, n1) in zip(calls, calls[1:])
+            if (n0 > M.SMALL_MAX) != (n1 > M.SMALL_MAX)}
+
+
+def script_arenas(dr):
+    m = dr.m
+    big = dr.batch(("large", 1700, 200 << 10))
+    one, none = M.from_texts(("one",), ["中"]), dr.batch(("empty", 0, 5))
+    tail = M.Batch(("tail",), big.buf, big.off[3:])
+    assert big.nbytes > 150 << 10 and one.nbytes == 3 and none.nbytes == 0 and none.ndocs == 5 and int(tail.off[0]) > 0
+    v1, v2 = m.vocab_keys(0), m.vocab_keys(1)
+    assert len(v2) < len(v1)
+    # (a large batch keeps one mode per kind, so that the references are few; the tiny ones take them in turn)
+    modes = {("join_batch", big.spec): "plain", ("join_batch", tail.spec): "search",
+             ("charspans_batch", big.spec): "search", ("charspans_batch", tail.spec): "full",
+             ("wc_batch", big.spec): "full", ("wc_batch", tail.spec): "plain"}
+    step = [0]
+
+    def call(kind, b):
+        i = step[0]
+        step[0] += 1
+        label = f"call {i}"
+        mode = modes.get((kind, b.spec), M.MODES[i % 3])
+        hmm = mode != "full" and (b.nbytes > M.SMALL_MAX or i % 2 == 0)
+        if kind == "keywords_batch":
+            dr.keywords(True, b, 20, label)
+        elif kind == "df_batch":
+            dr.df(True, b, label)
+        elif kind == "textrank_batch":
+            dr.textrank(True, b, label=label)
+        elif kind == "join_batch":
+            dr.join_batch(mode, hmm, b, JR.SEPS[i % 4], JR.SEPS[(i + 1) % 4], label)
+        elif kind == "charspans_batch":
+            # (new arrays for a tiny batch, 1,024 entries; a large one is handed the arrays of the call before)
+            dr.charspans_batch(mode, hmm, b, ("rune", "utf16")[i % 2], b.nbytes > M.SMALL_MAX, label)
+        else:
+            dr.wc_batch(mode, hmm, b, label)
+        dr.stats(label)
+
+    dr.set_vocab(v1)
+    # the five batches of test_batch_calls_share_their_buffers in their order, a kind of each set in turn
+    for kind, b in zip(("keywords_batch", "join_batch", "df_batch", "charspans_batch", "textrank_batch", "wc_batch"),
+                       (big, one, none, tail, big, big)):
+        call(kind, b)
+    # then the sizes alternate: an older kind on each large batch and a new kind on each tiny one, ...
+    for k, kind in enumerate(arena_order(M.BATCH_OPS, M.NEW_BATCH_OPS)):
+        call(kind, ((big, tail)[(k // 2) % 2], (one, none)[(k // 2) % 2])[k % 2])
+    dr.wc_read("half way")
+    dr.set_vocab(v2)
+    # ... and the other way round
+    for k, kind in enumerate(arena_order(M.NEW_BATCH_OPS, M.BATCH_OPS)):
+        if k == 14:
+            dr.add_word(m.pick_word(0, big), 10_000_000)
+            dr.stats("after AddWord")
+        call(kind, ((big, tail)[(k // 2) % 2], (one, none)[(k // 2) % 2])[k % 2])
+    dr.wc_read("at the end")
+    want = {(a, b, up) for a in M.BATCH_OPS for b in M.NEW_BATCH_OPS for up in (False, True)}
+    want |= {(b, a, up) for a, b, up in want}
+    assert len(want) == 36 and want <= arena_pairs(dr.calls), sorted(want - arena_pairs(dr.calls))
+    assert dr.too_small >= 1  # (the span arrays of a tiny batch were handed to a large one)
+
+
+def test_new_batch_calls_share_the_arenas(syn):
+    """The six *_batch kinds on one ctx with a vocabulary, over a 200 KiB batch, one 3-byte document, five empty
+    documents and the large buffer from its document 3 on, a smaller vocabulary and an AddWord in between,
+    jb_last_stats after every call: every ordered pair of an older kind and a new one, both ways round, lies on
+    a large-then-tiny and on a tiny-then-large transition (asserted from the driver's call list)."""
+    dr = open_20k(syn)
+    try:
+        script_arenas(dr)
+    finally:
+        dr.tk.close()
+
+
+REGROW_K, REGROW_N = 5, 11  # the smallest chain and run whose full-mode list is longer than the text (test_ctx_model.py)
+
+
+def regrow_dict(mini_text):
+    return F.chain_dict(REGROW_K) + mini_text
+
+
+def script_regrow(dr):
+    m = dr.m
+    full = M.from_texts(("regrow",), ["甲" * REGROW_N])
+    tiny = M.from_texts(("mini",), ["今天天氣很好", "", "一刹那，量子力學"])
+    smaller = M.from_texts(("smaller",), ["甲" * 3 + "很好"])
+    fs, fe, _ = m.cut(full, "full", False, count=False)
+    assert len(fs) > full.nbytes and smaller.nbytes < full.nbytes  # (from full_ref.expected: the call cuts twice)
+    keys = set()
+    for b in (full, tiny, smaller):
+        s, e, _ = m.cut(b, "plain", True, count=False)
+        keys |= {bytes(b.buf[int(x):int(y)]) for x, y in zip(s, e)}
+    dr.set_vocab(sorted(keys))
+    for k, (what, args) in enumerate((
+            ("join", ("full", False, full, b" ", b"\n")), ("keywords", (True, tiny, 5)),
+            ("charspans", ("full", False, full, "rune", False)), ("charspans", ("full", False, full, "utf16", True)),
+            ("textrank", (True, full)), ("wc", ("full", False, full)), ("df", (True, full)),
+            ("join", ("full", False, full, b"<-sep8->", b"")), ("join", ("plain", True, smaller, b"\xe3\x80\x80", b"\n")))):
+        f = {"join": dr.join_batch, "keywords": dr.keywords, "charspans": dr.charspans_batch, "textrank": dr.textrank,
+             "wc": dr.wc_batch, "df": dr.df}[what]
+        f(*args, label=f"call {k}")
+        dr.stats(f"after call {k} ({what})")
+    dr.wc_read()
+
+
+def test_full_mode_regrow_then_everything_else(mini):
+    """A full-mode list longer than its batch has bytes makes the three new calls move the span arrays into the
+    ids/terms arena and cut again; here each is followed by the calls that own that arena, and by itself."""
+    mini_text, emit = mini
+    dr = open_text(regrow_dict(mini_text), emit)
+    try:
+        script_regrow(dr)
+    finally:
+        dr.tk.close()
+
+
+HAN = ("一", "龥")  # (three bytes each)
+
+
+def twin(b):
+    """A batch of b's shape (doc_off, bytes, documents) and other content: every Han rune replaced by the next
+    Han rune of the text."""
+    a, end = int(b.off[0]), int(b.off[-1])
+    text = bytes(b.buf[a:end]).decode("utf-8")
+    han = [c for c in text if HAN[0] <= c <= HAN[1]]
+    nxt = iter(han[1:] + han[:1])
+    out = "".join(next(nxt) if HAN[0] <= c <= HAN[1] else c for c in text).encode()
+    assert len(out) == end - a and out != bytes(b.buf[a:end])
+    buf = b.buf.copy()
+    buf[a:end] = np.frombuffer(out, np.uint8)
+    return M.Batch(("twin",) + tuple(b.spec), buf, b.off)
+
+
+SAME_SHAPE_TABLE = (1 << 16, 1 << 18)  # (read after every call: a small one)
+
+
+def script_same_shape(dr):
+    m = dr.m
+    b = dr.batch(("small", 777, 36 << 10))
+    t = dr.batch(twin(b))
+    assert np.array_equal(b.off, t.off) and b.nbytes == t.nbytes and b.ndocs == t.ndocs and len(b.buf) == len(t.buf)
+    ps, pt = m.cut(b, "plain", True, count=False), m.cut(t, "plain", True, count=False)
+    assert len(ps[0]) != len(pt[0]) or not np.array_equal(ps[0], pt[0])  # (the model's spans differ)
+    dr.set_vocab(m.vocab_keys(0))
+    shared = np.zeros_like(b.buf)
+    for own in (False, True):  # from one host address, then from each batch's own
+        for kind in M.NEW_BATCH_OPS:
+            for mode in M.MODES:
+                for k, x in enumerate((b, b, t, t, b)):
+                    label = f"{'own' if own else 'shared'} buffer, call {k}"
+                    shared[:] = x.buf
+                    buf = None if own else shared
+                    if kind == "join_batch":
+                        dr.join_batch(mode, mode != "full", x, b" ", b"\n", label, buf=buf)
+                    elif kind == "charspans_batch":
+                        dr.charspans_batch(mode, mode != "full", x, "utf16", True, label, buf=buf)
+                    else:
+                        dr.wc_batch(mode, mode != "full", x, label, buf=buf)
+                        dr.wc_read(label)
+                    dr.stats(label)
+    for x in (b, t, t, b):
+        dr.keywords(True, x, 5, "same shape")
+
+
+def test_same_shape_other_text(syn):
+    """Two batches of one shape and different content, B B B' B' B, through each new *_batch call in each mode:
+    the cut's graph key holds no text, so the second and later calls replay; each must answer for its own text."""
+    dr = open_20k(syn, SAME_SHAPE_TABLE)
+    try:
+        script_same_shape(dr)
+    finally:
+        dr.tk.close()
+
+
+def test_charspans_in_place_on_the_ctx_arrays(syn):
+    """jb_charspans_device in place on the arrays jb_cut_device returned (the ctx's own), then the same cut
+    again, a replay, which must put byte spans back; ids and the joined text of the result."""
+    dr = open_20k(syn)
+    try:
+        b = dr.batch(("small", 410, 40 << 10))
+        dr.set_vocab(dr.m.vocab_keys(0))
+        for mode in ("plain", "search"):
+            for unit in ("rune", "utf16"):
+                dr.cut(mode, True, "device", b)  # (direct, captured, replayed)
+                assert dr.lastdev is not None and not dr.lastdev["into"]
+                n = dr.restored
+                dr.charspans(unit, True, f"{mode}")
+                assert dr.restored == n + 1 and dr.lastdev is not None
+                dr.ids("device", mode)
+                dr.join(b" ", b"\n", mode)
+                dr.charspans(unit, False, f"{mode}")
+                dr.stats(mode)
+    finally:
+        dr.tk.close()
+
+
+def test_joined_results_outlive_calls_and_contexts(syn):
+    """The arrays Tokenizer.cut_batch_join hands out are the library's pinned blocks, of which jb_joined_free
+    keeps one per process: a held result stays what it was over later joins, a second ctx and its owner's close."""
+    d, e, s, source = syn
+    m = M.Model(d, e, source=source)
+    big, mid, small = (M.make_batch(s, sp) for sp in (("large", 1700, 120 << 10), ("small", 1710, 40 << 10), ("tiny", 1720, 6)))
+
+    def join(tk, b, sep=b" ", term=b"\n"):
+        out, off = tk.cut_batch_join(b.buf, b.off, True, "cut", sep, term)
+        want, woff = m.join(b, "plain", True, sep, term)
+        assert out.tobytes() == want and off.tolist() == woff, (b.spec, sep)
+        return out, want
+
+    tk1 = J.Tokenizer(J.make_config(dict_bytes=d, emit_bytes=e))
+    tk2 = tk3 = None
+    try:
+        # A: a held result over two smaller joins, their release, and a larger one
+        held, want = join(tk1, big)
+        s1, s2 = join(tk1, mid), join(tk1, small)
+        del s1, s2
+        gc.collect()
+        larger, wl = join(tk1, big, b"<-sep8->", b"<-sep8->")
+        assert len(larger) > len(held) and held.tobytes() == want and larger.tobytes() == wl
+        # B: a second ctx, joins on both in turn, the first closed under a held result
+        tk2 = J.Tokenizer(J.make_config(dict_bytes=d, emit_bytes=e))
+        a1, w1 = join(tk1, mid)
+        a2, w2 = join(tk2, mid, b"")
+        b1, x1 = join(tk1, small)
+        b2, x2 = join(tk2, big)
+        assert [x.tobytes() for x in (held, larger, a1, a2, b1, b2)] == [want, wl, w1, w2, x1, x2]
+        del larger, b1, b2
+        gc.collect()
+        tk1.close()  # (drops the cached block, not the blocks that are out)
+        tk1 = None
+        assert held.tobytes() == want and a1.tobytes() == w1 and a2.tobytes() == w2
+        n1 = len(a1)
+        del a1, w1
+        gc.collect()  # (a block freed after its ctx was closed: the cache takes it)
+        c2, y2 = join(tk2, mid, b"")
+        assert len(c2) <= n1 and c2.tobytes() == y2 and a2.tobytes() == w2 and held.tobytes() == want
+        del held, a2, c2
+        gc.collect()
+        # C: everything closed, a new ctx
+        tk2.close()
+        tk2 = None
+        tk3 = J.Tokenizer(J.make_config(dict_bytes=d, emit_bytes=e))
+        for b in (small, big, mid):
+            out, w = join(tk3, b, b"\xe3\x80\x80")
+            assert out.tobytes() == w
+            del out
+            gc.collect()
+    finally:
+        for tk in (tk1, tk2, tk3):
+            if tk is not None:
+                tk.close()
+
+
+def script_wc_life(dr):
+    m = dr.m
+    b1, b2, b3 = dr.batch(m.source), dr.batch(("offset", 620, 20 << 10)), dr.batch(("tiny", 630, 6))
+    grow = dr.batch(("grow", 640, 150 << 10))
+    assert grow.nbytes > 2 * b1.nbytes
+    # The word to add: pick_word(0)'s one occurrence in the source batch is never cut as a token, whatever its
+    # frequency, and a count of 0 would show nothing.  So: the most frequent pair of neighbouring one-rune
+    # tokens of b1 (one document, both Han) that is reachable and not a key.
+    s, e, d = m.cut(b1, "plain", False, count=False)
+    firsts, pairs = set(d.tolist()), {}
+    for k in range(len(s) - 1):
+        if e[k] - s[k] == 3 and e[k + 1] - s[k + 1] == 3 and e[k] == s[k + 1] and k + 1 not in firsts:
+            w = bytes(b1.buf[int(s[k]):int(e[k + 1])]).decode("utf-8", "replace")
+            if all(HAN[0] <= c <= HAN[1] for c in w) and m.o.get(w) is None and m.reachable(w):
+                pairs[w] = pairs.get(w, 0) + 1
+    word = min(pairs, key=lambda w: (-pairs[w], w))
+    key = word.encode()
+
+    def occurs(b, mode):
+        s, e, _ = m.cut(b, mode, False, count=False)
+        return sum(1 for x, y in zip(s.tolist(), e.tolist()) if bytes(b.buf[x:y]) == key)
+
+    dr.wc_batch("plain", False, b1)
+    dr.cut("plain", False, "device", grow)  # (replaces the workspace)
+    dr.wc_batch("search", False, b2)
+    assert m.wc[key] == 0
+    dr.add_word(word, 10_000_000)
+    dr.wc_batch("plain", False, b1)
+    assert m.wc[key] == occurs(b1, "plain") > 0
+    r1 = dr.wc_read("first")
+    dr.wc_batch("full", False, b2)
+    dr.cut("plain", False, "device", b3, reps=1)
+    dr.wc_add()
+    # (from the model, before the library's answer: only the batches after the add count the word)
+    assert m.wc[key] == occurs(b1, "plain") + occurs(b2, "full") + occurs(b3, "plain")
+    r2 = dr.wc_read("second")
+    r3 = dr.wc_read("third")
+    if r2 is not None:
+        assert r1.tokens < r2.tokens and r2.keys == r3.keys and np.array_equal(r2.counts, r3.counts)
+        assert (r2.bad, r2.long, r2.dropped, r2.collided, r2.tokens) == (r3.bad, r3.long, r3.dropped, r3.collided, r3.tokens)
+        assert int(r2.counts[r2.keys.index(key)]) == m.wc[key]
+
+
+def test_word_counts_over_a_contexts_life(syn):
+    """One caller-owned table over plain, search and full mode, a workspace replaced in between, an AddWord (the
+    word counts only from then on), jb_wc_add_device on a device cut's spans, and two reads that agree."""
+    dr = open_20k(syn)
+    try:
+        script_wc_life(dr)
+    finally:
+        dr.tk.close()
+
+
+@pytest.mark.parametrize("seed", M.SEEDS2)
+def test_random_sequences2(syn, seed):
+    """gen_ops2(seed, NSTEPS2): test_random_sequences with the six new kinds of call in the deck."""
+    ops = M.gen_ops2(seed, M.NSTEPS2)
+    dr = open_20k(syn)
+    try:
+        dr.set_vocab(dr.m.vocab_keys(0))
+        for i, op in enumerate(ops):
+            try:
+                dr.run(op)
+            except (AssertionError, J.JbError) as e:
+                raise AssertionError(f"seed {seed}, step {i}: {op!r}\nops = {ops[:i + 1]!r}\n{e}") from e
+        dr.wc_read("at the end")
+        assert dr.too_small >= 1 and dr.restored >= 1  # (what covered2 promises did happen)
     finally:
         dr.tk.close()
