@@ -828,6 +828,119 @@ int jb_wc_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint3
 int jb_device_alloc(jb_ctx *ctx, size_t n, void **p);
 void jb_device_free(jb_ctx *ctx, void *p);
 
+/* ---- MinHash signatures: near-duplicate document sketches ------------------------------------
+ *
+ * The step that corpus pipelines run right after a cut: shingles of n consecutive words, a MinHash
+ * signature of K u32 slots per document, LSH band keys.  Two documents agree in a slot with the
+ * probability of their shingle sets' Jaccard similarity.  The signature is computed on the device from
+ * the span list the cut left there: no token reaches the host, and ndocs * K * 4 bytes come back.
+ *
+ * The rule.  jb_minhash (host only, no ctx, no GPU) and jb_minhash_device agree to the bit.  All
+ * arithmetic is unsigned and modulo 2^64 unless a width is stated.
+ *  - Tokens and documents.  The clamps are jb_join's: token k exists iff k < min(ntok, cap); document
+ *    d's tokens are [doc_tok[d], doc_tok[d+1]) clamped to that bound, m_d of them.  A token before
+ *    doc_tok[0] or at or past doc_tok[ndocs] belongs to no document.  doc_tok is trusted to be
+ *    non-decreasing; if it is not, the affected documents' values are unspecified, but still nothing
+ *    outside the outputs and the work buffer is written and no text byte outside [0, nbytes + 64) read.
+ *  - Token hash t_k.  The key is jb_ids_device's: the bytes text[s..e); a 1-byte span whose byte is
+ *    >= 0x80 is keyed as EF BF BD.  The spans are not trusted: s >= e or e > nbytes gives the empty
+ *    key (length 0, no byte read), as in jb_join.  A key longer than 255 bytes is cut to its first 255
+ *    bytes (bytes are bytes: the cut may fall inside a rune).  t_k is the vocabulary's hash of the key
+ *    (jb_vocab_build's table hash): h = 0x243F6A8885A308D3 ^ (len * 0xFF51AFD7ED558CCD); for every 8-byte
+ *    little-endian word w of the key, zero-padded (at least one word, so the empty key mixes one 0):
+ *    h = (h ^ w) * 0x9E3779B97F4A7C15, h ^= h >> 32 ("mix"); last h *= 0xD6E8FEB86659FD93, h ^= h >> 32
+ *    ("fin").  The first term, with c in place of len, is "init(c)" below.
+ *  - Shingles of width n, 1 <= n <= JB_MH_MAXN.  A document with m >= n has the shingles i = 0 .. m - n
+ *    over its tokens i .. i + n - 1; one with 0 < m < n has one shingle over all its m tokens; one
+ *    with m = 0 has none.  With c the number of tokens folded, the shingle's hash is g = init(c), then
+ *    g = mix(g, t) for each token in order, then s = fin(g).  A shingle never crosses a document
+ *    boundary.  doc_n[d] (u32) is the document's shingle count: 0, 1 or m - n + 1.
+ *  - Hash functions, 1 <= K <= JB_MH_MAXK, from a u64 seed by splitmix64: st += 0x9E3779B97F4A7C15,
+ *    z = st, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB,
+ *    next = z ^ z >> 31.  From st = seed the values are drawn in the order a_0, b_0, a_1, b_1, ... with
+ *    a_j = next() | 1 and b_j = next().  jb_minhash_params (host only) returns them, so that a caller
+ *    can sketch a query document elsewhere.
+ *  - Signature.  x_i = (uint32_t)s_i, and sig[d * K + j] is the least, over the document's shingles,
+ *    of (uint32_t)((a_j * (uint64_t)x_i + b_j) >> 32): multiply-shift hashing.  A document without
+ *    shingles has JB_MH_EMPTY in every slot.  Every one of the ndocs * K slots and ndocs counts is
+ *    written, and nothing else.
+ *  - Band keys.  jb_minhash_bands (host) and jb_minhash_bands_device turn signatures into LSH bucket
+ *    keys: B bands of R rows, B * R <= K.  key[d * B + b] (u64) is g = mix(init(R), b), then
+ *    g = mix(g, sig[d * K + b * R + r]) for r = 0 .. R - 1, then fin(g).  A document with doc_n[d] == 0
+ *    gets JB_MH_NOKEY in every band, so that empty documents never bucket together; a computed key
+ *    equal to JB_MH_NOKEY is stored as JB_MH_NOKEY - 1.
+ *  - Limits: JB_EINVAL for a null pointer (arrays of capacity 0 may be NULL), for n, K, B or R = 0 and
+ *    for B * R > K; JB_ELIMIT for n or K above the maxima, for nbytes >= 2 GiB and for
+ *    cap >= 2^32 - JB_MH_TILE.
+ *
+ * jb_minhash_device.  The contract is jb_join_device's: the call queues its kernels on `stream` and
+ * returns; it does not synchronise, allocate, read anything on the host or use the per-device
+ * workspace, and it holds the ctx's shared lock only while queuing.  d_text has nbytes bytes plus 64
+ * readable padding bytes and is 4-byte aligned, as for jb_ids_device.  d_start / d_end / d_doc_tok /
+ * d_ntok may be the ctx-owned results of any jb_cut_device* call, of any mode, or the caller's own.
+ * d_work is a caller-owned device buffer of nwork >= jb_minhash_work_bytes(cap, ndocs) bytes, 8-byte
+ * aligned (JB_EINVAL otherwise, with nothing queued): 8 bytes per token, the token hashes; today it
+ * does not depend on ndocs.  The helper is host only, non-decreasing in both arguments and never 0.
+ * The number of launches is 3, whatever the device data are (1, k_mh_init alone, when cap or ndocs is
+ * 0): k_mh_init (every slot JB_MH_EMPTY, doc_n from doc_tok alone), k_mh_hash (one lane per token: the
+ * key from aligned dwords, t_k into d_work) and k_mh_sig (the minima, by u32 atomicMin; a minimum does
+ * not depend on the order, so the bits are the same from run to run).  No lane waits for another.
+ * k_mh_sig has two forms with identical bits (JB_MH_FORM, read at jb_open).  0, the plain form: one
+ * lane per token finds its document by a search over doc_tok, folds its shingle from d_work and walks
+ * the K functions, with an atomicMin only where its value is below what a load of the slot shows.  1,
+ * the staged form (the default): one workgroup per tile of JB_MH_TILE tokens loads the tile's hashes
+ * and a halo of n - 1 into LDS, folds each shingle once, and every lane owns one hash function for a
+ * share of the tile: it keeps a running minimum per run of one document and flushes it with one
+ * atomicMin per (tile share, document run, function).
+ * Measured on the 1 GiB corpus (tools/minhash_bench.py, profiles/minhash_bench.json; 73,443 documents):
+ * the 139.5M plain-mode spans at n = 5, K = 128 take 6.41 ms staged against 344.0 ms plain, beside
+ * 6.23 ms for the cut step and 9.08 ms for jb_wc_add_device in the same run (k_mh_hash 0.67 ms, k_mh_sig
+ * 5.41 ms); at n = 1, K = 64, 3.90 against 195.7 ms.  Search mode's 223.7M spans: 10.16 and 6.24 ms
+ * staged; full mode's 320.4M spans: 14.19 and 8.74 ms.  The two forms' bits were identical in every
+ * mode and shape, and those of the plain-mode spans were jb_minhash's over the whole corpus.  The
+ * staged form ships.  From pageable host memory jb_minhash_batch takes 35.61 ms for the 1 GiB beside
+ * 29.98 ms for jb_cut_batch_into32.
+ *
+ * jb_minhash_bands_device: one kernel, one lane per (document, band), the same contract.
+ *
+ * jb_minhash_batch: host text in.  It uploads, cuts in `mode` (JB_MODE_*; hmm is ignored for
+ * JB_MODE_FULL) and sketches on ctx's first device, through the buffers jb_keywords_batch keeps in the
+ * ctx (one more, for the work buffer and the signatures, that only grows; concurrent calls take
+ * turns), and copies back only sig (ndocs * K u32) and doc_n (ndocs u32).  Requirements and errors are
+ * jb_wc_batch's; in full mode, when the span list exceeds the kept span arrays, it grows them and
+ * repeats the cut.  It does not use the multi-device piece pipeline, because pieces may split a
+ * document.
+ *
+ * Deliberate differences from the usual datasketch recipe:
+ *  - 32-bit multiply-shift hashing instead of a hash modulo a Mersenne prime;
+ *  - the shingles are runs of jieba words, not character n-grams;
+ *  - keys are cut at 255 bytes;
+ *  - a document shorter than n words has one shingle over all its words, not none. */
+#define JB_MH_MAXN 8
+#define JB_MH_MAXK 256
+#define JB_MH_TILE 1024 /* tokens per tile of the staged form (one workgroup) */
+#define JB_MH_EMPTY 0xFFFFFFFFu
+#define JB_MH_NOKEY 0xFFFFFFFFFFFFFFFFull
+/* Host only, no ctx: non-decreasing in both arguments, never 0. */
+size_t jb_minhash_work_bytes(uint64_t max_tokens, uint32_t ndocs);
+/* host only: a[K], b[K] of `seed` */
+int jb_minhash_params(uint64_t seed, uint32_t K, uint64_t *a, uint64_t *b);
+/* host only, no ctx, no GPU: the rule, and the reference the device kernels are pinned to */
+int jb_minhash(const uint8_t *text, uint64_t nbytes, const uint32_t *start, const uint32_t *end, const uint64_t *doc_tok,
+               uint64_t ntok, uint64_t cap, uint32_t ndocs, uint32_t n, uint32_t K, uint64_t seed, uint32_t *sig,
+               uint32_t *doc_n);
+int jb_minhash_bands(const uint32_t *sig, const uint32_t *doc_n, uint32_t ndocs, uint32_t K, uint32_t B, uint32_t R,
+                     uint64_t *keys);
+int jb_minhash_device(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uint32_t *d_start,
+                      const uint32_t *d_end, const uint64_t *d_doc_tok, const uint64_t *d_ntok, uint64_t cap,
+                      uint32_t ndocs, uint32_t n, uint32_t K, uint64_t seed, void *stream, uint32_t *d_sig,
+                      uint32_t *d_doc_n, void *d_work, size_t nwork);
+int jb_minhash_bands_device(jb_ctx *ctx, const uint32_t *d_sig, const uint32_t *d_doc_n, uint32_t ndocs, uint32_t K,
+                            uint32_t B, uint32_t R, void *stream, uint64_t *d_keys);
+/* sig: ndocs x K host entries; doc_n: ndocs. */
+int jb_minhash_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm, int mode,
+                     uint32_t n, uint32_t K, uint64_t seed, uint32_t *sig, uint32_t *doc_n);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

@@ -16,6 +16,7 @@
 #include "jb_host.h"
 #include "jb_join.h"
 #include "jb_textrank.h"
+#include "jb_minhash.h"
 #include "jb_wc.h"
 
 // ---------------------------------------------------------------------------
@@ -1869,6 +1870,155 @@ extern "C" int jb_wc_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc
     const int rc = run();
     if (st) {
         (void)hipStreamSynchronize(st);  // (the copy from the caller's memory may be in flight)
+        (void)hipStreamDestroy(st);
+    }
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// MinHash signatures (jb_minhash.hip; the host rule, jb_minhash, jb_minhash_params, jb_minhash_bands and the
+// size helper are jb_minhash.cpp)
+// ---------------------------------------------------------------------------
+static_assert(JB_MH_TILE == kMhTile && JB_MH_MAXN == kMhMaxN && JB_MH_MAXK == kMhMaxK,
+              "the header's constants are the kernels'");
+
+extern "C" int jb_minhash_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
+                                 const uint32_t* d_end, const uint64_t* d_doc_tok, const uint64_t* d_ntok, uint64_t cap,
+                                 uint32_t ndocs, uint32_t n, uint32_t K, uint64_t seed, void* stream, uint32_t* d_sig,
+                                 uint32_t* d_doc_n, void* d_work, size_t nwork) {
+    const char* who = "jb_minhash_device";
+    // (the limits come first: they need no ctx)
+    if (const int rc = minhash_args(who, nbytes, cap, n, K)) return rc;
+    if (!ctx || (!d_text && nbytes) || !d_doc_tok || !d_ntok || !d_work || (cap && (!d_start || !d_end)) ||
+        (ndocs && (!d_sig || !d_doc_n)))
+        return fail(JB_EINVAL, "%s: null argument", who);
+    if (((uintptr_t)d_text & 3u) != 0) return fail(JB_EINVAL, "d_text must be 4-byte aligned");
+    if (((uintptr_t)d_work & 7u) != 0) return fail(JB_EINVAL, "%s: d_work must be 8-byte aligned", who);
+    const size_t need = jb_minhash_work_bytes(cap, ndocs);
+    if (nwork < need)
+        return fail(JB_EINVAL, "%s: a work buffer of %llu bytes, jb_minhash_work_bytes asks for %llu", who,
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    const bool staged = d->lc.mh_form != 0;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_minhash(d_text, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, n, K, seed, staged, d_sig,
+                           d_doc_n, (uint64_t*)d_work, d->ncu, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_minhash(d_text, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, n, K, seed, staged, d_sig, d_doc_n,
+                       (uint64_t*)d_work, d->ncu, s, nullptr));
+    return JB_OK;
+}
+
+extern "C" int jb_minhash_bands_device(jb_ctx* ctx, const uint32_t* d_sig, const uint32_t* d_doc_n, uint32_t ndocs,
+                                       uint32_t K, uint32_t B, uint32_t R, void* stream, uint64_t* d_keys) {
+    const char* who = "jb_minhash_bands_device";
+    if (const int rc = minhash_band_args(who, K, B, R)) return rc;
+    if (!ctx || (ndocs && (!d_sig || !d_doc_n || !d_keys))) return fail(JB_EINVAL, "%s: null argument", who);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_minhash_bands(d_sig, d_doc_n, ndocs, K, B, R, d_keys, d->ncu, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_minhash_bands(d_sig, d_doc_n, ndocs, K, B, R, d_keys, d->ncu, s, nullptr));
+    return JB_OK;
+}
+
+// Host text in, signatures out: the cut of `mode` into the ctx's buffers [0] (and, when full mode's list is
+// longer than the batch has bytes, [1]), then jb_minhash_device with its work buffer, sig and doc_n in [8];
+// only sig and doc_n come back.
+extern "C" int jb_minhash_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                                int mode, uint32_t n, uint32_t K, uint64_t seed, uint32_t* sig, uint32_t* doc_n) {
+    const char* who = "jb_minhash_batch";
+    if (!ctx || !doc_off || (ndocs && (!sig || !doc_n))) return fail(JB_EINVAL, "%s: null argument", who);
+    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
+        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
+    if (const int rc = minhash_args(who, 0, 0, n, K)) return rc;
+    for (uint32_t k = 0; k < ndocs; k++)
+        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
+    const uint64_t nb = doc_off[ndocs] - doc_off[0];
+    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
+    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    if (ndocs == 0) return JB_OK;
+    HIPCHK(hipSetDevice(ordinal));
+    std::vector<uint64_t> rel;
+    try {
+        rel.resize((size_t)ndocs + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
+    }
+    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
+    uint64_t cap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
+    std::lock_guard<std::mutex> kg(ctx->kw_mu);
+    hipStream_t st = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
+        Arena a;
+        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * cap * 4), &a))) return rc;
+        uint8_t* dt = (uint8_t*)a.take(nb + 64);
+        uint64_t* doff = (uint64_t*)a.take(ndoc8);
+        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
+        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the span count)
+        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
+        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
+        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+        uint64_t ntok = 0;
+        for (int pass = 0;; pass++) {
+            if (mode == JB_MODE_CUT)
+                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
+            else if (mode == JB_MODE_SEARCH)
+                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
+            else
+                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + cap, cap, dtok, dcnt);
+            if (rc) return rc;
+            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
+            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
+            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > cap && pass == 0) {
+                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
+                cap = ntok;
+                Arena b;
+                if ((rc = kw_arena(ctx, 1, r256(2 * cap * 4), &b))) return rc;
+                dse = (uint32_t*)b.take(2 * cap * 4);
+                continue;
+            }
+            if (rc) return rc;
+            break;
+        }
+        const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);  // (the work buffer follows the token count)
+        if (const int r = minhash_args(who, nb, tcap, n, K)) return r;
+        const size_t nwork = jb_minhash_work_bytes(tcap, ndocs), nsig = (size_t)ndocs * K * 4, ndn = (size_t)ndocs * 4;
+        Arena w;
+        if ((rc = kw_arena(ctx, 8, r256(nwork) + r256(nsig) + r256(ndn), &w))) return rc;
+        void* dwork = w.take(nwork);
+        uint32_t* dsig = (uint32_t*)w.take(nsig);
+        uint32_t* ddn = (uint32_t*)w.take(ndn);
+        if ((rc = jb_minhash_device(ctx, dt, nb, dse, dse + cap, dtok, dcnt, tcap, ndocs, n, K, seed, st, dsig, ddn, dwork,
+                                    nwork)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(sig, dsig, nsig, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(doc_n, ddn, ndn, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return JB_OK;
+    };
+    const int rc = run();
+    if (st) {
+        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
         (void)hipStreamDestroy(st);
     }
     return rc;

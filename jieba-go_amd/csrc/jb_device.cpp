@@ -246,6 +246,7 @@ static const uint64_t kMaxPiece = 1ull << 30;  // (a piece of several documents;
 //   JB_JOIN_STAGE jb_join_device's write kernel: 0 the plain form (default), 1 the staged form
 //   JB_WC_COMBINE jb_wc_add_device's count pass: 0 one global atomic per token, 1 combined in LDS (default)
 //   JB_WC_HASHBITS the word-count fingerprint's width, 1 .. 64 (default 64; fewer to test collisions)
+//   JB_MH_FORM   jb_minhash_device's signature kernel: 0 the plain form, 1 the staged form (default)
 static int init_launch_cfg(Device* d) {
     LaunchCfg& lc = d->lc;
     lc.zh_waves = d->ncu * std::max(zh_waves_per_cu(true, false), zh_waves_per_cu(false, false));
@@ -319,6 +320,9 @@ static int init_launch_cfg(Device* d) {
     const int wcb = env_int("JB_WC_HASHBITS", 64);
     if (wcb < 1 || wcb > 64) return fail(JB_EINVAL, "JB_WC_HASHBITS=%d: want 1 .. 64", wcb);
     lc.wc_bits = (uint32_t)wcb;
+    const int mhf = env_int("JB_MH_FORM", 1);
+    if (mhf < 0 || mhf > 1) return fail(JB_EINVAL, "JB_MH_FORM=%d: want 0 or 1", mhf);
+    lc.mh_form = (uint32_t)mhf;
     return JB_OK;
 }
 

@@ -342,10 +342,11 @@ struct jb_ctx {
     // (they only grow; calls take kw_mu in turn): [0] sized by the batch's bytes, [1] by its token count,
     // [2] jb_df_batch's ndf counters, [3] jb_textrank_batch's keep mask, records and work buffer,
     // [4] jb_cut_batch_join's output, [5] its work buffer and output offsets,
-    // [6] jb_cut_batch_charspans' work buffer and doc_units, [7] jb_wc_batch's work buffer
+    // [6] jb_cut_batch_charspans' work buffer and doc_units, [7] jb_wc_batch's work buffer,
+    // [8] jb_minhash_batch's work buffer, signatures and shingle counts
     std::mutex kw_mu;
-    void* kw_buf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t kw_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    void* kw_buf[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t kw_cap[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 #pragma GCC visibility pop

@@ -129,6 +129,7 @@ enum KernelId {
     K_JOIN_COUNT, K_JOIN_SCAN, K_JOIN_DOC, K_JOIN_WRITE,
     K_CS_CLASS, K_CS_SCAN, K_CS_LOOKUP,
     K_WC_CLAIM, K_WC_STORE, K_WC_COUNT,
+    K_MH_INIT, K_MH_HASH, K_MH_SIG, K_MH_BANDS,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -172,6 +173,8 @@ struct LaunchCfg {
                              // (JB_WC_COMBINE; results do not depend on it)
     uint32_t wc_bits;        // the fingerprint keeps this many low bits of the hash (JB_WC_HASHBITS: 64; fewer
                              // only to test the collision path)
+    uint32_t mh_form;        // jb_minhash_device's signature pass: 0 the plain form, 1 the staged form (JB_MH_FORM;
+                             // results do not depend on it)
 };
 
 // k_zh's group split: g1 groups of grp bytes, then groups of *sgrp bytes to the end.
@@ -348,6 +351,23 @@ hipError_t run_wc_init(void* d_table, uint64_t nslots, uint64_t pool_bytes, uint
 hipError_t run_wc_add(void* d_table, uint64_t ntable, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
                       const uint32_t* d_end, const uint64_t* d_ntok, uint64_t cap, uint32_t bits, bool combine,
                       uint32_t* d_work, uint32_t ncu, hipStream_t stream, KernelTimer* timer);
+
+// MinHash signatures (jb_minhash_device, jb_minhash_bands_device; jb_minhash.hip, the rule's shared code is
+// jb_minhash.h's).  Tile = kMhTile consecutive tokens, one workgroup each in the staged form.
+constexpr uint32_t kMhTile = 1024;  // JB_MH_TILE
+constexpr uint32_t kMhMaxN = 8;     // JB_MH_MAXN: the halo of a tile is at most 7 tokens
+constexpr uint32_t kMhMaxK = 256;   // JB_MH_MAXK: one lane of a workgroup per hash function
+// Enqueue k_mh_init, k_mh_hash and k_mh_sig on `stream` (k_mh_init alone when cap or ndocs is 0): sig (ndocs x
+// K) and doc_n (ndocs) of the tokens k < min(*d_ntok, cap) under shingles of n tokens (1 .. kMhMaxN) and K
+// (1 .. kMhMaxK) hash functions of `seed`.  d_text is 4-byte aligned and no byte at or past nbytes + 64 is
+// read; d_work holds 8 bytes per token of cap.  `staged` chooses the signature kernel's form.
+hipError_t run_minhash(const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start, const uint32_t* d_end,
+                       const uint64_t* d_doc_tok, const uint64_t* d_ntok, uint64_t cap, uint32_t ndocs, uint32_t n,
+                       uint32_t K, uint64_t seed, bool staged, uint32_t* d_sig, uint32_t* d_doc_n, uint64_t* d_work,
+                       uint32_t ncu, hipStream_t stream, KernelTimer* timer);
+// Enqueue k_mh_bands on `stream`: keys (ndocs x B) from sig and doc_n, one lane per (document, band).
+hipError_t run_minhash_bands(const uint32_t* d_sig, const uint32_t* d_doc_n, uint32_t ndocs, uint32_t K, uint32_t B,
+                             uint32_t R, uint64_t* d_keys, uint32_t ncu, hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

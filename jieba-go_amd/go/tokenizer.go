@@ -544,6 +544,52 @@ func (t *Tokenizer) WordCounts(texts []string, useHmm bool, mode int, minCount, 
 	return words, r.ndropped == 0 && r.ncollided == 0
 }
 
+// MinHash sketches every text of a batch for near-duplicate detection: the cut of mode (C.JB_MODE_CUT,
+// C.JB_MODE_SEARCH, C.JB_MODE_FULL; full mode ignores useHmm), shingles of n consecutive words (1 to
+// JB_MH_MAXN) and k hash functions (1 to JB_MH_MAXK) of seed, all on the GPU; only the signatures come
+// back.  sig[d] holds text d's k slots, docN[d] its shingle count; two texts agree in a slot with the
+// probability of their shingle sets' Jaccard similarity.  A text without tokens has docN 0 and
+// JB_MH_EMPTY in every slot.  The rule is jiebahip.h's (tests/c_abi_minhash.c).  Never returns nil.
+func (t *Tokenizer) MinHash(texts []string, n, k int, seed uint64, useHmm bool, mode int) (sig [][]uint32, docN []uint32) {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	sig = make([][]uint32, len(texts))
+	docN = make([]uint32, len(texts))
+	if len(texts) == 0 {
+		return sig, docN
+	}
+	if n < 1 || n > C.JB_MH_MAXN || k < 1 || k > C.JB_MH_MAXK {
+		panic("jiebahip: MinHash n or k out of range")
+	}
+	off := make([]uint64, len(texts)+1)
+	total := 0
+	for i, d := range texts {
+		total += len(d)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, d := range texts {
+		b = append(b, d...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	flat := make([]uint32, len(texts)*k)
+	rc := C.jb_minhash_batch(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+		C.uint32_t(len(texts)), hmm, C.int(mode), C.uint32_t(n), C.uint32_t(k), C.uint64_t(seed),
+		(*C.uint32_t)(unsafe.Pointer(&flat[0])), (*C.uint32_t)(unsafe.Pointer(&docN[0])))
+	if rc != C.JB_OK {
+		// JB_EINVAL: an unknown mode; JB_EPANIC: the reference panics on this input
+		panic("jiebahip: " + lastError())
+	}
+	for d := range texts {
+		sig[d] = flat[d*k : (d+1)*k]
+	}
+	return sig, docN
+}
+
 // CutJoin is strings.Join(Cut(text), sep) for every text of a batch, with the cut of mode (C.JB_MODE_CUT,
 // C.JB_MODE_SEARCH, C.JB_MODE_FULL; full mode ignores useHmm) and the join both on the GPU: only the joined
 // bytes come back, no span and no token.  sep holds at most JB_JOIN_MAXSEP (8) bytes.  An invalid byte comes

@@ -231,6 +231,24 @@ std::vector<Tokenizer::WordCount> Tokenizer::WordCounts(const std::vector<std::s
     return out;
 }
 
+Tokenizer::MinHashResult Tokenizer::MinHash(const std::vector<std::string>& docs, uint32_t n, uint32_t K, uint64_t seed,
+                                            bool useHmm, int mode) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& d : docs) {
+        all += d;
+        off.push_back(all.size());
+    }
+    MinHashResult r;
+    r.sig.resize(docs.size() * (size_t)K + 1);  // (+ 1: never an empty vector, its address is passed)
+    r.docN.resize(docs.size() + 1);
+    check(jb_minhash_batch(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)docs.size(), useHmm ? 1 : 0, mode, n, K,
+                           seed, r.sig.data(), r.docN.data()));
+    r.sig.resize(docs.size() * (size_t)K);
+    r.docN.resize(docs.size());
+    return r;
+}
+
 std::vector<std::vector<Tokenizer::Token>> Tokenizer::Tokenize(const std::vector<std::string>& docs, bool useHmm, int mode,
                                                                int unit) {
     std::string all;

@@ -129,6 +129,17 @@ public:
     std::vector<WordCount> WordCounts(const std::vector<std::string>& docs, bool useHmm = true, int mode = JB_MODE_CUT,
                                       uint64_t minCount = 1, uint64_t maxKeys = 0, uint64_t nslots = 1u << 20,
                                       uint64_t poolBytes = 4u << 20, bool strict = true);
+    // MinHash signatures (jb_minhash_batch in jiebahip.h): per document K u32 slots over its shingles of n
+    // consecutive words of the cut of `mode`, for near-duplicate detection: two documents agree in a slot with
+    // the probability of their shingle sets' Jaccard similarity.  The cut and the sketch both run on the GPU;
+    // only the signatures come back.  sig holds docs.size() rows of K slots; docN[d] is document d's shingle
+    // count, and a document without tokens has 0 there and JB_MH_EMPTY in every slot.
+    struct MinHashResult {
+        std::vector<uint32_t> sig;   // docs.size() x K
+        std::vector<uint32_t> docN;  // docs.size()
+    };
+    MinHashResult MinHash(const std::vector<std::string>& docs, uint32_t n = 5, uint32_t K = 128, uint64_t seed = 1,
+                          bool useHmm = true, int mode = JB_MODE_CUT);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

@@ -37,6 +37,10 @@ JB_UNIT_RUNE, JB_UNIT_UTF16 = 0, 1  # the units of the character-offset calls
 JB_CHAR_NONE = 0xFFFFFFFF  # a token without character offsets (malformed, outside its document, of no document)
 JB_CHARSPANS_TILE = 4096  # text bytes per tile of jb_charspans_device
 _UNITS = {"rune": JB_UNIT_RUNE, "utf16": JB_UNIT_UTF16}
+JB_MH_MAXN, JB_MH_MAXK = 8, 256  # the widest shingle (tokens) and the most hash functions of the MinHash calls
+JB_MH_TILE = 1024  # tokens per tile of jb_minhash_device's staged form
+JB_MH_EMPTY = 0xFFFFFFFF  # every slot of a document without shingles
+JB_MH_NOKEY = 0xFFFFFFFFFFFFFFFF  # every band key of a document without shingles
 _TOKENIZE_MODES = {"default": JB_MODE_CUT, "search": JB_MODE_SEARCH, "full": JB_MODE_FULL}
 
 # Every symbol include/jiebahip.h declares.
@@ -59,6 +63,8 @@ EXPORTS = [
     "jb_charspans_work_bytes", "jb_charspans", "jb_charspans_device", "jb_cut_batch_charspans",
     "jb_wc_table_bytes", "jb_wc_work_bytes", "jb_wc_fp", "jb_wc_init_device", "jb_wc_add_device", "jb_wc_read",
     "jb_wc_result_free", "jb_wc_count", "jb_wc_batch", "jb_device_alloc", "jb_device_free",
+    "jb_minhash_work_bytes", "jb_minhash_params", "jb_minhash", "jb_minhash_bands", "jb_minhash_device",
+    "jb_minhash_bands_device", "jb_minhash_batch",
 ]
 
 
@@ -268,6 +274,17 @@ def lib():
         L.jb_wc_count.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                   C.POINTER(jb_wc_result)]
         L.jb_wc_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, vp, C.c_size_t]
+        L.jb_minhash_work_bytes.restype = C.c_size_t
+        L.jb_minhash_work_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        L.jb_minhash_params.argtypes = [C.c_uint64, C.c_uint32, vp, vp]
+        L.jb_minhash.argtypes = [vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                 C.c_uint64, vp, vp]
+        L.jb_minhash_bands.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.jb_minhash_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32,
+                                        C.c_uint32, C.c_uint64, vp, vp, vp, vp, C.c_size_t]
+        L.jb_minhash_bands_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+        L.jb_minhash_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, vp,
+                                       vp]
         L.jb_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
         L.jb_device_free.argtypes = [vp, vp]
         L.jb_device_free.restype = None
@@ -1037,6 +1054,50 @@ class Tokenizer:
         self.set_vocab(keys)
         return keys, counts
 
+    # -- MinHash signatures ------------------------------------------------
+    def minhash_device(self, d_text_ptr, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, n, K, seed, d_sig,
+                       d_doc_n, d_work, nwork, stream_ptr=0):
+        """jb_minhash_device over raw device pointers: per document the K-slot MinHash signature of its shingles
+        of n tokens (u32[ndocs, K] into d_sig) and its shingle count (u32[ndocs] into d_doc_n), from a span
+        list of any mode; queued on the stream.  d_work: minhash_work_bytes(cap, ndocs) bytes."""
+        _check(lib().jb_minhash_device(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_start), C.c_void_p(d_end),
+                                       C.c_void_p(d_doc_tok), C.c_void_p(d_ntok), cap, ndocs, n, K, seed,
+                                       C.c_void_p(stream_ptr), C.c_void_p(d_sig), C.c_void_p(d_doc_n),
+                                       C.c_void_p(d_work), nwork))
+
+    def minhash_bands_device(self, d_sig, d_doc_n, ndocs, K, B, R, d_keys, stream_ptr=0):
+        """jb_minhash_bands_device over raw device pointers: the LSH keys of B bands of R rows (u64[ndocs, B] into
+        d_keys) of the signatures at d_sig; queued on the stream."""
+        _check(lib().jb_minhash_bands_device(self.h, C.c_void_p(d_sig), C.c_void_p(d_doc_n), ndocs, K, B, R,
+                                             C.c_void_p(stream_ptr), C.c_void_p(d_keys)))
+
+    def minhash_batch(self, buf, doc_off, hmm, n=5, K=128, seed=1, mode="cut"):
+        """jb_minhash_batch: host batch -> (sig uint32[ndocs, K], doc_n uint32[ndocs]); mode "cut", "search" or
+        "full" (or a JB_MODE_* value; full mode ignores hmm)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        nd = len(doc_off) - 1
+        if isinstance(mode, str):
+            if mode not in _MODES:
+                raise ValueError(f"mode {mode!r}: one of 'cut', 'search', 'full'")
+            mode = _MODES[mode]
+        sig = np.empty((nd, max(int(K), 0)), np.uint32)
+        doc_n = np.empty(nd, np.uint32)
+        _check(lib().jb_minhash_batch(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, int(hmm), int(mode), n, K, seed,
+                                      sig.ctypes.data if sig.size else None, doc_n.ctypes.data if nd else None))
+        return sig, doc_n
+
+    def minhash(self, texts, n=5, K=128, seed=1, mode="cut", hmm=True):
+        """The MinHash signatures of a batch of texts (str / bytes), cut in `mode` and sketched on the GPU over
+        shingles of n consecutive words: (sig uint32[ndocs, K], doc_n uint32[ndocs]).  The share of equal slots
+        of two rows estimates the Jaccard similarity of the two documents' shingle sets; a document without
+        tokens has doc_n 0 and JB_MH_EMPTY in every slot.  The rule is jiebahip.h's."""
+        docs = [_b(t) for t in texts]
+        off = np.zeros(len(docs) + 1, np.uint64)
+        if docs:
+            off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+        return self.minhash_batch(np.frombuffer(b"".join(docs) + b"\0", np.uint8), off, hmm, n, K, seed, mode)
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -1086,7 +1147,7 @@ class Tokenizer:
         _check(lib().jb_profile_reset(self.h))
 
     def profile_read(self):
-        cap = 64  # (more than the library's kernels: 47)
+        cap = 64  # (more than the library's kernels: 54)
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         n = (C.c_uint64 * cap)()
@@ -1259,6 +1320,48 @@ def wc_count(text, starts, ends, ntok=None, cap=None, nbytes=None, min_count=1, 
         return WcResult(r)
     finally:
         lib().jb_wc_result_free(C.byref(r))
+
+
+def minhash_work_bytes(max_tokens, ndocs):
+    """jb_minhash_work_bytes: bytes of the work buffer jb_minhash_device needs (host only)."""
+    return lib().jb_minhash_work_bytes(max_tokens, ndocs)
+
+
+def minhash_params(seed, K):
+    """jb_minhash_params (host only): (a uint64[K], b uint64[K]), the K hash functions of `seed`."""
+    a, b = np.empty(max(int(K), 0), np.uint64), np.empty(max(int(K), 0), np.uint64)
+    _check(lib().jb_minhash_params(seed, K, a.ctypes.data if len(a) else None, b.ctypes.data if len(b) else None))
+    return a, b
+
+
+def minhash(text, starts, ends, doc_tok, n=5, K=128, seed=1, ntok=None, cap=None, nbytes=None):
+    """jb_minhash (host only): the MinHash rule of jiebahip.h on host arrays (text bytes or a uint8 array, u32
+    spans, u64 doc_tok): (sig uint32[ndocs, K], doc_n uint32[ndocs])."""
+    t = np.ascontiguousarray(text, np.uint8) if isinstance(text, np.ndarray) else np.frombuffer(_b(text), np.uint8)
+    s = np.ascontiguousarray(starts, np.uint32)
+    e = np.ascontiguousarray(ends, np.uint32)
+    d = np.ascontiguousarray(doc_tok, np.uint64)
+    nd = len(d) - 1
+    cap = len(s) if cap is None else cap
+    ntok = len(s) if ntok is None else ntok
+    nbytes = len(t) if nbytes is None else nbytes
+    sig = np.empty((nd, max(int(K), 0)), np.uint32)
+    doc_n = np.empty(nd, np.uint32)
+    p = lambda a: a.ctypes.data if a.size else None
+    _check(lib().jb_minhash(p(t), nbytes, p(s), p(e), d.ctypes.data, ntok, cap, nd, n, K, seed, p(sig), p(doc_n)))
+    return sig, doc_n
+
+
+def minhash_bands(sig, doc_n, B, R):
+    """jb_minhash_bands (host only): the LSH keys (uint64[ndocs, B]) of B bands of R rows of the signatures
+    sig (uint32[ndocs, K]); doc_n (uint32[ndocs]) marks the documents without shingles, which get JB_MH_NOKEY."""
+    sig = np.ascontiguousarray(sig, np.uint32)
+    doc_n = np.ascontiguousarray(doc_n, np.uint32)
+    nd, K = sig.shape
+    keys = np.empty((nd, max(int(B), 0)), np.uint64)
+    p = lambda a: a.ctypes.data if a.size else None
+    _check(lib().jb_minhash_bands(p(sig), p(doc_n), nd, K, B, R, p(keys)))
+    return keys
 
 
 def _unit(unit):
