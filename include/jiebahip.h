@@ -941,6 +941,135 @@ int jb_minhash_bands_device(jb_ctx *ctx, const uint32_t *d_sig, const uint32_t *
 int jb_minhash_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm, int mode,
                      uint32_t n, uint32_t K, uint64_t seed, uint32_t *sig, uint32_t *doc_n);
 
+/* ---- Token filtering: stop words, classes and lengths ----------------------------------------
+ *
+ * `[w for w in jieba.cut(s) if w not in stopwords and len(w) > 1]`: a span list of any mode becomes a
+ * shorter span list of the same shape (u32 starts and ends, u64 per-document offsets, a count), so that
+ * every consumer of a span list (jb_ids_device, jb_join_device, jb_wc_add_device, jb_minhash_device,
+ * jb_charspans_device) works on the result unchanged.  No token reaches the host.
+ *
+ * The rule.  jb_filter (host only, no ctx, no GPU) and jb_filter_device agree exactly, on every output.
+ *  - Tokens.  Token k takes part iff k < nt = min(ntok, cap): jb_join's clamps (full mode's list may be
+ *    longer than its arrays).
+ *  - Key.  jb_ids_device's: the bytes text[s..e); EF BF BD for a 1-byte span whose byte is >= 0x80.
+ *  - Bad spans.  The spans are not trusted.  A span with s >= e or e > nbytes is bad: it is never kept
+ *    and none of its bytes is read.
+ *  - Class.  Every other token has one class, decided from its own bytes only:
+ *      JB_TC_INVALID  one byte, and that byte is >= 0x80;
+ *      JB_TC_NUM      the first byte is ASCII [0-9A-Za-z], the key has at most 255 bytes, and all of
+ *                     them are ASCII digits;
+ *      JB_TC_ALNUM    every other key whose first byte is ASCII [0-9A-Za-z]; a key over 255 bytes is
+ *                     ALNUM without being scanned (a 1 MB run is one token);
+ *      JB_TC_HAN      the first rune is Han (Unicode 13 Script=Han, the cut kernels' class, the
+ *                     reference's `zh`, tokenizer.go:21); the rune is decoded by Go's utf8.DecodeRune over
+ *                     [s, e), so a sequence cut short by e is (U+FFFD, 1) and not Han;
+ *      JB_TC_OTHER    everything else: punctuation, symbols, kana, hangul and other scripts, which the
+ *                     reference emits one rune at a time (cutNonZh, tokenizer.go:289-310).  This is a
+ *                     deliberate limit: there are no Unicode category tables here.
+ *  - Length.  runes(k) is the number of key bytes that are not 10xxxxxx, saturating at 256.  A key
+ *    longer than 1024 bytes counts 256 without being read, so no token costs more than 1024 byte reads
+ *    (valid UTF-8 has at least 256 runes in 1024 bytes; only a malformed span can tell the difference).
+ *    INVALID counts 1.  min_runes and max_runes are at most 255 (JB_ELIMIT above that); max_runes == 0
+ *    means no upper bound.  Counting may stop as soon as the answer is decided.
+ *  - Stop words.  With JB_FILTER_STOP in the rule's flags a token is a stop word iff its key is found
+ *    in the stop set: an exact byte comparison, the vocabulary table's lookup.  A key longer than the
+ *    set's longest key is not read for it.
+ *  - Decision.  A token gets the first reason that applies, in this order: bad; class (drop_classes has
+ *    the class's bit); length (runes < min_runes, or max_runes && runes > max_runes); stop.  With no
+ *    reason it is kept.  The stop probe comes last because it costs the most.
+ *  - Output.  The kept tokens come in their original order as out_start and out_end (u32).  out_src, a
+ *    u32 array that may be NULL, receives the index of each kept token's source token; with it a caller
+ *    gathers ids or anything else.  With R(i) the number of kept tokens whose source index is below i,
+ *    out_doc_tok[d] = R(min(doc_tok[d], nt)) for d = 0 .. ndocs (u64) and *out_ntok = R(nt).  Entries
+ *    with index >= out_cap are not written, and nothing else is written; out_cap = cap is always enough,
+ *    and the caller checks *out_ntok <= out_cap, as for jb_terms_device.  Outputs must not alias inputs
+ *    or each other: equal pointers return JB_EINVAL.
+ *  - Statistics.  stats[5] (u64) is written, not accumulated: ntokens (= nt), nbad, nclass, nlength,
+ *    nstop.  ntokens == *out_ntok + nbad + nclass + nlength + nstop always holds.  All values are
+ *    integer sums, so they are the same from run to run.
+ *  - Errors.  JB_EINVAL: a null pointer (arrays of capacity 0 may be NULL), unknown flag or class bits,
+ *    JB_FILTER_STOP without a stop set.  JB_ELIMIT: min_runes or max_runes above 255, nbytes >= 2 GiB,
+ *    cap >= 2^32 - JB_FILTER_TILE.
+ *
+ * The stop set.  jb_stopwords_set(ctx, keys, key_off, nkeys) attaches the caller's stop list, in
+ * jb_vocab_set's format and under its contract in every respect: it is built aside and takes the
+ * exclusive lock, it waits for queued device work before the old table is released, NULL with 0 keys
+ * removes the set, and on any error the old set stays.  It is a second table beside the id vocabulary,
+ * with its device copy on the first device; the ids are unused.  It is independent of jb_vocab_set, it
+ * is not part of jb_save, and jb_add_word does not touch it.  jb_stopwords_size: the number of keys, or
+ * -1 without a set.  The host rule takes a `const jb_vocab *stop` (may be NULL) from jb_vocab_build.
+ *
+ * jb_filter_device.  The contract is jb_join_device's: the call queues its kernels on `stream` and
+ * returns; it does not synchronise, allocate, read anything on the host or use the per-device
+ * workspace, and it holds the ctx's shared lock only while queuing.  d_text has nbytes bytes plus 64
+ * readable padding bytes and is 4-byte aligned, as for jb_ids_device.  d_work is a caller-owned device
+ * buffer of nwork >= jb_filter_work_bytes(cap, ndocs) bytes, 8-byte aligned (JB_EINVAL otherwise, with
+ * nothing queued): one bit per token and about 40 bytes per tile of JB_FILTER_TILE tokens.  The helper
+ * is host only, non-decreasing in both arguments and never 0.  There are three launches whatever the
+ * data; when cap == 0 there is none, only the memsets that zero out_doc_tok, *out_ntok and stats.  No
+ * lane waits for another, and there are no global atomics.
+ *   k_filt_mark   one lane per token: the key from aligned dwords (jb_ids_device's reads), the decision;
+ *                 a wave ballot writes each wave's 64-bit keep word into d_work, and ballots of the four
+ *                 reasons give the tile's counts.
+ *   k_filt_scan   one workgroup, looping over the tiles: exclusive tile prefixes, the five totals,
+ *                 *out_ntok and stats.
+ *   k_filt_write  per tile, a kept token's rank is the tile's prefix, plus the popcounts of the tile's
+ *                 earlier words, plus the popcount of the lane's own word below the lane; it writes
+ *                 out_start, out_end and out_src below out_cap.  ndocs + 1 further lanes compute
+ *                 out_doc_tok[d] from the same bitmap and prefixes.
+ * Measured on the 1 GiB corpus (tools/filter_bench.py, profiles/filter_bench.json; 73,443 documents) with
+ * the rule drop = OTHER | INVALID, min_runes = 2, JB_FILTER_STOP against 1,000 stop keys: the 139.5M
+ * plain-mode spans take 2.96 ms (53.5M kept; k_filt_mark 2.49 ms, k_filt_scan 0.14 ms, k_filt_write
+ * 0.34 ms), beside 6.26 ms for the cut step, 2.61 ms for jb_charspans_device and 3.73 ms for
+ * jb_join_device in the same run; with the class test alone 1.29 ms.  Search mode's 223.7M spans: 4.67
+ * and 1.98 ms; full mode's 320.4M spans: 6.78 and 2.80 ms.  The plain-mode outputs were jb_filter's over
+ * the whole corpus.  jb_join_device on the filtered list takes 1.78 ms against 3.73 ms.  From pageable
+ * host memory jb_cut_batch_join with the batch filter set takes 40.2 ms for the 1 GiB against 51.4 ms
+ * without it.
+ *
+ * jb_cut_batch_filter: host text in, the filtered u32 byte spans (relative to doc_off[0]) out, under
+ * jb_cut_batch_into32's cap protocol on the filtered count: *ntokens is always the filtered count, and
+ * when it exceeds cap the call returns JB_ELIMIT and nothing but *ntokens and stats is written.
+ * It uploads, cuts in `mode` and filters on ctx's first device, through the buffers jb_keywords_batch
+ * keeps in the ctx (one more, that only grows; concurrent calls take turns); in full mode, when the
+ * span list exceeds the kept span arrays, it grows them and repeats the cut.  stats may be NULL.
+ *
+ * jb_batch_filter_set(ctx, rule) stores a rule in the ctx (NULL clears it).  While one is set,
+ * jb_cut_batch_join, jb_wc_batch and jb_minhash_batch run the filter between their cut and their own
+ * step.  With none set, the default, those calls queue exactly the work they queued before this call
+ * existed.  jb_cut_batch_charspans and the id-based batch calls (which have weights and keep masks)
+ * are deliberately left alone.  A rule with JB_FILTER_STOP needs a stop set at the time of the batch
+ * call, which fails with JB_EINVAL otherwise. */
+#define JB_TC_HAN 1u
+#define JB_TC_ALNUM 2u
+#define JB_TC_NUM 4u
+#define JB_TC_OTHER 8u
+#define JB_TC_INVALID 16u
+#define JB_FILTER_STOP 1u
+#define JB_FILTER_TILE 2048 /* tokens per tile (one workgroup) */
+typedef struct {
+    uint32_t flags, drop_classes, min_runes, max_runes;
+} jb_filter_rule;
+int jb_stopwords_set(jb_ctx *ctx, const uint8_t *keys, const uint64_t *key_off, uint32_t nkeys);
+int64_t jb_stopwords_size(jb_ctx *ctx);
+/* Host only, no ctx: non-decreasing in both arguments, never 0. */
+size_t jb_filter_work_bytes(uint64_t max_tokens, uint32_t ndocs);
+/* host only, no ctx, no GPU: the rule, and the reference the device kernels are pinned to */
+int jb_filter(const uint8_t *text, uint64_t nbytes, const uint32_t *start, const uint32_t *end, const uint64_t *doc_tok,
+              uint64_t ntok, uint64_t cap, uint32_t ndocs, const jb_filter_rule *rule, const jb_vocab *stop,
+              uint32_t *out_start, uint32_t *out_end, uint32_t *out_src, uint64_t out_cap, uint64_t *out_doc_tok,
+              uint64_t *out_ntok, uint64_t *stats);
+int jb_filter_device(jb_ctx *ctx, const uint8_t *d_text, uint64_t nbytes, const uint32_t *d_start, const uint32_t *d_end,
+                     const uint64_t *d_doc_tok, const uint64_t *d_ntok, uint64_t cap, uint32_t ndocs,
+                     const jb_filter_rule *rule, void *stream, uint32_t *d_out_start, uint32_t *d_out_end,
+                     uint32_t *d_out_src, uint64_t out_cap, uint64_t *d_out_doc_tok, uint64_t *d_out_ntok,
+                     uint64_t *d_stats, void *d_work, size_t nwork);
+/* start / end: cap host entries; doc_tok: ndocs + 1; stats: 5 entries or NULL. */
+int jb_cut_batch_filter(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm, int mode,
+                        const jb_filter_rule *rule, uint32_t *start, uint32_t *end, uint64_t cap, uint64_t *doc_tok,
+                        uint64_t *ntokens, uint64_t *stats);
+int jb_batch_filter_set(jb_ctx *ctx, const jb_filter_rule *rule);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

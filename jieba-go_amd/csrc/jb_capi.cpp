@@ -16,6 +16,7 @@
 #include "jb_host.h"
 #include "jb_join.h"
 #include "jb_textrank.h"
+#include "jb_filter.h"
 #include "jb_minhash.h"
 #include "jb_wc.h"
 
@@ -236,6 +237,12 @@ extern "C" void jb_close(jb_ctx* ctx) {
         (void)hipDeviceSynchronize();
         dfree(ctx->d_vslots);
         dfree(ctx->d_vpool);
+    }
+    if (ctx->stopw && !ctx->devs.empty()) {  // (k_filt_mark may still be queued on a caller's stream)
+        (void)hipSetDevice(ctx->devs[0]->ordinal);
+        (void)hipDeviceSynchronize();
+        dfree(ctx->d_sslots);
+        dfree(ctx->d_spool);
     }
     if (std::any_of(std::begin(ctx->kw_buf), std::end(ctx->kw_buf), [](void* p) { return p != nullptr; }) &&
         !ctx->devs.empty()) {
@@ -817,11 +824,16 @@ extern "C" int jb_vocab_info(const jb_vocab* v, uint32_t* nkeys, uint32_t* maxle
 
 static_assert(JB_ID_UNK == JB_VOCAB_UNK, "the header's unknown id is the table's");
 
-extern "C" int jb_vocab_set(jb_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, uint32_t nkeys) {
-    if (!ctx) return fail(JB_EINVAL, "jb_vocab_set: null ctx");
+namespace {
+// jb_vocab_set and jb_stopwords_set: the caller's list built aside, uploaded to the first device and swapped in
+// under the exclusive lock, after the device's queued work (which may read the old table) has finished.
+int table_set(jb_ctx* ctx, const char* who, const uint8_t* keys, const uint64_t* key_off, uint32_t nkeys,
+              std::unique_ptr<Vocab> jb_ctx::*tab, uint32_t* jb_ctx::*dslots, uint8_t* jb_ctx::*dpool,
+              DevVocab jb_ctx::*dview) {
+    if (!ctx) return fail(JB_EINVAL, "%s: null ctx", who);
     const bool remove = !keys && nkeys == 0;
     std::unique_ptr<Vocab> nv;
-    if (!remove) {  // built aside: on any error the old vocabulary stays attached
+    if (!remove) {  // built aside: on any error the old table stays attached
         try {
             nv = std::make_unique<Vocab>();
             std::string err;
@@ -844,18 +856,35 @@ extern "C" int jb_vocab_set(jb_ctx* ctx, const uint8_t* keys, const uint64_t* ke
         if (e != hipSuccess) {
             dfree(ns);
             dfree(np);
-            return fail(JB_EDEVICE, "jb_vocab_set: uploading the table: %s", hipGetErrorString(e));
+            return fail(JB_EDEVICE, "%s: uploading the table: %s", who, hipGetErrorString(e));
         }
     }
-    // the old table may be in use by id kernels queued earlier, on any stream of the device
-    if (ctx->vocab) (void)hipDeviceSynchronize();
-    dfree(ctx->d_vslots);
-    dfree(ctx->d_vpool);
-    ctx->d_vslots = ns;
-    ctx->d_vpool = np;
-    ctx->vocab = std::move(nv);
-    ctx->dvocab = ctx->vocab ? DevVocab{ns, np, (uint32_t)(ctx->vocab->nslots - 1u), ctx->vocab->maxlen} : DevVocab{};
+    // the old table may be in use by kernels queued earlier, on any stream of the device
+    if (ctx->*tab) (void)hipDeviceSynchronize();
+    dfree(ctx->*dslots);
+    dfree(ctx->*dpool);
+    ctx->*dslots = ns;
+    ctx->*dpool = np;
+    ctx->*tab = std::move(nv);
+    ctx->*dview = ctx->*tab ? DevVocab{ns, np, (uint32_t)((ctx->*tab)->nslots - 1u), (ctx->*tab)->maxlen} : DevVocab{};
     return JB_OK;
+}
+}  // namespace
+
+extern "C" int jb_vocab_set(jb_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, uint32_t nkeys) {
+    return table_set(ctx, "jb_vocab_set", keys, key_off, nkeys, &jb_ctx::vocab, &jb_ctx::d_vslots, &jb_ctx::d_vpool,
+                     &jb_ctx::dvocab);
+}
+
+extern "C" int jb_stopwords_set(jb_ctx* ctx, const uint8_t* keys, const uint64_t* key_off, uint32_t nkeys) {
+    return table_set(ctx, "jb_stopwords_set", keys, key_off, nkeys, &jb_ctx::stopw, &jb_ctx::d_sslots, &jb_ctx::d_spool,
+                     &jb_ctx::dstop);
+}
+
+extern "C" int64_t jb_stopwords_size(jb_ctx* ctx) {
+    if (!ctx) return -1;
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    return ctx->stopw ? (int64_t)ctx->stopw->nkeys : -1;
 }
 
 extern "C" int64_t jb_vocab_size(jb_ctx* ctx) {
@@ -1141,6 +1170,33 @@ int kw_arena(jb_ctx* ctx, int which, size_t need, Arena* a) {
     }
     *a = Arena{};
     a->p = (uint8_t*)ctx->kw_buf[which];
+    return JB_OK;
+}
+
+// The batch filter's step between a host-batch call's cut and its own step (jb_batch_filter_set,
+// jb_cut_batch_filter; under kw_mu): jb_filter_device over the cut's span list, with its work buffer and the
+// filtered list in the ctx's buffer [9].  On return the caller's names for the span list (starts at *dse, ends
+// at *dse + *cap, *dtok, the count at *dcnt) are the filtered list's; (*dcnt)[1] is spare, as the cut's is, and
+// (*dcnt)[2 .. 6] are the statistics.  ntok is the cut's count.
+int batch_filter_step(jb_ctx* ctx, const char* who, const jb_filter_rule& rule, const uint8_t* dt, uint64_t nb,
+                      uint32_t ndocs, hipStream_t st, uint64_t ntok, uint32_t** dse, uint64_t* cap, uint64_t** dtok,
+                      uint64_t** dcnt) {
+    const uint64_t tcap = std::max<uint64_t>(std::min(ntok, *cap), 1);  // (kept tokens never exceed the cut's)
+    if (const int r = filter_args(who, nb, tcap, &rule, true)) return r;  // (the stop set is jb_filter_device's check)
+    const size_t nwork = jb_filter_work_bytes(tcap, ndocs), ndoc8 = ((size_t)ndocs + 1) * 8;
+    Arena f;
+    if (const int r = kw_arena(ctx, 9, r256(nwork) + r256(2 * tcap * 4) + r256(ndoc8) + r256(64), &f)) return r;
+    void* work = f.take(nwork);
+    uint32_t* ose = (uint32_t*)f.take(2 * tcap * 4);
+    uint64_t* otok = (uint64_t*)f.take(ndoc8);
+    uint64_t* ocnt = (uint64_t*)f.take(64);
+    if (const int r = jb_filter_device(ctx, dt, nb, *dse, *dse + *cap, *dtok, *dcnt, tcap, ndocs, &rule, st, ose, ose + tcap,
+                                       nullptr, tcap, otok, ocnt, ocnt + 2, work, nwork))
+        return r;
+    *dse = ose;
+    *cap = tcap;
+    *dtok = otok;
+    *dcnt = ocnt;
     return JB_OK;
 }
 
@@ -1490,6 +1546,9 @@ extern "C" int jb_cut_batch_join(jb_ctx* ctx, const uint8_t* text, const uint64_
             if (rc) return rc;
             break;
         }
+        if (ctx->bfilter_on &&
+            (rc = batch_filter_step(ctx, who, ctx->bfilter, dt, nb, ndocs, st, ntok, &dse, &cap, &dtok, &dcnt)))
+            return rc;
         if (const int r = join_args(who, nb, cap, sep, seplen, term, termlen)) return r;
         const size_t nwork = join_work_bytes(cap, ndocs);
         Arena w;
@@ -1859,6 +1918,9 @@ extern "C" int jb_wc_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc
             if (rc) return rc;
             break;
         }
+        if (ctx->bfilter_on &&
+            (rc = batch_filter_step(ctx, who, ctx->bfilter, dt, nb, ndocs, st, ntok, &dse, &cap, &dtok, &dcnt)))
+            return rc;
         const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);  // (the work buffer follows the token count)
         const size_t nwork = jb_wc_work_bytes(tcap);
         Arena w;
@@ -2000,6 +2062,9 @@ extern "C" int jb_minhash_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t
             if (rc) return rc;
             break;
         }
+        if (ctx->bfilter_on &&
+            (rc = batch_filter_step(ctx, who, ctx->bfilter, dt, nb, ndocs, st, ntok, &dse, &cap, &dtok, &dcnt)))
+            return rc;
         const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);  // (the work buffer follows the token count)
         if (const int r = minhash_args(who, nb, tcap, n, K)) return r;
         const size_t nwork = jb_minhash_work_bytes(tcap, ndocs), nsig = (size_t)ndocs * K * 4, ndn = (size_t)ndocs * 4;
@@ -2013,6 +2078,160 @@ extern "C" int jb_minhash_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t
             return rc;
         HIPCHK(hipMemcpyAsync(sig, dsig, nsig, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(doc_n, ddn, ndn, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return JB_OK;
+    };
+    const int rc = run();
+    if (st) {
+        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
+        (void)hipStreamDestroy(st);
+    }
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// The token filter (jb_filter.hip; the host rule, jb_filter, the argument checks and the size helper are
+// jb_filter.cpp; the stop set, jb_stopwords_set, is with jb_vocab_set above)
+// ---------------------------------------------------------------------------
+static_assert(JB_FILTER_TILE == kFiltTile, "the header's constant is the kernels'");
+
+extern "C" int jb_filter_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start,
+                                const uint32_t* d_end, const uint64_t* d_doc_tok, const uint64_t* d_ntok, uint64_t cap,
+                                uint32_t ndocs, const jb_filter_rule* rule, void* stream, uint32_t* d_out_start,
+                                uint32_t* d_out_end, uint32_t* d_out_src, uint64_t out_cap, uint64_t* d_out_doc_tok,
+                                uint64_t* d_out_ntok, uint64_t* d_stats, void* d_work, size_t nwork) {
+    const char* who = "jb_filter_device";
+    // (the limits come first: they need no ctx; the stop set is looked at under the lock)
+    if (const int rc = filter_args(who, nbytes, cap, rule, true)) return rc;
+    if (!ctx || (!d_text && nbytes) || !d_doc_tok || !d_ntok || !d_out_doc_tok || !d_out_ntok || !d_stats || !d_work ||
+        (cap && (!d_start || !d_end)) || (out_cap && (!d_out_start || !d_out_end)))
+        return fail(JB_EINVAL, "%s: null argument", who);
+    if (const int rc = filter_alias(who, d_start, d_end, d_doc_tok, d_out_start, d_out_end, d_out_src, d_out_doc_tok))
+        return rc;
+    if (((uintptr_t)d_text & 3u) != 0) return fail(JB_EINVAL, "d_text must be 4-byte aligned");
+    if (((uintptr_t)d_work & 7u) != 0) return fail(JB_EINVAL, "%s: d_work must be 8-byte aligned", who);
+    const size_t need = jb_filter_work_bytes(cap, ndocs);
+    if (nwork < need)
+        return fail(JB_EINVAL, "%s: a work buffer of %llu bytes, jb_filter_work_bytes asks for %llu", who,
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    if ((rule->flags & JB_FILTER_STOP) && !ctx->stopw)
+        return fail(JB_EINVAL, "%s: JB_FILTER_STOP without a stop set (jb_stopwords_set)", who);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_filter(d_text, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, *rule, ctx->dstop, d_out_start,
+                          d_out_end, d_out_src, out_cap, d_out_doc_tok, d_out_ntok, d_stats, d_work, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_filter(d_text, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, *rule, ctx->dstop, d_out_start,
+                      d_out_end, d_out_src, out_cap, d_out_doc_tok, d_out_ntok, d_stats, d_work, s, nullptr));
+    return JB_OK;
+}
+
+extern "C" int jb_batch_filter_set(jb_ctx* ctx, const jb_filter_rule* rule) {
+    const char* who = "jb_batch_filter_set";
+    if (!ctx) return fail(JB_EINVAL, "%s: null ctx", who);
+    if (rule)  // (a stop set is asked for when a batch call runs the rule)
+        if (const int rc = filter_args(who, 0, 0, rule, true)) return rc;
+    std::lock_guard<std::mutex> kg(ctx->kw_mu);
+    ctx->bfilter_on = rule != nullptr;
+    ctx->bfilter = rule ? *rule : jb_filter_rule{0, 0, 0, 0};
+    return JB_OK;
+}
+
+// Host text in, the filtered spans out: the cut of `mode` into the ctx's buffers [0] (and, when full mode's
+// list is longer than the batch has bytes, [1]), the filter into [9], and the count, the statistics and, when
+// the count fits the caller's arrays, the spans and doc_tok back.
+extern "C" int jb_cut_batch_filter(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                                   int mode, const jb_filter_rule* rule, uint32_t* start, uint32_t* end, uint64_t cap,
+                                   uint64_t* doc_tok, uint64_t* ntokens, uint64_t* stats) {
+    const char* who = "jb_cut_batch_filter";
+    if (!ctx || !doc_off || !doc_tok || !ntokens || (cap && (!start || !end))) return fail(JB_EINVAL, "%s: null argument", who);
+    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
+        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
+    if (const int rc = filter_args(who, 0, 0, rule, true)) return rc;
+    for (uint32_t k = 0; k < ndocs; k++)
+        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
+    const uint64_t nb = doc_off[ndocs] - doc_off[0];
+    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
+    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+        if ((rule->flags & JB_FILTER_STOP) && !ctx->stopw)
+            return fail(JB_EINVAL, "%s: JB_FILTER_STOP without a stop set (jb_stopwords_set)", who);
+    }
+    *ntokens = 0;
+    if (stats) memset(stats, 0, 40);
+    if (ndocs == 0) {
+        doc_tok[0] = 0;
+        return JB_OK;
+    }
+    HIPCHK(hipSetDevice(ordinal));
+    std::vector<uint64_t> rel;
+    try {
+        rel.resize((size_t)ndocs + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
+    }
+    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
+    uint64_t dcap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
+    std::lock_guard<std::mutex> kg(ctx->kw_mu);
+    hipStream_t st = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
+        Arena a;
+        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * dcap * 4), &a))) return rc;
+        uint8_t* dt = (uint8_t*)a.take(nb + 64);
+        uint64_t* doff = (uint64_t*)a.take(ndoc8);
+        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
+        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the span count)
+        uint32_t* dse = (uint32_t*)a.take(2 * dcap * 4);  // (starts, ends)
+        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
+        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+        uint64_t ntok = 0;
+        for (int pass = 0;; pass++) {
+            if (mode == JB_MODE_CUT)
+                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + dcap, dcap, dtok, dcnt);
+            else if (mode == JB_MODE_SEARCH)
+                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + dcap, dcap, dtok, dcnt);
+            else
+                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + dcap, dcap, dtok, dcnt);
+            if (rc) return rc;
+            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
+            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
+            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > dcap && pass == 0) {
+                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
+                dcap = ntok;
+                Arena b;
+                if ((rc = kw_arena(ctx, 1, r256(2 * dcap * 4), &b))) return rc;
+                dse = (uint32_t*)b.take(2 * dcap * 4);
+                continue;
+            }
+            if (rc) return rc;
+            break;
+        }
+        if ((rc = batch_filter_step(ctx, who, *rule, dt, nb, ndocs, st, ntok, &dse, &dcap, &dtok, &dcnt))) return rc;
+        uint64_t head[7];  // (the count, a spare word, the statistics)
+        HIPCHK(hipMemcpyAsync(head, dcnt, sizeof head, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        *ntokens = head[0];
+        if (stats) memcpy(stats, head + 2, 40);
+        if (head[0] > cap)
+            return fail(JB_ELIMIT, "%s: %llu tokens, the arrays hold %llu", who, (unsigned long long)head[0],
+                        (unsigned long long)cap);
+        if (head[0]) {
+            HIPCHK(hipMemcpyAsync(start, dse, head[0] * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(end, dse + dcap, head[0] * 4, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipMemcpyAsync(doc_tok, dtok, ndoc8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         return JB_OK;
     };

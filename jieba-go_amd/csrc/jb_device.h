@@ -324,10 +324,6 @@ static int grow_mapped(T** p, T** dp, uint64_t* cap, uint64_t want) {
     return JB_OK;
 }
 
-struct jb_vocab {
-    Vocab v;
-};
-
 struct jb_ctx {
     std::unique_ptr<jb_image> im;
     std::vector<std::unique_ptr<Device>> devs;
@@ -338,15 +334,24 @@ struct jb_ctx {
     uint32_t* d_vslots = nullptr;
     uint8_t* d_vpool = nullptr;
     DevVocab dvocab{};
+    // the caller's stop set (jb_stopwords_set): a second table under the same rules, read by jb_filter_device
+    std::unique_ptr<Vocab> stopw;
+    uint32_t* d_sslots = nullptr;
+    uint8_t* d_spool = nullptr;
+    DevVocab dstop{};
     // jb_keywords_batch's and jb_df_batch's device buffers on the first device, kept for the next call
     // (they only grow; calls take kw_mu in turn): [0] sized by the batch's bytes, [1] by its token count,
     // [2] jb_df_batch's ndf counters, [3] jb_textrank_batch's keep mask, records and work buffer,
     // [4] jb_cut_batch_join's output, [5] its work buffer and output offsets,
     // [6] jb_cut_batch_charspans' work buffer and doc_units, [7] jb_wc_batch's work buffer,
-    // [8] jb_minhash_batch's work buffer, signatures and shingle counts
+    // [8] jb_minhash_batch's work buffer, signatures and shingle counts,
+    // [9] the batch filter's work buffer and filtered span list (jb_cut_batch_filter, jb_batch_filter_set)
     std::mutex kw_mu;
-    void* kw_buf[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t kw_cap[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void* kw_buf[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t kw_cap[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // the rule jb_cut_batch_join, jb_wc_batch and jb_minhash_batch filter by (jb_batch_filter_set; under kw_mu)
+    bool bfilter_on = false;
+    jb_filter_rule bfilter{0, 0, 0, 0};
 };
 
 #pragma GCC visibility pop

@@ -7,6 +7,7 @@
 
 #include "jb_common.h"
 #include "jb_vocab.h"
+#include "jiebahip.h"
 
 namespace jb {
 
@@ -130,6 +131,7 @@ enum KernelId {
     K_CS_CLASS, K_CS_SCAN, K_CS_LOOKUP,
     K_WC_CLAIM, K_WC_STORE, K_WC_COUNT,
     K_MH_INIT, K_MH_HASH, K_MH_SIG, K_MH_BANDS,
+    K_FILT_MARK, K_FILT_SCAN, K_FILT_WRITE,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -368,6 +370,20 @@ hipError_t run_minhash(const uint8_t* d_text, uint64_t nbytes, const uint32_t* d
 // Enqueue k_mh_bands on `stream`: keys (ndocs x B) from sig and doc_n, one lane per (document, band).
 hipError_t run_minhash_bands(const uint32_t* d_sig, const uint32_t* d_doc_n, uint32_t ndocs, uint32_t K, uint32_t B,
                              uint32_t R, uint64_t* d_keys, uint32_t ncu, hipStream_t stream, KernelTimer* timer);
+
+// The token filter (jb_filter_device; jb_filter.hip, the rule's shared code is jb_filter.h's).  Tile = kFiltTile
+// consecutive tokens, one workgroup each.
+constexpr uint32_t kFiltTile = 2048;  // JB_FILTER_TILE
+// Enqueue k_filt_mark, k_filt_scan and k_filt_write on `stream` (three memsets and no launch when cap is 0):
+// the tokens k < min(*d_ntok, cap) that `rule` keeps, in order, into d_out_start / d_out_end / d_out_src (may
+// be null) at ranks below out_cap, d_out_doc_tok (ndocs + 1), *d_out_ntok and d_stats (5).  `stop` is the
+// device copy of the stop set (read only with JB_FILTER_STOP).  d_text is 4-byte aligned and no byte at or
+// past nbytes + 64 is read; d_work holds jb_filter_work_bytes(cap, ndocs) bytes, 8-byte aligned.
+hipError_t run_filter(const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_start, const uint32_t* d_end,
+                      const uint64_t* d_doc_tok, const uint64_t* d_ntok, uint64_t cap, uint32_t ndocs,
+                      const jb_filter_rule& rule, const DevVocab& stop, uint32_t* d_out_start, uint32_t* d_out_end,
+                      uint32_t* d_out_src, uint64_t out_cap, uint64_t* d_out_doc_tok, uint64_t* d_out_ntok,
+                      uint64_t* d_stats, void* d_work, hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

@@ -131,3 +131,8 @@ int vocab_build(const uint8_t* keys, const uint64_t* key_off, uint32_t nkeys, Vo
 uint32_t vocab_lookup(const Vocab& v, const uint8_t* tok, size_t len);
 
 }  // namespace jb
+
+// The C ABI's handle of a table (jb_vocab_build).
+struct jb_vocab {
+    jb::Vocab v;
+};

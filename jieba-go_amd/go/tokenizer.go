@@ -590,6 +590,126 @@ func (t *Tokenizer) MinHash(texts []string, n, k int, seed uint64, useHmm bool, 
 	return sig, docN
 }
 
+// FilterRule is jb_filter_rule: DropClasses holds C.JB_TC_* bits, MinRunes and MaxRunes (0: no upper bound) are at
+// most 255, and Stop drops the tokens found in the stop set (SetStopWords).
+type FilterRule struct {
+	DropClasses, MinRunes, MaxRunes uint32
+	Stop                            bool
+}
+
+func (r FilterRule) c() C.jb_filter_rule {
+	var f C.jb_filter_rule
+	if r.Stop {
+		f.flags = C.JB_FILTER_STOP
+	}
+	f.drop_classes = C.uint32_t(r.DropClasses)
+	f.min_runes = C.uint32_t(r.MinRunes)
+	f.max_runes = C.uint32_t(r.MaxRunes)
+	return f
+}
+
+// SetStopWords attaches the caller's stop list (1 to 255 bytes each, no duplicates), replacing any earlier one;
+// nil removes it.  It is independent of SetVocab (jb_stopwords_set).
+func (t *Tokenizer) SetStopWords(keys []string) error {
+	t.mu.Lock()
+	defer t.mu.Unlock()
+	if keys == nil {
+		if rc := C.jb_stopwords_set(t.ctx, nil, nil, 0); rc != C.JB_OK {
+			return errors.New("jiebahip: " + lastError())
+		}
+		return nil
+	}
+	buf := make([]byte, 0, 16)
+	off := make([]uint64, len(keys)+1)
+	for i, k := range keys {
+		buf = append(buf, k...)
+		off[i+1] = uint64(len(buf))
+	}
+	buf = append(buf, 0)
+	if rc := C.jb_stopwords_set(t.ctx, (*C.uint8_t)(unsafe.Pointer(&buf[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+		C.uint32_t(len(keys))); rc != C.JB_OK {
+		return errors.New("jiebahip: " + lastError())
+	}
+	return nil
+}
+
+// SetBatchFilter stores a rule that CutJoin, WordCounts and MinHash filter the cut's tokens by before their own
+// step; nil clears it (jb_batch_filter_set).
+func (t *Tokenizer) SetBatchFilter(rule *FilterRule) error {
+	t.mu.Lock()
+	defer t.mu.Unlock()
+	var rc C.int
+	if rule == nil {
+		rc = C.jb_batch_filter_set(t.ctx, nil)
+	} else {
+		f := rule.c()
+		rc = C.jb_batch_filter_set(t.ctx, &f)
+	}
+	if rc != C.JB_OK {
+		return errors.New("jiebahip: " + lastError())
+	}
+	return nil
+}
+
+// CutFiltered is Cut (or the cut of mode: C.JB_MODE_CUT, C.JB_MODE_SEARCH, C.JB_MODE_FULL; full mode ignores
+// useHmm) for every text of a batch with the tokens the rule drops left out, by class, length in runes and the
+// stop set; the cut and the filter both run on the GPU (jb_cut_batch_filter).  A kept invalid byte comes out as
+// U+FFFD.  Never returns nil.
+func (t *Tokenizer) CutFiltered(texts []string, rule FilterRule, useHmm bool, mode int) [][]string {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	out := make([][]string, len(texts))
+	if len(texts) == 0 {
+		return out
+	}
+	off := make([]uint64, len(texts)+1)
+	total := 0
+	for i, d := range texts {
+		total += len(d)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, d := range texts {
+		b = append(b, d...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	f := rule.c()
+	tok := make([]uint64, len(texts)+1)
+	start := make([]uint32, total+1)
+	end := make([]uint32, total+1)
+	var n C.uint64_t
+	call := func() C.int {
+		return C.jb_cut_batch_filter(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+			C.uint32_t(len(texts)), hmm, C.int(mode), &f, (*C.uint32_t)(unsafe.Pointer(&start[0])),
+			(*C.uint32_t)(unsafe.Pointer(&end[0])), C.uint64_t(len(start)), (*C.uint64_t)(unsafe.Pointer(&tok[0])), &n, nil)
+	}
+	rc := call()
+	if rc == C.JB_ELIMIT && uint64(n) > uint64(len(start)) { // (full mode: more spans than bytes)
+		start = make([]uint32, uint64(n))
+		end = make([]uint32, uint64(n))
+		rc = call()
+	}
+	if rc != C.JB_OK {
+		// JB_EINVAL: an unknown mode or rule, or Stop without a stop set; JB_EPANIC: the reference panics on this input
+		panic("jiebahip: " + lastError())
+	}
+	for d := range texts {
+		out[d] = make([]string, 0, tok[d+1]-tok[d])
+		for k := tok[d]; k < tok[d+1]; k++ {
+			if end[k]-start[k] == 1 && b[start[k]] >= 0x80 {
+				out[d] = append(out[d], "\uFFFD")
+			} else {
+				out[d] = append(out[d], string(b[start[k]:end[k]]))
+			}
+		}
+	}
+	return out
+}
+
 // CutJoin is strings.Join(Cut(text), sep) for every text of a batch, with the cut of mode (C.JB_MODE_CUT,
 // C.JB_MODE_SEARCH, C.JB_MODE_FULL; full mode ignores useHmm) and the join both on the GPU: only the joined
 // bytes come back, no span and no token.  sep holds at most JB_JOIN_MAXSEP (8) bytes.  An invalid byte comes

@@ -199,6 +199,47 @@ std::vector<std::string> Tokenizer::CutJoin(const std::vector<std::string>& docs
     return out;
 }
 
+void Tokenizer::SetStopWords(const std::vector<std::string>& keys) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& k : keys) {
+        all += k;
+        off.push_back(all.size());
+    }
+    // (keys.data() of an empty list may be null, which would remove the set: pass a byte)
+    check(jb_stopwords_set(ctx_, (const uint8_t*)(all.empty() ? "" : all.data()), off.data(), (uint32_t)keys.size()));
+}
+
+std::vector<std::vector<std::string>> Tokenizer::CutFiltered(const std::vector<std::string>& docs,
+                                                             const jb_filter_rule& rule, bool useHmm, int mode) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& d : docs) {
+        all += d;
+        off.push_back(all.size());
+    }
+    // (a plain or search cut has at most one span per byte; full mode's count comes back with JB_ELIMIT)
+    std::vector<uint32_t> s(all.size() + 1), e(all.size() + 1);
+    std::vector<uint64_t> tok(docs.size() + 1);
+    uint64_t n = 0;
+    int rc = jb_cut_batch_filter(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)docs.size(), useHmm ? 1 : 0, mode,
+                                 &rule, s.data(), e.data(), s.size(), tok.data(), &n, nullptr);
+    if (rc == JB_ELIMIT && n > s.size()) {
+        s.resize(n);
+        e.resize(n);
+        rc = jb_cut_batch_filter(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)docs.size(), useHmm ? 1 : 0, mode,
+                                 &rule, s.data(), e.data(), s.size(), tok.data(), &n, nullptr);
+    }
+    check(rc);
+    std::vector<std::vector<std::string>> out(docs.size());
+    for (size_t d = 0; d < docs.size(); d++)
+        for (uint64_t k = tok[d]; k < tok[d + 1]; k++) out[d].push_back(token_at(all, s[k], e[k]));
+    return out;
+}
+
+void Tokenizer::SetBatchFilter(const jb_filter_rule& rule) { check(jb_batch_filter_set(ctx_, &rule)); }
+void Tokenizer::ClearBatchFilter() { check(jb_batch_filter_set(ctx_, nullptr)); }
+
 std::vector<Tokenizer::WordCount> Tokenizer::WordCounts(const std::vector<std::string>& docs, bool useHmm, int mode,
                                                         uint64_t minCount, uint64_t maxKeys, uint64_t nslots,
                                                         uint64_t poolBytes, bool strict) {

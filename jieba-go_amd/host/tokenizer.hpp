@@ -104,6 +104,19 @@ public:
     // non-Han blocks without an alnum byte are absent, as in Cut.  sep holds at most JB_JOIN_MAXSEP bytes.
     std::vector<std::string> CutJoin(const std::vector<std::string>& docs, const std::string& sep = " ",
                                      bool useHmm = true, int mode = JB_MODE_CUT);
+    // Token filtering (jb_stopwords_set, jb_cut_batch_filter and jb_batch_filter_set in jiebahip.h).
+    // SetStopWords attaches the caller's stop list (1..255 bytes each, no duplicates), replacing any earlier
+    // one; it is independent of SetVocab.  CutFiltered is `[w for w in cut(doc) if ...]` for every document of a
+    // batch: the cut of `mode` and the filter both on the GPU, by class (rule.drop_classes, JB_TC_* bits), length
+    // in runes (rule.min_runes, rule.max_runes; 0: no upper bound) and, with JB_FILTER_STOP in rule.flags, the
+    // stop set.  A kept invalid byte comes out as U+FFFD.  SetBatchFilter stores a rule that CutJoin, WordCounts
+    // and MinHash filter the cut's tokens by before their own step, until ClearBatchFilter.
+    void SetStopWords(const std::vector<std::string>& keys);
+    std::vector<std::vector<std::string>> CutFiltered(const std::vector<std::string>& docs,
+                                                      const jb_filter_rule& rule = {0, JB_TC_OTHER | JB_TC_INVALID, 0, 0},
+                                                      bool useHmm = true, int mode = JB_MODE_CUT);
+    void SetBatchFilter(const jb_filter_rule& rule);
+    void ClearBatchFilter();
     // jieba's tokenize (jb_cut_batch_charspans in jiebahip.h): per document its tokens with their offsets in
     // the document, in Unicode characters (JB_UNIT_RUNE) or UTF-16 code units (JB_UNIT_UTF16), the cut of
     // `mode` and the conversion both on the GPU; no byte offset reaches the host.  The word is the token's

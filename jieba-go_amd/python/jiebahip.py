@@ -41,6 +41,10 @@ JB_MH_MAXN, JB_MH_MAXK = 8, 256  # the widest shingle (tokens) and the most hash
 JB_MH_TILE = 1024  # tokens per tile of jb_minhash_device's staged form
 JB_MH_EMPTY = 0xFFFFFFFF  # every slot of a document without shingles
 JB_MH_NOKEY = 0xFFFFFFFFFFFFFFFF  # every band key of a document without shingles
+JB_TC_HAN, JB_TC_ALNUM, JB_TC_NUM, JB_TC_OTHER, JB_TC_INVALID = 1, 2, 4, 8, 16  # the token filter's classes
+JB_FILTER_STOP = 1  # the filter rule's flag: drop the tokens found in the stop set
+JB_FILTER_TILE = 2048  # tokens per tile of jb_filter_device
+_CLASSES = {"han": JB_TC_HAN, "alnum": JB_TC_ALNUM, "num": JB_TC_NUM, "other": JB_TC_OTHER, "invalid": JB_TC_INVALID}
 _TOKENIZE_MODES = {"default": JB_MODE_CUT, "search": JB_MODE_SEARCH, "full": JB_MODE_FULL}
 
 # Every symbol include/jiebahip.h declares.
@@ -65,6 +69,8 @@ EXPORTS = [
     "jb_wc_result_free", "jb_wc_count", "jb_wc_batch", "jb_device_alloc", "jb_device_free",
     "jb_minhash_work_bytes", "jb_minhash_params", "jb_minhash", "jb_minhash_bands", "jb_minhash_device",
     "jb_minhash_bands_device", "jb_minhash_batch",
+    "jb_stopwords_set", "jb_stopwords_size", "jb_filter_work_bytes", "jb_filter", "jb_filter_device",
+    "jb_cut_batch_filter", "jb_batch_filter_set",
 ]
 
 
@@ -126,6 +132,29 @@ class WcResult:
     def __repr__(self):
         return (f"WcResult({len(self.keys)} keys, tokens={self.tokens}, bad={self.bad}, long={self.long}, "
                 f"dropped={self.dropped}, collided={self.collided})")
+
+
+class jb_filter_rule(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("drop_classes", C.c_uint32), ("min_runes", C.c_uint32),
+                ("max_runes", C.c_uint32)]
+
+
+def filter_rule(drop=(), min_runes=0, max_runes=0, stop=False):
+    """A jb_filter_rule: `drop` is a JB_TC_* mask or an iterable of class names ("han", "alnum", "num", "other",
+    "invalid"); min_runes / max_runes bound a token's length in runes (max_runes 0: no upper bound); stop drops
+    the tokens found in the stop set."""
+    if isinstance(drop, jb_filter_rule):
+        return drop
+    if isinstance(drop, str):
+        drop = (drop,)
+    if not isinstance(drop, int):
+        m = 0
+        for c in drop:
+            if c not in _CLASSES:
+                raise ValueError(f"class {c!r}: one of {sorted(_CLASSES)}")
+            m |= _CLASSES[c]
+        drop = m
+    return jb_filter_rule(JB_FILTER_STOP if stop else 0, drop, min_runes, max_runes)
 
 
 class jb_spans(C.Structure):
@@ -285,6 +314,17 @@ def lib():
         L.jb_minhash_bands_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
         L.jb_minhash_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, vp,
                                        vp]
+        L.jb_stopwords_set.argtypes = [vp, vp, vp, C.c_uint32]
+        L.jb_stopwords_size.restype = C.c_int64
+        L.jb_stopwords_size.argtypes = [vp]
+        L.jb_filter_work_bytes.restype = C.c_size_t
+        L.jb_filter_work_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        L.jb_filter.argtypes = [vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp,
+                                C.c_uint64, vp, vp, vp]
+        L.jb_filter_device.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp,
+                                       C.c_uint64, vp, vp, vp, vp, C.c_size_t]
+        L.jb_cut_batch_filter.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, C.c_uint64, vp, vp, vp]
+        L.jb_batch_filter_set.argtypes = [vp, vp]
         L.jb_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
         L.jb_device_free.argtypes = [vp, vp]
         L.jb_device_free.restype = None
@@ -1098,6 +1138,92 @@ class Tokenizer:
             off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
         return self.minhash_batch(np.frombuffer(b"".join(docs) + b"\0", np.uint8), off, hmm, n, K, seed, mode)
 
+    # -- token filtering ---------------------------------------------------
+    def set_stop_words(self, keys, packed=None):
+        """jb_stopwords_set: attach a stop set (a list of str / bytes), replacing any earlier one.  None removes
+        it; an empty list attaches an empty set."""
+        if keys is None and packed is None:
+            _check(lib().jb_stopwords_set(self.h, None, None, 0))
+            return
+        buf, off = packed if packed is not None else pack_keys(keys)
+        buf = np.ascontiguousarray(buf, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        _check(lib().jb_stopwords_set(self.h, buf.ctypes.data, off.ctypes.data, len(off) - 1))
+
+    @property
+    def stop_words_size(self):
+        """Keys of the attached stop set; -1 when none is attached."""
+        return lib().jb_stopwords_size(self.h)
+
+    def filter_device(self, d_text_ptr, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, rule, d_out_start,
+                      d_out_end, d_out_src, out_cap, d_out_doc_tok, d_out_ntok, d_stats, d_work, nwork, stream_ptr=0):
+        """jb_filter_device over raw device pointers: the tokens of a span list of any mode that `rule` (a
+        jb_filter_rule, see filter_rule) keeps, in order, as a span list of the same shape (u32 starts / ends and,
+        when d_out_src is not 0, source indices at ranks below out_cap; u64 doc_tok[ndocs + 1]; a u64 count; 5 u64
+        statistics); queued on the stream.  d_work: filter_work_bytes(cap, ndocs) bytes."""
+        _check(lib().jb_filter_device(self.h, C.c_void_p(d_text_ptr), nbytes, C.c_void_p(d_start), C.c_void_p(d_end),
+                                      C.c_void_p(d_doc_tok), C.c_void_p(d_ntok), cap, ndocs,
+                                      C.byref(rule) if rule is not None else None, C.c_void_p(stream_ptr),
+                                      C.c_void_p(d_out_start), C.c_void_p(d_out_end), C.c_void_p(d_out_src), out_cap,
+                                      C.c_void_p(d_out_doc_tok), C.c_void_p(d_out_ntok), C.c_void_p(d_stats),
+                                      C.c_void_p(d_work), nwork))
+
+    def cut_batch_filter(self, buf, doc_off, hmm, rule, mode="cut", out=None):
+        """jb_cut_batch_filter: host batch -> (start[:n], end[:n], doc_tok, stats, out), the tokens of `mode`
+        ("cut", "search", "full" or a JB_MODE_* value) that `rule` keeps, as u32 byte spans relative to
+        doc_off[0].  stats: uint64[5] (ntokens, nbad, nclass, nlength, nstop).  `out` = (start u32, end u32,
+        doc_tok u64[ndocs + 1]) to reuse; the span arrays are grown when too small."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        nd = len(doc_off) - 1
+        if isinstance(mode, str):
+            if mode not in _MODES:
+                raise ValueError(f"mode {mode!r}: one of 'cut', 'search', 'full'")
+            mode = _MODES[mode]
+        if out is None or len(out[2]) != nd + 1:
+            cap = max(1024, int(doc_off[-1] - doc_off[0]) // 2)
+            out = (np.empty(cap, np.uint32), np.empty(cap, np.uint32), np.empty(nd + 1, np.uint64))
+        n = C.c_uint64()
+        stats = np.zeros(5, np.uint64)
+        for _ in range(2):
+            rc = lib().jb_cut_batch_filter(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, int(hmm), int(mode),
+                                           C.byref(rule) if rule is not None else None, out[0].ctypes.data,
+                                           out[1].ctypes.data, len(out[0]), out[2].ctypes.data, C.byref(n),
+                                           stats.ctypes.data)
+            if rc == JB_ELIMIT and n.value > len(out[0]):
+                out = (np.empty(n.value, np.uint32), np.empty(n.value, np.uint32), out[2])
+                continue
+            _check(rc)
+            break
+        k = n.value
+        return out[0][:k], out[1][:k], out[2], stats, out
+
+    def set_batch_filter(self, drop=(), min_runes=0, max_runes=0, stop=False):
+        """jb_batch_filter_set: while set, cut_batch_join / cut_join, wc_batch / word_counts / fit_vocab and
+        minhash_batch / minhash filter the cut's tokens by this rule (see filter_rule) before their own step."""
+        r = filter_rule(drop, min_runes, max_runes, stop)
+        _check(lib().jb_batch_filter_set(self.h, C.byref(r)))
+
+    def clear_batch_filter(self):
+        """jb_batch_filter_set(NULL): the host-batch calls see every token of the cut again."""
+        _check(lib().jb_batch_filter_set(self.h, None))
+
+    def cut_filtered(self, texts, drop=("other", "invalid"), min_runes=0, max_runes=0, stop=False, mode="cut", hmm=True):
+        """`[w for w in cut(text) if ...]` for every text (str / bytes) of a batch: a list of token lists, cut in
+        `mode` and filtered on the GPU by class, length in runes and the stop set (set_stop_words).  An invalid
+        byte that is kept comes back as U+FFFD."""
+        docs = [_b(t) for t in texts]
+        if not docs:
+            return []
+        all_ = b"".join(docs)
+        off = np.zeros(len(docs) + 1, np.uint64)
+        off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+        s, e, dtok, _, _ = self.cut_batch_filter(np.frombuffer(all_ + b"\0", np.uint8), off, hmm,
+                                                 filter_rule(drop, min_runes, max_runes, stop), mode)
+        s, e, dtok = s.tolist(), e.tolist(), dtok.tolist()
+        return [[all_[s[k]:e[k]].decode("utf-8", "replace") for k in range(dtok[d], dtok[d + 1])]
+                for d in range(len(docs))]
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -1147,7 +1273,7 @@ class Tokenizer:
         _check(lib().jb_profile_reset(self.h))
 
     def profile_read(self):
-        cap = 64  # (more than the library's kernels: 54)
+        cap = 64  # (more than the library's kernels: 57)
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         n = (C.c_uint64 * cap)()
@@ -1362,6 +1488,39 @@ def minhash_bands(sig, doc_n, B, R):
     p = lambda a: a.ctypes.data if a.size else None
     _check(lib().jb_minhash_bands(p(sig), p(doc_n), nd, K, B, R, p(keys)))
     return keys
+
+
+def filter_work_bytes(max_tokens, ndocs):
+    """jb_filter_work_bytes: bytes of the work buffer jb_filter_device needs (host only)."""
+    return lib().jb_filter_work_bytes(max_tokens, ndocs)
+
+
+def filter_spans(text, starts, ends, doc_tok, rule=None, stop=None, ntok=None, cap=None, nbytes=None, out_cap=None,
+                 src=True):
+    """jb_filter (host only): the filter rule of jiebahip.h on host arrays (text bytes or a uint8 array, u32 spans,
+    u64 doc_tok).  `rule` is a jb_filter_rule (see filter_rule; None keeps every good span), `stop` a Vocab or
+    None.  Returns (out_start, out_end, out_src or None, out_doc_tok, out_ntok, stats uint64[5]); the arrays have
+    out_cap entries (default cap), of which min(out_ntok, out_cap) are written."""
+    t = np.ascontiguousarray(text, np.uint8) if isinstance(text, np.ndarray) else np.frombuffer(_b(text), np.uint8)
+    s = np.ascontiguousarray(starts, np.uint32)
+    e = np.ascontiguousarray(ends, np.uint32)
+    d = np.ascontiguousarray(doc_tok, np.uint64)
+    nd = len(d) - 1
+    cap = len(s) if cap is None else cap
+    ntok = len(s) if ntok is None else ntok
+    nbytes = len(t) if nbytes is None else nbytes
+    out_cap = cap if out_cap is None else out_cap
+    rule = filter_rule() if rule is None else rule
+    os_, oe = np.zeros(out_cap, np.uint32), np.zeros(out_cap, np.uint32)
+    osrc = np.zeros(out_cap, np.uint32) if src else None
+    odt = np.zeros(nd + 1, np.uint64)
+    n = C.c_uint64()
+    stats = np.zeros(5, np.uint64)
+    p = lambda a: a.ctypes.data if a is not None and a.size else None
+    _check(lib().jb_filter(p(t), nbytes, p(s), p(e), d.ctypes.data, ntok, cap, nd, C.byref(rule),
+                           stop.h if stop is not None else None, p(os_), p(oe), p(osrc), out_cap, odt.ctypes.data,
+                           C.byref(n), stats.ctypes.data))
+    return os_, oe, osrc, odt, n.value, stats
 
 
 def _unit(unit):
