@@ -1070,6 +1070,100 @@ int jb_cut_batch_filter(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_of
                         uint64_t *ntokens, uint64_t *stats);
 int jb_batch_filter_set(jb_ctx *ctx, const jb_filter_rule *rule);
 
+/* ---- postings (the inverted index; jieba ships a Whoosh ChineseAnalyzer, jieba/analyse/analyzer.py, and
+ * leaves the index to Whoosh; the reference has only Cut) -----------------------------------------------
+ * The document-term matrix of jb_terms_device by columns: per id, the documents that contain it, ascending,
+ * each with its term frequency, on the device.  It replaces copying the CSR to the host and sorting it there
+ * (np.argsort(kind="stable") over the flat id list), the last step of an indexer after search-mode cutting,
+ * UTF-16 offsets, the token filter and the vocabulary lookup.
+ *
+ * The rule (jb_postings on host arrays, jb_postings_device on device arrays: one rule, bit for bit).  Inputs:
+ * a CSR as jb_terms_device writes it, term_id / term_cnt / term_off (u64[ndocs + 1]) / nterms and the cap it
+ * was written with; nids, the index has one list per id below nids; doc_base (u32), added to every document
+ * number.  Let n = min(nterms, cap, term_off[ndocs]).
+ *  - Entry i takes part iff i < n and term_id[i] < nids.  This is jb_df_device's rule: the ids are not
+ *    trusted and no table is indexed by an id >= nids.
+ *  - Its document is doc_base + d, where d is the row with term_off[d] <= i < term_off[d + 1].  term_off is
+ *    trusted to be non-decreasing from 0; with a caller's own broken offsets the documents are unspecified,
+ *    but nothing is written outside the output arrays and nothing is read outside the input arrays.
+ *  - Output: the participating entries stably sorted by id, as post_doc (u32) and post_tf (u32, the entry's
+ *    term_cnt).  post_off (u64[nids + 1]): the list of id t is [post_off[t], post_off[t + 1]).  *nposts ==
+ *    post_off[nids].
+ *  - Stability is the whole ordering contract.  Rows come in document order, so every list is ascending by
+ *    document; a caller's own CSR that repeats an id in a row keeps those entries in input order.  For a CSR
+ *    of jb_terms_device, post_off[t + 1] - post_off[t] is jb_df_device's df[t] for the batch.
+ *  - Capacity, as everywhere here: post_off and *nposts always describe the complete result; entries with
+ *    index >= pcap are not written, and nothing else is written.  pcap = cap is always enough; the caller
+ *    checks *nposts <= pcap.  With doc_base, the lists of consecutive batches concatenate per id into the
+ *    lists of the corpus.
+ *  - Errors.  JB_EINVAL: a null pointer (arrays of capacity 0 may be NULL), an output that is an input, the
+ *    work buffer or another output, or a work buffer that is too small or not 8-byte aligned; nothing is
+ *    queued.  JB_ELIMIT: cap >= 2^32 - JB_POSTINGS_TILE, or doc_base + ndocs > 2^32.  nids == 0 is valid:
+ *    post_off[0] = 0 and *nposts = 0.
+ *
+ * jb_postings_device.  The contract is jb_terms_device's: the call queues its kernels on `stream` and
+ * returns; it does not synchronise, allocate, read anything on the host or use the per-device workspace, it
+ * holds the ctx's shared lock only while queuing, and it needs no vocabulary.  d_work is a caller-owned
+ * device buffer of nwork >= jb_postings_work_bytes(cap, nids, ndocs) bytes: 24 bytes per entry of whole
+ * tiles of JB_POSTINGS_TILE entries (two key and two payload arrays the passes alternate between) and 1 KiB
+ * per tile.  The helper is host only, non-decreasing in every argument and never 0.  The sort is a stable
+ * LSD radix sort with key = id (nids for an entry that does not take part, so those sort to the end) and
+ * payload = (document, tf), in ceil(bit_width(nids) / 8) passes of 8-bit digits, 1 to 4.  There are three
+ * launches per pass and one more, a number that depends on nids alone, never on device data; when cap == 0
+ * or nids == 0 there is none, only the memsets that zero post_off and *nposts.  No lane waits for another
+ * workgroup, and there are no global atomics.
+ *   k_post_hist     per tile, the counts of the 256 digit values (ballot match, one LDS add per group).
+ *   k_post_scan     one workgroup per digit value: that value's counters over the tiles become exclusive
+ *                   positions, and its total is written.
+ *   k_post_scatter  per tile: the 256 totals are scanned again; every entry is written at its digit's
+ *                   position for the tile plus its stable rank among the tile's equal digits (a ballot match
+ *                   per round of 64, then wave-ordered counters in LDS; jb_postings.hip says why the rank
+ *                   follows entry order).  The first pass builds keys and documents from the CSR (a search in
+ *                   term_off); the last writes post_doc and post_tf.
+ *   k_post_off      one lane per t in 0 .. nids: post_off[t] by binary search in the sorted keys; *nposts.
+ * The scatter has two forms, chosen by JB_POSTINGS_FORM at jb_open; their outputs are identical byte for
+ * byte.  Form 0 writes each entry straight from its lane to its global position; form 1 first reorders the
+ * tile by digit in LDS and writes runs.
+ * Measured on the 1 GiB corpus (tools/postings_bench.py, profiles/postings_bench.json; 73,443 documents, the
+ * 350,000-key vocabulary: 3 passes, 10 launches): the CSR's 77.3M entries take 3.26 ms in form 0, which ships
+ * as the default, and 3.37 ms in form 1 (k_post_hist 0.65 ms, k_post_scan 0.11 ms, k_post_scatter 2.49 ms
+ * against 2.59 ms, k_post_off 0.04 ms, each summed over the passes), beside 6.23 ms for the cut step, 4.88 ms
+ * for jb_terms_device and 3.22 ms for jb_df_device in the same run.  The two forms' outputs were identical byte
+ * for byte and those of jb_postings over the whole corpus (0.41 s on the host).  The path it replaces, the CSR
+ * copied to the host (72 ms) and np.argsort(kind="stable") with its gathers there, takes 7.8 s.  From pageable
+ * host memory jb_postings_batch takes 100.7 ms for 1 GiB in and 77.3M postings (0.62 GB) out, beside 36.7 ms
+ * for jb_df_batch.  The grid covers the tiles of cap, but the tiles past the entry count do nothing, so the
+ * cost follows *d_nterms, not cap.
+ *
+ * jb_postings_batch: host text in, postings out.  It runs plain Cut -> ids -> terms -> postings on ctx's first
+ * device through the buffers jb_keywords_batch keeps in the ctx (one more, that only grows; concurrent calls
+ * take turns), under jb_cut_batch_into32's cap protocol: *nposts is always the full count, and when it
+ * exceeds pcap the call returns JB_ELIMIT with only *nposts and post_off written.  doc_len (u32[ndocs], may
+ * be NULL) receives each document's token count, unknown tokens included (BM25's document length).
+ * Requirements and errors are jb_df_batch's: an attached vocabulary (JB_EINVAL), a batch under 2 GiB
+ * (JB_ELIMIT), doc_off non-decreasing, and the cut's errors pass through.  nids would normally be
+ * jb_vocab_size.  Other modes and the token filter stay on the device chain: jb_cut_device_search_into ->
+ * jb_filter_device -> jb_ids_device -> jb_terms_device -> jb_postings_device.
+ *
+ * Deliberate differences from an analyzer-fed index (Whoosh under jieba's ChineseAnalyzer): those of the
+ * term counts above, the vocabulary is closed (unknown tokens are in no list), and there are no positions,
+ * only term frequencies. */
+#define JB_POSTINGS_TILE 4096 /* entries per tile (one workgroup) */
+/* Host only, no ctx: non-decreasing in every argument, never 0. */
+size_t jb_postings_work_bytes(uint64_t max_terms, uint64_t nids, uint32_t ndocs);
+/* host only, no ctx, no GPU: the rule, and the reference the device kernels are pinned to */
+int jb_postings(const uint32_t *term_id, const uint32_t *term_cnt, const uint64_t *term_off, uint64_t nterms,
+                uint64_t cap, uint32_t ndocs, uint32_t nids, uint32_t doc_base, uint32_t *post_doc, uint32_t *post_tf,
+                uint64_t pcap, uint64_t *post_off, uint64_t *nposts);
+int jb_postings_device(jb_ctx *ctx, const uint32_t *d_term_id, const uint32_t *d_term_cnt, const uint64_t *d_term_off,
+                       const uint64_t *d_nterms, uint64_t cap, uint32_t ndocs, uint32_t nids, uint32_t doc_base,
+                       void *stream, uint32_t *d_post_doc, uint32_t *d_post_tf, uint64_t pcap, uint64_t *d_post_off,
+                       uint64_t *d_nposts, void *d_work, size_t nwork);
+/* post_off: nids + 1 host entries; post_doc / post_tf: pcap; doc_len: ndocs or NULL. */
+int jb_postings_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm,
+                      uint32_t doc_base, uint64_t pcap, uint64_t *post_off, uint32_t nids, uint32_t *post_doc,
+                      uint32_t *post_tf, uint64_t *nposts, uint32_t *doc_len);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

@@ -18,6 +18,7 @@
 #include "jb_textrank.h"
 #include "jb_filter.h"
 #include "jb_minhash.h"
+#include "jb_postings.h"
 #include "jb_wc.h"
 
 // ---------------------------------------------------------------------------
@@ -2239,6 +2240,99 @@ extern "C" int jb_cut_batch_filter(jb_ctx* ctx, const uint8_t* text, const uint6
     if (st) {
         (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
         (void)hipStreamDestroy(st);
+    }
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Postings (jb_postings.hip; the host rule, jb_postings, the argument checks, the work buffer's layout and the
+// size helper are jb_postings.cpp)
+// ---------------------------------------------------------------------------
+static_assert(JB_POSTINGS_TILE == kPostTile, "the header's constant is the kernels'");
+
+extern "C" int jb_postings_device(jb_ctx* ctx, const uint32_t* d_term_id, const uint32_t* d_term_cnt,
+                                  const uint64_t* d_term_off, const uint64_t* d_nterms, uint64_t cap, uint32_t ndocs,
+                                  uint32_t nids, uint32_t doc_base, void* stream, uint32_t* d_post_doc,
+                                  uint32_t* d_post_tf, uint64_t pcap, uint64_t* d_post_off, uint64_t* d_nposts,
+                                  void* d_work, size_t nwork) {
+    const char* who = "jb_postings_device";
+    // (the limits come first: they need no ctx)
+    if (const int rc = postings_args(who, cap, ndocs, doc_base)) return rc;
+    if (!ctx || !d_term_off || !d_nterms || !d_post_off || !d_nposts || !d_work || (cap && (!d_term_id || !d_term_cnt)) ||
+        (pcap && (!d_post_doc || !d_post_tf)))
+        return fail(JB_EINVAL, "%s: null argument", who);
+    if (const int rc = postings_alias(who, d_term_id, d_term_cnt, d_term_off, d_nterms, d_post_doc, d_post_tf, d_post_off,
+                                      d_nposts, d_work))
+        return rc;
+    if (((uintptr_t)d_work & 7u) != 0) return fail(JB_EINVAL, "%s: d_work must be 8-byte aligned", who);
+    const size_t need = jb_postings_work_bytes(cap, nids, ndocs);
+    if (nwork < need)
+        return fail(JB_EINVAL, "%s: a work buffer of %llu bytes, jb_postings_work_bytes asks for %llu", who,
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    const uint32_t form = d->lc.post_form;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_postings(d_term_id, d_term_cnt, d_term_off, d_nterms, cap, ndocs, nids, doc_base, form, d_post_doc,
+                            d_post_tf, pcap, d_post_off, d_nposts, d_work, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_postings(d_term_id, d_term_cnt, d_term_off, d_nterms, cap, ndocs, nids, doc_base, form, d_post_doc,
+                        d_post_tf, pcap, d_post_off, d_nposts, d_work, s, nullptr));
+    return JB_OK;
+}
+
+// Host text in, the batch's postings out: batch_chain, then jb_postings_device with its work buffer and its
+// outputs in the ctx's buffer [10]; post_off and the count come back first, the lists when they fit pcap.
+extern "C" int jb_postings_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                                 uint32_t doc_base, uint64_t pcap, uint64_t* post_off, uint32_t nids,
+                                 uint32_t* post_doc, uint32_t* post_tf, uint64_t* nposts, uint32_t* doc_len) {
+    const char* who = "jb_postings_batch";
+    if (!ctx || !doc_off || !post_off || !nposts || (pcap && (!post_doc || !post_tf)))
+        return fail(JB_EINVAL, "%s: null argument", who);
+    if (const int rc = postings_args(who, 0, ndocs, doc_base)) return rc;
+    bool ran = false;
+    const int rc = batch_chain(ctx, who, text, doc_off, ndocs, hmm, 0, [&](const BatchCsr& c, Arena*) -> int {
+        const size_t nwork = jb_postings_work_bytes(c.tcap, nids, ndocs), noff = ((size_t)nids + 1) * 8;
+        Arena b;
+        if (const int r = kw_arena(ctx, 10, r256(nwork) + r256(2 * c.tcap * 4) + r256(noff) + r256(8), &b)) return r;
+        void* work = b.take(nwork);
+        uint32_t* dpost = (uint32_t*)b.take(2 * c.tcap * 4);  // (documents, term frequencies)
+        uint64_t* dpoff = (uint64_t*)b.take(noff);
+        uint64_t* dn = (uint64_t*)b.take(8);
+        if (const int r = jb_postings_device(ctx, c.term_id, c.term_cnt, c.term_off, c.nterms, c.tcap, ndocs, nids,
+                                             doc_base, c.st, dpost, dpost + c.tcap, c.tcap, dpoff, dn, work, nwork))
+            return r;
+        std::vector<uint64_t> dtok;
+        if (doc_len) {
+            try {
+                dtok.resize((size_t)ndocs + 1);
+            } catch (const std::bad_alloc&) {
+                return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
+            }
+            HIPCHK(hipMemcpyAsync(dtok.data(), c.doc_tok, dtok.size() * 8, hipMemcpyDeviceToHost, c.st));
+        }
+        HIPCHK(hipMemcpyAsync(post_off, dpoff, noff, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipMemcpyAsync(nposts, dn, 8, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipStreamSynchronize(c.st));
+        ran = true;
+        if (*nposts > pcap)
+            return fail(JB_ELIMIT, "%s: %llu postings, the arrays hold %llu", who, (unsigned long long)*nposts,
+                        (unsigned long long)pcap);
+        if (doc_len)
+            for (uint32_t k = 0; k < ndocs; k++) doc_len[k] = (uint32_t)(dtok[k + 1] - dtok[k]);
+        if (*nposts) {
+            HIPCHK(hipMemcpyAsync(post_doc, dpost, *nposts * 4, hipMemcpyDeviceToHost, c.st));
+            HIPCHK(hipMemcpyAsync(post_tf, dpost + c.tcap, *nposts * 4, hipMemcpyDeviceToHost, c.st));
+        }
+        return JB_OK;
+    });
+    if (rc == JB_OK && !ran) {  // (no document: the empty index)
+        for (uint64_t t = 0; t <= nids; t++) post_off[t] = 0;
+        *nposts = 0;
     }
     return rc;
 }

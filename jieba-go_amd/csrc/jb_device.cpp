@@ -247,6 +247,7 @@ static const uint64_t kMaxPiece = 1ull << 30;  // (a piece of several documents;
 //   JB_WC_COMBINE jb_wc_add_device's count pass: 0 one global atomic per token, 1 combined in LDS (default)
 //   JB_WC_HASHBITS the word-count fingerprint's width, 1 .. 64 (default 64; fewer to test collisions)
 //   JB_MH_FORM   jb_minhash_device's signature kernel: 0 the plain form, 1 the staged form (default)
+//   JB_POSTINGS_FORM jb_postings_device's scatter kernel: 0 from the lanes (default), 1 through LDS in runs
 static int init_launch_cfg(Device* d) {
     LaunchCfg& lc = d->lc;
     lc.zh_waves = d->ncu * std::max(zh_waves_per_cu(true, false), zh_waves_per_cu(false, false));
@@ -323,6 +324,9 @@ static int init_launch_cfg(Device* d) {
     const int mhf = env_int("JB_MH_FORM", 1);
     if (mhf < 0 || mhf > 1) return fail(JB_EINVAL, "JB_MH_FORM=%d: want 0 or 1", mhf);
     lc.mh_form = (uint32_t)mhf;
+    const int pf = env_int("JB_POSTINGS_FORM", 0);
+    if (pf < 0 || pf > 1) return fail(JB_EINVAL, "JB_POSTINGS_FORM=%d: want 0 or 1", pf);
+    lc.post_form = (uint32_t)pf;
     return JB_OK;
 }
 

@@ -345,10 +345,11 @@ struct jb_ctx {
     // [4] jb_cut_batch_join's output, [5] its work buffer and output offsets,
     // [6] jb_cut_batch_charspans' work buffer and doc_units, [7] jb_wc_batch's work buffer,
     // [8] jb_minhash_batch's work buffer, signatures and shingle counts,
-    // [9] the batch filter's work buffer and filtered span list (jb_cut_batch_filter, jb_batch_filter_set)
+    // [9] the batch filter's work buffer and filtered span list (jb_cut_batch_filter, jb_batch_filter_set),
+    // [10] jb_postings_batch's work buffer and postings
     std::mutex kw_mu;
-    void* kw_buf[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t kw_cap[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void* kw_buf[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t kw_cap[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // the rule jb_cut_batch_join, jb_wc_batch and jb_minhash_batch filter by (jb_batch_filter_set; under kw_mu)
     bool bfilter_on = false;
     jb_filter_rule bfilter{0, 0, 0, 0};

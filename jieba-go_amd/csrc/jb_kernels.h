@@ -132,6 +132,7 @@ enum KernelId {
     K_WC_CLAIM, K_WC_STORE, K_WC_COUNT,
     K_MH_INIT, K_MH_HASH, K_MH_SIG, K_MH_BANDS,
     K_FILT_MARK, K_FILT_SCAN, K_FILT_WRITE,
+    K_POST_HIST, K_POST_SCAN, K_POST_SCATTER, K_POST_OFF,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -176,6 +177,9 @@ struct LaunchCfg {
     uint32_t wc_bits;        // the fingerprint keeps this many low bits of the hash (JB_WC_HASHBITS: 64; fewer
                              // only to test the collision path)
     uint32_t mh_form;        // jb_minhash_device's signature pass: 0 the plain form, 1 the staged form (JB_MH_FORM;
+                             // results do not depend on it)
+    uint32_t post_form;      // jb_postings_device's scatter: 0 from the lanes (default: 3.26 ms against 3.37 ms on the
+                             // 1 GiB corpus, profiles/postings_bench.json), 1 through LDS in runs (JB_POSTINGS_FORM;
                              // results do not depend on it)
 };
 
@@ -384,6 +388,19 @@ hipError_t run_filter(const uint8_t* d_text, uint64_t nbytes, const uint32_t* d_
                       const jb_filter_rule& rule, const DevVocab& stop, uint32_t* d_out_start, uint32_t* d_out_end,
                       uint32_t* d_out_src, uint64_t out_cap, uint64_t* d_out_doc_tok, uint64_t* d_out_ntok,
                       uint64_t* d_stats, void* d_work, hipStream_t stream, KernelTimer* timer);
+
+// Postings (jb_postings_device; jb_postings.hip, the rule's shared code is jb_postings.h's).  Tile = kPostTile
+// consecutive entries, one workgroup each.
+constexpr uint32_t kPostTile = 4096;  // JB_POSTINGS_TILE
+// Enqueue 3 * jb_postings_passes(nids) + 1 launches on `stream` (two memsets and no launch when cap or nids is
+// 0): the entries i < min(*d_nterms, cap, d_term_off[ndocs]) of the CSR whose id is below nids, stably sorted
+// by id, as d_post_doc (doc_base + row) / d_post_tf at positions below pcap, d_post_off (nids + 1) and
+// *d_nposts.  d_work holds jb_postings_work_bytes(cap, nids, ndocs) bytes, 8-byte aligned.  `form` chooses
+// the scatter kernel's form.
+hipError_t run_postings(const uint32_t* d_term_id, const uint32_t* d_term_cnt, const uint64_t* d_term_off,
+                        const uint64_t* d_nterms, uint64_t cap, uint32_t ndocs, uint32_t nids, uint32_t doc_base,
+                        uint32_t form, uint32_t* d_post_doc, uint32_t* d_post_tf, uint64_t pcap, uint64_t* d_post_off,
+                        uint64_t* d_nposts, void* d_work, hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

@@ -42,7 +42,8 @@ const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_
                                          "k_tr_final", "k_join_count", "k_join_scan", "k_join_doc", "k_join_write",
                                          "k_cs_class", "k_cs_scan", "k_cs_lookup", "k_wc_claim", "k_wc_store",
                                          "k_wc_count", "k_mh_init", "k_mh_hash", "k_mh_sig", "k_mh_bands",
-                                         "k_filt_mark", "k_filt_scan", "k_filt_write"};
+                                         "k_filt_mark", "k_filt_scan", "k_filt_write",
+                                         "k_post_hist", "k_post_scan", "k_post_scatter", "k_post_off"};
 
 hipError_t run_pipeline(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes,
                         const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, const LaunchCfg& lc,

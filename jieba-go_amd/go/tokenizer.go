@@ -914,6 +914,72 @@ func (t *Tokenizer) FitIdf(batches [][]string, useHmm bool, minDf, maxDf uint32,
 	return fit
 }
 
+// Index is the result of Postings: the inverted index of a batch under the attached vocabulary.  The list
+// of id t is Doc / Tf[Off[t]:Off[t+1]]: the documents that contain t, ascending, each with its term
+// frequency.  DocLen[d] is document d's token count, unknown tokens included (BM25's document length).
+type Index struct {
+	Off    []uint64 // vocabulary size + 1
+	Doc    []uint32
+	Tf     []uint32
+	DocLen []uint32
+}
+
+// Postings indexes one batch of documents (jb_postings_batch): plain Cut, the vocabulary lookup, the term
+// counts and their transposition all run on the GPU, and only the index comes back.  Document numbers are
+// docBase + the document's position in docs, so the lists of consecutive batches with a running docBase
+// concatenate per id into the lists of the corpus.  With mini_dict.txt, the vocabulary and the documents
+// of FitIdf's comment, the list of id 0 (abc) is documents {0, 1, 4} with frequencies {2, 1, 1}.
+func (t *Tokenizer) Postings(docs []string, useHmm bool, docBase uint32) Index {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	nv := int64(C.jb_vocab_size(t.ctx))
+	if nv < 0 {
+		panic("jiebahip: Postings without a vocabulary (SetVocab)")
+	}
+	ix := Index{Off: make([]uint64, nv+1), DocLen: make([]uint32, len(docs))}
+	if len(docs) == 0 {
+		return ix
+	}
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	off := make([]uint64, len(docs)+1)
+	total := 0
+	for i, d := range docs {
+		total += len(d)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, d := range docs {
+		b = append(b, d...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	// a first guess of one posting per four bytes; the full count comes back with JB_ELIMIT
+	pcap := uint64(total/4 + 16)
+	var n C.uint64_t
+	for pass := 0; ; pass++ {
+		ix.Doc = make([]uint32, pcap)
+		ix.Tf = make([]uint32, pcap)
+		rc := C.jb_postings_batch(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+			C.uint32_t(len(docs)), hmm, C.uint32_t(docBase), C.uint64_t(pcap), (*C.uint64_t)(unsafe.Pointer(&ix.Off[0])),
+			C.uint32_t(nv), (*C.uint32_t)(unsafe.Pointer(&ix.Doc[0])), (*C.uint32_t)(unsafe.Pointer(&ix.Tf[0])), &n,
+			(*C.uint32_t)(unsafe.Pointer(&ix.DocLen[0])))
+		if rc == C.JB_ELIMIT && uint64(n) > pcap && pass == 0 {
+			pcap = uint64(n)
+			continue
+		}
+		if rc != C.JB_OK {
+			// JB_EPANIC: the reference panics on this input
+			panic("jiebahip: " + lastError())
+		}
+		break
+	}
+	ix.Doc = ix.Doc[:n]
+	ix.Tf = ix.Tf[:n]
+	return ix
+}
+
 // CutParallel (tokenizer.go:81) returns the tokens of Cut in document order.
 // The library splits the work itself: the text goes to the device in pieces cut
 // at Han-run starts (jb_split_points), and over every device of a multi-device

@@ -160,6 +160,38 @@ Tokenizer::IdfFit Tokenizer::FitIdf(const std::vector<std::vector<std::string>>&
     return fit;
 }
 
+Tokenizer::Index Tokenizer::Postings(const std::vector<std::string>& docs, bool useHmm, uint32_t docBase) {
+    const int64_t nv = jb_vocab_size(ctx_);
+    if (nv < 0) throw Error(JB_EINVAL, "Postings: no vocabulary attached (SetVocab)");
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& d : docs) {
+        all += d;
+        off.push_back(all.size());
+    }
+    Index ix;
+    ix.off.assign((size_t)nv + 1, 0);
+    ix.docLen.assign(docs.size(), 0);
+    // (a first guess of one posting per four bytes; the full count comes back with JB_ELIMIT)
+    uint64_t n = 0, pcap = all.size() / 4 + 16;
+    for (int pass = 0; pass < 2; pass++) {
+        ix.doc.resize(pcap);
+        ix.tf.resize(pcap);
+        const int rc = jb_postings_batch(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)docs.size(), useHmm ? 1 : 0,
+                                         docBase, pcap, ix.off.data(), (uint32_t)nv, ix.doc.data(), ix.tf.data(), &n,
+                                         ix.docLen.data());
+        if (rc == JB_ELIMIT && n > pcap && pass == 0) {
+            pcap = n;
+            continue;
+        }
+        check(rc);
+        break;
+    }
+    ix.doc.resize(n);
+    ix.tf.resize(n);
+    return ix;
+}
+
 std::vector<std::vector<Tokenizer::Rank>> Tokenizer::TextRank(const std::vector<std::string>& docs,
                                                               const std::vector<uint8_t>& keep, uint32_t topK,
                                                               uint32_t span, uint32_t iters, bool useHmm) {

@@ -85,6 +85,16 @@ public:
     };
     IdfFit FitIdf(const std::vector<std::vector<std::string>>& batches, bool useHmm = true, uint32_t minDf = 1,
                   uint32_t maxDf = JB_DF_NOMAX, const std::vector<uint8_t>& keep = {});
+    // Postings (jb_postings_batch in jiebahip.h): the inverted index of a batch under the attached vocabulary.
+    // The list of id t is doc / tf[off[t] .. off[t + 1]): the documents that contain t, ascending (docBase + the
+    // document's index in docs), each with its term frequency; docLen[d] is document d's token count, unknown
+    // tokens included.  Cut, counted and transposed on the GPU: only the index comes back.  With a running
+    // docBase the lists of consecutive batches concatenate per id into the lists of the corpus.
+    struct Index {
+        std::vector<uint64_t> off;  // vocabulary size + 1
+        std::vector<uint32_t> doc, tf, docLen;
+    };
+    Index Postings(const std::vector<std::string>& docs, bool useHmm = true, uint32_t docBase = 0);
     // TextRank keywords (jieba.analyse.textrank; jb_textrank_batch in jiebahip.h, with the rule and its
     // differences from jieba's): per document the topK words of the attached vocabulary by PageRank over
     // the co-occurrence graph of the kept tokens within `span` positions, `iters` Jacobi rounds, best

@@ -44,6 +44,7 @@ JB_MH_NOKEY = 0xFFFFFFFFFFFFFFFF  # every band key of a document without shingle
 JB_TC_HAN, JB_TC_ALNUM, JB_TC_NUM, JB_TC_OTHER, JB_TC_INVALID = 1, 2, 4, 8, 16  # the token filter's classes
 JB_FILTER_STOP = 1  # the filter rule's flag: drop the tokens found in the stop set
 JB_FILTER_TILE = 2048  # tokens per tile of jb_filter_device
+JB_POSTINGS_TILE = 4096  # entries per tile of jb_postings_device
 _CLASSES = {"han": JB_TC_HAN, "alnum": JB_TC_ALNUM, "num": JB_TC_NUM, "other": JB_TC_OTHER, "invalid": JB_TC_INVALID}
 _TOKENIZE_MODES = {"default": JB_MODE_CUT, "search": JB_MODE_SEARCH, "full": JB_MODE_FULL}
 
@@ -71,6 +72,7 @@ EXPORTS = [
     "jb_minhash_bands_device", "jb_minhash_batch",
     "jb_stopwords_set", "jb_stopwords_size", "jb_filter_work_bytes", "jb_filter", "jb_filter_device",
     "jb_cut_batch_filter", "jb_batch_filter_set",
+    "jb_postings_work_bytes", "jb_postings", "jb_postings_device", "jb_postings_batch",
 ]
 
 
@@ -325,6 +327,14 @@ def lib():
                                        C.c_uint64, vp, vp, vp, vp, C.c_size_t]
         L.jb_cut_batch_filter.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, C.c_uint64, vp, vp, vp]
         L.jb_batch_filter_set.argtypes = [vp, vp]
+        L.jb_postings_work_bytes.restype = C.c_size_t
+        L.jb_postings_work_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+        L.jb_postings.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
+                                  C.c_uint64, vp, vp]
+        L.jb_postings_device.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp,
+                                         C.c_uint64, vp, vp, vp, C.c_size_t]
+        L.jb_postings_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64, vp, C.c_uint32, vp, vp,
+                                        vp, vp]
         L.jb_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
         L.jb_device_free.argtypes = [vp, vp]
         L.jb_device_free.restype = None
@@ -1224,6 +1234,80 @@ class Tokenizer:
         return [[all_[s[k]:e[k]].decode("utf-8", "replace") for k in range(dtok[d], dtok[d + 1])]
                 for d in range(len(docs))]
 
+    # -- postings (the inverted index) ------------------------------------------
+    def postings_device(self, d_term_id, d_term_cnt, d_term_off, d_nterms, cap, ndocs, nids, doc_base, d_post_doc,
+                        d_post_tf, pcap, d_post_off, d_nposts, d_work, nwork, stream_ptr=0):
+        """jb_postings_device over raw device pointers: the CSR of terms_device by columns.  The entries
+        i < min(*d_nterms, cap, term_off[ndocs]) with id < nids, stably sorted by id, as u32 documents (doc_base +
+        row) and term frequencies at positions below pcap, u64 post_off[nids + 1] and a u64 count; queued on the
+        stream.  d_work: postings_work_bytes(cap, nids, ndocs) bytes."""
+        _check(lib().jb_postings_device(self.h, C.c_void_p(d_term_id), C.c_void_p(d_term_cnt), C.c_void_p(d_term_off),
+                                        C.c_void_p(d_nterms), cap, ndocs, nids, doc_base, C.c_void_p(stream_ptr),
+                                        C.c_void_p(d_post_doc), C.c_void_p(d_post_tf), pcap, C.c_void_p(d_post_off),
+                                        C.c_void_p(d_nposts), C.c_void_p(d_work), nwork))
+
+    def postings_batch(self, buf, doc_off, hmm, doc_base=0, nids=None, pcap=None):
+        """jb_postings_batch: host batch -> (post_off u64[nids + 1], post_doc u32[n], post_tf u32[n], doc_len
+        u32[ndocs]) of the plain cut's terms under the attached vocabulary; document numbers start at doc_base.
+        nids defaults to vocab_size.  With `pcap` given the arrays hold that many entries and a longer result
+        raises JbError(JB_ELIMIT); otherwise they are grown to the count the first call reports."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        nd = len(doc_off) - 1
+        if nids is None:
+            nids = max(self.vocab_size, 0)
+        cap = max(1024, int(doc_off[-1] - doc_off[0]) // 4) if pcap is None else pcap
+        post_off = np.zeros(nids + 1, np.uint64)
+        doc_len = np.zeros(nd, np.uint32)
+        n = C.c_uint64()
+        p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        for _ in range(2):
+            pd, pt = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+            rc = lib().jb_postings_batch(self.h, buf.ctypes.data, doc_off.ctypes.data, nd, int(hmm), doc_base, cap,
+                                         post_off.ctypes.data, nids, p(pd), p(pt), C.byref(n), p(doc_len))
+            if rc == JB_ELIMIT and n.value > cap and pcap is None:
+                cap = n.value
+                continue
+            _check(rc)
+            break
+        return post_off, pd[:n.value], pt[:n.value], doc_len
+
+    def build_index(self, batches, hmm=True):
+        """Index a corpus given as an iterable of batches, each a list of documents (str / bytes), under the
+        attached vocabulary: (post_off u64[vocab_size + 1], post_doc u32, post_tf u32, doc_len u32[ndocs], ndocs).
+        The list of id t is post_doc / post_tf[post_off[t]:post_off[t + 1]], ascending by document number
+        (documents are numbered in the order they come); doc_len is each document's token count."""
+        nv = self.vocab_size
+        if nv < 0:
+            raise JbError(JB_EINVAL, "build_index: no vocabulary attached (set_vocab)")
+        parts, lens, ndocs = [], [], 0
+        for batch in batches:
+            docs = [_b(t) for t in batch]
+            if not docs:
+                continue
+            off = np.zeros(len(docs) + 1, np.uint64)
+            off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+            po, pd, pt, dl = self.postings_batch(np.frombuffer(b"".join(docs) + b"\0", np.uint8), off, hmm, ndocs, nv)
+            parts.append((po, pd, pt))
+            lens.append(dl)
+            ndocs += len(docs)
+        post_off = np.zeros(nv + 1, np.uint64)
+        for po, _, _ in parts:
+            post_off += po
+        total = int(post_off[nv])
+        post_doc, post_tf = np.empty(total, np.uint32), np.empty(total, np.uint32)
+        # batch b's list of id t goes behind the lists of id t of the batches before it
+        at = post_off[:-1].astype(np.int64)
+        for po, pd, pt in parts:
+            n = np.diff(po.astype(np.int64))
+            if len(pd):
+                dst = np.repeat(at - po[:-1].astype(np.int64), n) + np.arange(len(pd), dtype=np.int64)
+                post_doc[dst] = pd
+                post_tf[dst] = pt
+            at += n
+        doc_len = np.concatenate(lens) if lens else np.zeros(0, np.uint32)
+        return post_off, post_doc, post_tf, doc_len, ndocs
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -1521,6 +1605,31 @@ def filter_spans(text, starts, ends, doc_tok, rule=None, stop=None, ntok=None, c
                            stop.h if stop is not None else None, p(os_), p(oe), p(osrc), out_cap, odt.ctypes.data,
                            C.byref(n), stats.ctypes.data))
     return os_, oe, osrc, odt, n.value, stats
+
+
+def postings_work_bytes(max_terms, nids, ndocs):
+    """jb_postings_work_bytes: bytes of the work buffer jb_postings_device needs (host only)."""
+    return lib().jb_postings_work_bytes(max_terms, nids, ndocs)
+
+
+def postings(term_id, term_cnt, term_off, nids, doc_base=0, nterms=None, cap=None, pcap=None):
+    """jb_postings (host only): the postings rule of jiebahip.h on host arrays (a CSR: u32 ids and counts, u64
+    term_off[ndocs + 1]).  Returns (post_doc, post_tf, post_off u64[nids + 1], nposts); the arrays have pcap
+    entries (default cap), of which min(nposts, pcap) are written."""
+    ti = np.ascontiguousarray(term_id, np.uint32)
+    tc = np.ascontiguousarray(term_cnt, np.uint32)
+    to = np.ascontiguousarray(term_off, np.uint64)
+    nd = len(to) - 1
+    cap = len(ti) if cap is None else cap
+    nterms = len(ti) if nterms is None else nterms
+    pcap = cap if pcap is None else pcap
+    pd, pt = np.zeros(pcap, np.uint32), np.zeros(pcap, np.uint32)
+    po = np.zeros(nids + 1, np.uint64)
+    n = C.c_uint64()
+    p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    _check(lib().jb_postings(p(ti), p(tc), to.ctypes.data, nterms, cap, nd, nids, doc_base, p(pd), p(pt), pcap,
+                             po.ctypes.data, C.byref(n)))
+    return pd, pt, po, n.value
 
 
 def _unit(unit):
