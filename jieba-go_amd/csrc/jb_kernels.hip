@@ -58,7 +58,11 @@ constexpr uint32_t kMwOffScan = (kMwOffWl + kTileE * 2u + 3u) & ~3u;      // u32
 // the walk list is grouped by the line of each walk's first probe
 constexpr uint32_t kMwSortB = 64u;                   // buckets of the walk-list sort
 constexpr uint32_t kMwOffHist = kMwOffScan + 8u * 4u;  // u32 per bucket
-constexpr uint32_t kMwLds = kMwOffHist + kMwSortB * 4u;
+constexpr uint32_t kMwOffDump = kMwOffHist + kMwSortB * 4u;  // where the empty slots of a lane's seven store
+constexpr uint32_t kMwLds = kMwOffDump + 16u;
+constexpr uint32_t kMwDumpC = kMwOffDump / 8u;                  // ... as an index of s_c (u64)
+constexpr uint32_t kMwDumpE = (kMwOffDump + 8u - kMwOffE) / 4u;  // ... and of s_e (u32)
+static_assert(kMwOffDump % 8u == 0u && (kMwOffDump + 8u - kMwOffE) % 4u == 0u, "the dump cells are aligned");
 constexpr uint32_t kMwOffHot = (kMwOffE + 15u) & ~15u;  // hot level-1 rows (phase 1 only), under the entries
 static_assert(kMwOffHot % 16u == 0u && kMwOffHot + 10u * JB_HOT_SLOTS <= kMwOffDb && JB_HOT_SLOTS == 512u,
               "k_mark_walk: the hot rows fit under the entry list, 256 threads stage them");
@@ -117,9 +121,6 @@ __device__ __forceinline__ uint32_t ent_w(uint32_t e) { return 3u + ((e >> 17) &
 // workgroups per CU instead of 6 (k_mark_walk is latency-bound: 0.695 -> 0.618 ms).
 #ifndef JB_MW_SGPR
 #define JB_MW_SGPR 80
-#endif
-#ifndef JB_MW_WALKS
-#define JB_MW_WALKS 1  // trie walks per lane at once (2 measured slower)
 #endif
 #define JB_MW_ATTR __attribute__((amdgpu_num_sgpr(JB_MW_SGPR), amdgpu_waves_per_eu(8, 8)))
 __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __restrict__ text, uint64_t nbytes,
@@ -181,22 +182,24 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
     if (threadIdx.x < kMwSortB) s_hist[threadIdx.x] = 0u;
     const uint64_t p0 = t0 + threadIdx.x * 16u;
     // doc-start / past-the-end mask, bit k <-> byte p0 - 4 + k (k < 24)
-    uint64_t M;
+    // (only bits 0-23 are read, so 32 bits hold it: one v_alignbit across the two document
+    // words, and 32-bit shifts wherever it is used)
+    uint32_t M;
     {
         const int64_t base = (int64_t)p0 - 4;
         if (base >= 0) {
             const uint64_t wi = (uint64_t)base >> 5;
             const uint32_t off = (uint32_t)base & 31u;
-            const uint64_t lo = wi < lastw ? docbits[wi] : 0u;
-            const uint64_t hi = wi + 1 < lastw ? docbits[wi + 1] : 0u;
-            M = ((hi << 32) | lo) >> off;
+            const uint32_t lo = wi < lastw ? docbits[wi] : 0u;
+            const uint32_t hi = wi + 1 < lastw ? docbits[wi + 1] : 0u;
+            M = __builtin_amdgcn_alignbit(hi, lo, off);
         } else {
-            M = (uint64_t)docbits[0] << 4;  // p0 == 0: window bytes -4..-1 do not exist (zeros)
+            M = docbits[0] << 4;  // p0 == 0: window bytes -4..-1 do not exist (zeros)
         }
         if (nbytes < p0 + 20) {  // bytes at or past the end stop every decode
-            const int64_t endk = (int64_t)nbytes - base;
-            if (endk <= 0) M = ~0ull;
-            else M |= ~0ull << endk;
+            const int64_t endk = (int64_t)nbytes - base;  // (< 24)
+            if (endk <= 0) M = ~0u;
+            else M |= ~0u << (uint32_t)endk;
         }
     }
     reinterpret_cast<uint4*>(s_t)[threadIdx.x] = va;
@@ -261,24 +264,24 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
         // branch-free classification.  A missing lead (fewer than 7) reads position 0 and is
         // masked out.
         uint32_t l = lead, slow = 0, xs[7], vm = 0;
-        uint64_t kq = 0;  // the leads' positions, 5 bits each (registers: 63 VGPRs, 8 waves per SIMD)
+        uint32_t kq[2] = {0u, 0u};  // the leads' positions, 5 bits each, six to a word (registers: 8 waves per SIMD)
 #pragma unroll
         for (int i = 0; i < 7; i++) {
             vm |= (l != 0u ? 1u : 0u) << i;
             const uint32_t k = l ? (uint32_t)__builtin_ctz(l) : 0u;
-            kq |= (uint64_t)k << (5 * i);
+            kq[i / 6] |= k << (5 * (i % 6));
             xs[i] = lds4(win, k);
             l &= l - 1u;
         }
 #pragma unroll
         for (int i = 0; i < 7; i++) {
             const bool v = (vm >> i) & 1u;
-            const uint32_t k = (uint32_t)(kq >> (5 * i)) & 31u, x = xs[i];
+            const uint32_t k = (kq[i / 6] >> (5 * (i % 6))) & 31u, x = xs[i];
             const uint32_t b0 = x & 0xFFu;
             const uint32_t r = ((b0 & 0x0Fu) << 12) | (((x >> 8) & 0x3Fu) << 6) | ((x >> 16) & 0x3Fu);
             const bool plain = (b0 - 0xE1u < 12u) | (b0 - 0xEEu < 2u);
             const bool rare = (r - 0x2E80u < 0x180u) | (r - 0xF900u < 0x200u);
-            const bool ok = ((x & 0x00C0C000u) == 0x00808000u) & (((uint32_t)(M >> (k + 1u)) & 3u) == 0u);
+            const bool ok = ((x & 0x00C0C000u) == 0x00808000u) & (((M >> (k + 1u)) & 3u) == 0u);
             const uint32_t o = r - 0x3000u;
             const bool h = (r - 0x4E00u <= 0x9FFCu - 0x4E00u) | (r - 0x3400u <= 0x4DBFu - 0x3400u) |
                            ((o < 64u) & (((k3000 >> (o & 63u)) & 1ull) != 0ull));
@@ -297,7 +300,7 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
     while (lead) {
         const uint32_t k = __builtin_ctz(lead);
         lead &= lead - 1u;
-        const uint32_t lim = 1u + (uint32_t)__builtin_ctzll(((M >> (k + 1)) & 7ull) | 8ull);
+        const uint32_t lim = 1u + (uint32_t)__builtin_ctz(((M >> (k + 1u)) & 7u) | 8u);
         uint32_t r;
         const uint32_t w = dec_lead(lds4(win, k), lim, &r);
         covered |= ((1u << (w - 1u)) - 1u) << (k + 1u);  // (nothing for w == 1)
@@ -306,7 +309,7 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
     if (p0 == 0) hanb &= ~0xFu;
     uint32_t valid = 0xFFFF0u;  // window indices 4..19 that are inside the batch
     if (nbytes < p0 + 16) valid = nbytes > p0 ? ((1u << (uint32_t)(nbytes - p0)) - 1u) << 4 : 0u;
-    const uint32_t bs = ~covered & valid & ((uint32_t)M | (hanb ^ (hanb << 1)));
+    const uint32_t bs = ~covered & valid & (M | (hanb ^ (hanb << 1)));
     const uint32_t bmask = (bs >> 4) & 0xFFFFu, zmask = ((bs & hanb) >> 4) & 0xFFFFu;
     __builtin_nontemporal_store(bmask | (zmask << 16), lanemask + tile * 256u + threadIdx.x);  // (read on other XCDs)
     uint32_t tot;
@@ -335,11 +338,15 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
             const uint32_t r = ((rowp[i >> 1] >> (16 * (i & 1))) & 0xFFFFu) + 0x3300u;
             hit |= (((hsm >> i) & 1u) & (tg[i] == r ? 1u : 0u)) << i;
         }
+        // (one exec mask per slot, on the gather alone: a slot without a Han start keeps whatever
+        // the hot read gave, which goes to the dump cell below; the row is 16 bits, so the address
+        // is the scalar table base plus a 32-bit lane offset)
+        const uint8_t* const l1row8 = reinterpret_cast<const uint8_t*>(im.l1row);
+        const uint32_t miss = hsm & ~hit;
 #pragma unroll
         for (int i = 0; i < 7; i++) {
             const uint32_t row = (rowp[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-            if (!((hit >> i) & 1u)) cl[i] = 0ull;
-            if ((~hit & hsm) >> i & 1u) cl[i] = im.l1row[row];
+            if ((miss >> i) & 1u) cl[i] = *reinterpret_cast<const uint64_t*>(l1row8 + (row << 3));
         }
     }
     uint32_t nent;
@@ -397,10 +404,12 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
         }
 #pragma unroll
         for (int i = 0; i < 7; i++) {  // (s_e is not under the staged text)
-            if ((hsm >> i) & 1u)
-                s_e[o + __popc(hsm & ((1u << i) - 1u))] = jb_l1row_code(cl[i]) | (((w4m >> i) & 1u) << 17) |
-                                                          ((threadIdx.x * 16u + ((kp >> (4 * i)) & 15u)) << 18);
-            cl[i] = ((hsm >> i) & 1u) ? jb_l1row_cell(cl[i]) : 0ull;
+            // every slot stores, an empty one to the dump word: a select of the index instead of an
+            // exec-mask branch around each of the seven stores
+            const bool on = (hsm >> i) & 1u;
+            s_e[on ? o + __popc(hsm & ((1u << i) - 1u)) : kMwDumpE] =
+                jb_l1row_code(cl[i]) | (((w4m >> i) & 1u) << 17) | ((threadIdx.x * 16u + ((kp >> (4 * i)) & 15u)) << 18);
+            cl[i] = jb_l1row_cell(cl[i]);
         }
         // Lookahead (the last lane, while the cell loads fly): when the tile's last
         // Han rune ends at or past the tile end, the runes that continue its run
@@ -440,8 +449,8 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
         __syncthreads();  // every lane has decoded from s_t: its bytes now take the cells
         if (stamps) c1b = __builtin_amdgcn_s_memtime();  // (codes, cells and lookahead in)
 #pragma unroll
-        for (int i = 0; i < 7; i++)
-            if ((hsm >> i) & 1u) s_c[o + __popc(hsm & ((1u << i) - 1u))] = cl[i];
+        for (int i = 0; i < 7; i++)  // (an empty slot's to the dump cell, as above)
+            s_c[((hsm >> i) & 1u) ? o + __popc(hsm & ((1u << i) - 1u)) : kMwDumpC] = cl[i];
     }
     __syncthreads();
     // Run links, then level 1 of every entry: a rune that is absent, has count 0,
@@ -449,34 +458,33 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
     // which only its own walk would read); the others go on the walk list.
     const uint32_t nla = s_nla;
     uint32_t wm = 0;  // which of the thread's entries went on the walk list
+    // (The loop runs once per 256 entries, up to six times for a tile of Han text: its reads
+    // are unconditional, the cases are selects on the cell's two 32-bit halves, and what is
+    // the same for every entry — this workgroup's share of the entries, plainw — is outside.)
+    const uint32_t pe0 = (nent * part) >> split, pe1 = (nent * (part + 1u)) >> split;
+    const bool plainw = im.plainw != 0;  // (else weights that are +Inf or NaN: k_zh folds every rune literally)
     for (uint32_t i = threadIdx.x, k = 0; i < nent; i += 256u, k++) {
-        const uint32_t e = s_e[i];
-        const uint32_t nxt = ent_pos(e) + ent_w(e);
-        uint32_t f = 0;
-        if (nxt >= kTileBytes) f = nla ? kEntCont : 0u;  // (the tile's last rune: the lookahead goes on)
-        else if (i + 1u < nent && ent_pos(s_e[i + 1u]) == nxt && !((s_db[nxt >> 5] >> (nxt & 31u)) & 1u)) f = kEntCont;
-        s_e[i] = e | f;
+        const uint32_t e = s_e[i], e1 = s_e[i + 1u];  // (entry nent: a lookahead entry or stale, then not used)
         const uint64_t c1 = s_c[i];
-        const uint32_t fc = jb_cell_fc(c1), wi = jb_cell_widx(c1);
-        uint64_t r1 = 0;
-        bool go = false;
-        if (jb_cell_check(c1) != JB_CHECK_ROOT) {
-            r1 = 1ull | ((uint64_t)(JB_WIDX_ABSENT + 1u) << kRecTop);  // absent: the single edge only, Log(1) (:468-471)
-        } else if (wi > kRecIdxMax && fc != JB_FC_NEG) {
-            r1 = 0ull;  // the weight index does not fit a record: k_zh walks this rune
-        } else if (fc == JB_FC_ZERO) {
-            r1 = 1ull | ((uint64_t)(wi + 1u) << kRecTop);  // count 0: the single edge only, Log(0) = -Inf
-        } else {
-            if (fc == JB_FC_POS) r1 = 1ull | ((uint64_t)(wi + 1u) << kRecTop);  // (a negative count has no edge)
-            go = jb_cell_hc(c1) != 0u && f != 0u;
-        }
-        if (!im.plainw) {  // weights that are +Inf or NaN: k_zh folds every rune literally
-            r1 = 0ull;
-            go = false;
-        }
+        const uint32_t nxt = ent_pos(e) + ent_w(e);                 // <= kTileBytes + 3: s_db has that word
+        const uint32_t dbit = (s_db[nxt >> 5] >> (nxt & 31u)) & 1u;  // a document starts at the next byte
+        const bool cont = nxt >= kTileBytes ? nla != 0u  // (the tile's last rune: the lookahead goes on)
+                                            : (i + 1u < nent) & (ent_pos(e1) == nxt) & (dbit == 0u);
+        s_e[i] = e | (cont ? kEntCont : 0u);
+        const uint32_t clo = (uint32_t)c1, chi = (uint32_t)(c1 >> 32);
+        const uint32_t fc = (chi >> 12) & 3u, wi1 = (chi >> 15) + 1u;  // jb_cell_fc, jb_cell_widx + 1
+        // absent: the single edge only, Log(1) (:468-471).  A weight index that does not fit a
+        // record (and is used: the count is not negative): record 0, k_zh walks this rune.
+        // Count 0: the single edge only, Log(0) = -Inf.  A negative count has no edge.
+        const bool root = (clo & 0x3FFFFFu) == JB_CHECK_ROOT;
+        const bool fits = !(wi1 > kRecIdxMax + 1u && fc != JB_FC_NEG);
+        const bool edge = plainw & (!root | (fits & ((fc == JB_FC_ZERO) | (fc == JB_FC_POS))));
+        const uint32_t r1lo = edge ? 1u : 0u;
+        const uint32_t r1hi = edge ? (root ? wi1 : JB_WIDX_ABSENT + 1u) << (kRecTop - 32u) : 0u;
+        const bool go = plainw & root & fits & (fc != JB_FC_ZERO) & ((chi & 0x4000u) != 0u) & cont;  // (jb_cell_hc)
         if (!go) {
-            s_c[i] = r1;
-        } else if (i < ((nent * part) >> split) || i >= ((nent * (part + 1u)) >> split)) {
+            s_c[i] = ((uint64_t)r1hi << 32) | r1lo;
+        } else if (i < pe0 || i >= pe1) {
             // (another workgroup of the tile walks it)
         } else {
             // Walks whose first probes fall in one 128-byte line of cells go next to each
@@ -484,7 +492,7 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
             // counting sort by a hash of that line (the order within a bucket does not
             // matter).  The bucket and the rank in it wait in the entry cell's check
             // field, which a walk never reads (its check is the root).
-            const uint32_t ln = (jb_cell_base(c1) + ent_code(s_e[i + 1u])) >> 4;
+            const uint32_t ln = (jb_cell_base(c1) + ent_code(e1)) >> 4;
             const uint32_t b = (ln * 0x9E3779B1u) >> 26;
             static_assert(kMwSortB == 64u && kTileEX <= 2048u, "bucket (6 bits) and rank (11 bits) in the check field");
             const uint32_t rk = atomicAdd(&s_hist[b], 1u);
@@ -512,8 +520,9 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
     if (stamps) c2 = __builtin_amdgcn_s_memtime();
     // ---- walks: wave w takes a quarter of the walk list ------------------------------
     const uint32_t* ent = s_e;
-    const uint32_t wv = threadIdx.x >> 6;
-    const uint32_t nwl = s_nwl;
+    // (the list bounds are wave-uniform: kept in scalar registers)
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t nwl = __builtin_amdgcn_readfirstlane(s_nwl);
     uint32_t head = (nwl * wv) >> 2;
     const uint32_t hi = (nwl * (wv + 1u)) >> 2;
     // Walk state per lane: entry j of the current node's rune, start entry js,
@@ -522,97 +531,92 @@ __global__ __launch_bounds__(256) JB_MW_ATTR void k_mark_walk(const uint8_t* __r
     // at the last field, kRecTop, pushing the earlier ones a field down: after n
     // edges they fill the last n fields, the record's layout, and the first
     // 4 - n fields are still 0).  One trip = one probe per walk, with selects
-    // instead of branches.  Each lane runs JB_MW_WALKS walks side by side (two:
-    // two probes in flight per lane and trip, so the wave pays the probe round
-    // trip half as often; the walk phase is latency-bound).
-    struct Walk {
-        bool act, ovf;
-        uint32_t j, js, id, base, len, nedge, m, en;
-        uint64_t rw;
-    };
-    Walk wk[JB_MW_WALKS];
-#pragma unroll
-    for (int q = 0; q < JB_MW_WALKS; q++) {
-        wk[q].act = wk[q].ovf = false;
-        wk[q].j = wk[q].js = wk[q].id = wk[q].base = wk[q].len = wk[q].nedge = wk[q].m = wk[q].en = 0u;
-        wk[q].rw = 0ull;
-    }
+    // instead of branches.  (Two walks per lane measured slower)
+    //
+    // The trip is the only part of the kernel that runs many times per wave, so its
+    // state is kept in the form that takes the fewest instructions (DESIGN.md §4.2,
+    // round 7): the shift register as two 32-bit halves (rlo, rhi: a step is one
+    // v_alignbit and one shift, and the first field, bits 8-21 of rlo, is not 0 exactly
+    // when four edges are in); the edge length as the mask bit lbit = 1 << (len - 1) the
+    // next edge would set, doubled with saturation every trip (past bit 7: the edge is longer
+    // than kEdgeMaxL; 0, which no walk of any length reaches: the lane has no walk, so that "idle" is one compare on a register and not
+    // a flag the compiler moves between a scalar mask and a register twice a trip); the
+    // entry index as the byte offset ja into the entry list, the start entry as the byte
+    // offset js8 of its cell, the node as id1 = cell index + 1, which is what a child's check
+    // holds; and an overflow ends its walk in the same trip, so it is no state at all.
+    static_assert(kEdgeMaxL == 8u && kEdgeIdxBits == 14u && kRecTop == 50u, "the walk trip's 32-bit record halves");
+    const uint8_t* const cells8 = reinterpret_cast<const uint8_t*>(im.cells);
+    const uint8_t* const ent8 = reinterpret_cast<const uint8_t*>(s_e);
+    uint8_t* const sc8 = reinterpret_cast<uint8_t*>(s_c);
+    uint32_t ja = 0, js8 = 0, id1 = 0, base = 0, en = 0, m = 0, lbit = 0, rlo = 0, rhi = 0;
     for (;;) {
-#pragma unroll
-        for (int q = 0; q < JB_MW_WALKS; q++) {  // idle walks take the next starts of the wave's list
-            Walk& w = wk[q];
-            const uint64_t need = __ballot(!w.act);
+        // idle lanes take the next starts of the wave's list (skipped by the whole wave when
+        // no lane is idle or the list is used up, which is most trips of a wave's tail)
+        const uint64_t need = __ballot(lbit == 0u);
+        if (need != 0ull && head < hi) {
             const uint32_t rank =
                 __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
             const uint32_t j0 = head + rank;
-            const bool fresh = !w.act && j0 < hi;
             head = min(hi, head + (uint32_t)__popcll(need));
-            if (fresh) {  // a walk from the list: its rune has children and the run goes on in the tile
-                w.js = s_wl[j0];
-                w.j = w.js;
-                const uint64_t c = s_c[w.j];
-                w.id = ent_code(ent[w.j]);  // its level-1 cell
-                w.base = jb_cell_base(c);
+            if (lbit == 0u && j0 < hi) {  // a walk from the list: its rune has children and the run goes on in the tile
+                const uint32_t js = s_wl[j0];
+                ja = js * 4u;
+                js8 = js * 8u;
+                const uint64_t c = s_c[js];
+                id1 = ent_code(ent[js]) + 1u;  // its level-1 cell
+                en = ent[js + 1u];
+                base = jb_cell_base(c);
                 const bool pos = jb_cell_fc(c) == JB_FC_POS;  // (weight index < 2^14: checked by the run links)
-                w.m = pos ? 1u : 0u;
-                w.nedge = w.m;
-                w.rw = pos ? (uint64_t)(jb_cell_widx(c) + 1u) << kRecTop : 0ull;
-                w.len = 1u;
-                w.ovf = false;
-                w.act = true;
-                w.en = ent[w.j + 1u];
+                m = pos ? 1u : 0u;
+                rlo = 0u;
+                rhi = pos ? (jb_cell_widx(c) + 1u) << (kRecTop - 32u) : 0u;
+                lbit = 2u;
             }
         }
-        uint64_t child[JB_MW_WALKS];
-        uint32_t tt[JB_MW_WALKS], en2[JB_MW_WALKS];
-#pragma unroll
-        for (int q = 0; q < JB_MW_WALKS; q++) {  // every walk's probe issued before any is used
-            tt[q] = wk[q].base + ent_code(wk[q].en);
-            child[q] = wk[q].act ? im.cells[tt[q]] : 0ull;
-            en2[q] = ent[wk[q].j + 2u];  // (used only when the walk goes on: then entry j + 2 exists)
-        }
-#pragma unroll
-        for (int q = 0; q < JB_MW_WALKS; q++) {
-            Walk& w = wk[q];
-            if (w.act) {
-                const uint64_t ch = child[q];
-                const bool hit = dat_hit(ch, w.id);
-                ++w.len;
-                const uint32_t wi = jb_cell_widx(ch);
-                const bool pos = hit && jb_cell_fc(ch) == JB_FC_POS;
-                const bool bad = pos && (w.len > kEdgeMaxL || w.nedge >= 4u || wi > kRecIdxMax);
-                const bool add = pos && !bad;
-                w.ovf |= bad;
-                w.m |= add ? 1u << ((w.len - 1u) & 7u) : 0u;
-                w.rw = add ? (w.rw >> kEdgeIdxBits) | ((uint64_t)(wi + 1u) << kRecTop) : w.rw;
-                w.nedge += add ? 1u : 0u;
-                const bool more = hit && jb_cell_hc(ch) && !w.ovf;
-                const bool go = more && (w.en & kEntCont);
-                const bool dfr = more && !(w.en & kEntCont) && (w.en & kEntEdge);  // past the lookahead: k_zh walks it
-                ++w.j;
-                w.en = en2[q];
-                w.id = tt[q];
-                w.base = jb_cell_base(ch);
-                if (!go) {  // the record goes to the start entry's LDS cell (read when the walk began)
-                    s_c[w.js] = (w.ovf || dfr) ? 0ull : ((uint64_t)w.m | w.rw);
-                    w.act = false;
-                }
+        if (lbit != 0u) {
+            const uint32_t tt = base + ent_code(en);
+            // (a cell index is under 2^23: the probe is the scalar table address plus a 32-bit lane offset)
+            const uint64_t ch = *reinterpret_cast<const uint64_t*>(cells8 + (tt << 3));
+            const uint32_t en2 = *reinterpret_cast<const uint32_t*>(ent8 + ja + 8u);  // entry j + 2 (used only when
+                                                                                      // the walk goes on: then it exists)
+            const uint32_t clo = (uint32_t)ch, chi = (uint32_t)(ch >> 32);
+            const bool hit = (clo & 0x3FFFFFu) == id1;                        // dat_hit
+            const bool pos = hit && ((chi >> 12) & 3u) == JB_FC_POS;          // jb_cell_fc
+            const uint32_t wi1 = (chi >> 15) + 1u;                            // jb_cell_widx + 1
+            const bool bad = pos && (lbit > (1u << (kEdgeMaxL - 1u)) || (rlo & 0x3FFF00u) != 0u || wi1 > kRecIdxMax + 1u);
+            const bool add = pos && !bad;
+            m |= add ? lbit : 0u;
+            const uint32_t nlo = __builtin_amdgcn_alignbit(rhi, rlo, kEdgeIdxBits);
+            const uint32_t nhi = (rhi >> kEdgeIdxBits) | (wi1 << (kRecTop - 32u));
+            rlo = add ? nlo : rlo;
+            rhi = add ? nhi : rhi;
+            lbit = __builtin_elementwise_add_sat(lbit, lbit);  // (saturating: a walk of any length keeps it non-zero)
+            const bool more = hit && (chi & 0x4000u) != 0u && !bad;           // jb_cell_hc
+            const bool go = more && (en & kEntCont);
+            const bool dfr = more && !(en & kEntCont) && (en & kEntEdge);  // past the lookahead: k_zh walks it
+            id1 = tt + 1u;
+            base = __builtin_amdgcn_alignbit(chi, clo, 22) & 0x3FFFFFu;      // jb_cell_base
+            ja += 4u;
+            en = en2;
+            if (!go) {  // the record goes to the start entry's LDS cell (read when the walk began)
+                *reinterpret_cast<uint64_t*>(sc8 + js8) = (bad || dfr) ? 0ull : ((uint64_t)rhi << 32) | (rlo | m);
+                lbit = 0u;
             }
         }
         trips++;
-        bool any = false;
-#pragma unroll
-        for (int q = 0; q < JB_MW_WALKS; q++) any |= wk[q].act;
-        if (!__any(any) && head >= hi) break;
+        if (!__any(lbit != 0u) && head >= hi) break;
     }
     if (stamps) c3 = __builtin_amdgcn_s_memtime();
     __syncthreads();
     // records out in entry (= text) order: consecutive lanes, mostly consecutive slots
     // (non-temporal: k_zh reads them on another XCD; kept out of this L2, where the trie's hot lines live)
     {
-        const uint32_t e0 = (nent * part) >> split, e1 = (nent * (part + 1u)) >> split;
-        for (uint32_t i = e0 + threadIdx.x; i < e1; i += 256u)
-            __builtin_nontemporal_store(s_c[i], erec + (t0 + ent_pos(s_e[i])) / 3u);
+        // (slot (t0 + pos) / 3 as the tile's own t0 / 3, once per workgroup in scalar registers,
+        // plus a 32-bit quotient per entry, instead of a 64-bit division per entry)
+        uint64_t* const erec0 = erec + t0 / 3u;
+        const uint32_t r0 = (uint32_t)(t0 % 3u);
+        for (uint32_t i = pe0 + threadIdx.x; i < pe1; i += 256u)
+            __builtin_nontemporal_store(s_c[i], erec0 + (r0 + ent_pos(s_e[i])) / 3u);
     }
     if (stamps && part == 0u && (threadIdx.x & 63u) == 0) {  // per-wave phase clocks, summed on the host
         uint64_t* o = dbg + ((uint64_t)tile * 4u + (threadIdx.x >> 6)) * 8u;
