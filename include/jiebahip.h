@@ -1164,6 +1164,110 @@ int jb_postings_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off,
                       uint32_t doc_base, uint64_t pcap, uint64_t *post_off, uint32_t nids, uint32_t *post_doc,
                       uint32_t *post_tf, uint64_t *nposts, uint32_t *doc_len);
 
+/* ---- BM25 search (the query half of the Whoosh use case: Whoosh's default scorer under jieba's
+ * ChineseAnalyzer is BM25F; the reference has only Cut) -------------------------------------------------
+ * Rank the documents of an index (the postings above, with doc_len) for queries, on the device: cut the query,
+ * look up its ids, score and keep the best topk.  It replaces copying the postings to the host and scoring there.
+ *
+ * The rule, stated once; the host forms and the device forms agree to the bit (the build keeps every f64
+ * operation separately rounded).  Parameters: k1 and b are f64, JB_EINVAL unless 0 <= k1 <= 64 and 0 <= b <= 1
+ * (NaN is rejected); avgdl is f64, finite and > 0.
+ *  - jb_bm25_avgdl (host only): the u64 sum of doc_len divided by ndocs, as f64; JB_EINVAL for ndocs == 0 or a
+ *    zero sum.
+ *  - jb_bm25_norms(_device): norm[d] = (float)(k1 * ((1.0 - b) + b * ((double)doc_len[d] / avgdl))), each
+ *    operation one f64 rounding in that order, then one narrowing; one lane per document.
+ *  - jb_bm25_idf(_device): df = min(post_off[t + 1] - post_off[t], ndocs_total), 0 when the offsets decrease;
+ *    weight[t] = 0.0f for df == 0, otherwise (float)jb_go_log(1.0 + ((double)(ndocs_total - df) + 0.5) /
+ *    ((double)df + 0.5)), Lucene's form, > 0 for every ndocs_total below 2^51 (past that the f64 sum of a list of
+ *    every document rounds to 1 and the weight to 0).  JB_ELIMIT for ndocs_total >= 2^53.  One lane per id.
+ *  - jb_bm25_search(_device).  Inputs: the index post_doc / post_tf / post_off (u64[nids + 1]) and npost, the
+ *    number of valid entries of the two arrays; norm (f32[ndocs]); weight (f32[nweights]); k1; the queries as a
+ *    CSR, q_id (u32, q_cap valid entries) and q_off (u64[nq + 1]); topk.
+ *     - Query q's entries are [q_off[q], q_off[q + 1]) clamped to q_cap, and only the first JB_BM25_MAXQ of them
+ *       are read.  An entry with id t takes part iff t < nids, t < nweights and 0 < weight[t] <= JB_BM25_WMAX
+ *       (which excludes NaN and +Inf).  A repeated id counts once per occurrence.  JB_ID_UNK fails the first test
+ *       in any real vocabulary; no table is indexed by an id that is not checked.
+ *     - The list of t is [post_off[t], post_off[t + 1]) clamped to [0, npost], empty if the offsets decrease.  A
+ *       posting takes part iff post_doc < ndocs, post_tf > 0 and norm[post_doc] >= 0 (the norms of jb_bm25_norms
+ *       are; a caller's negative or NaN norm drops the document).  Lists are trusted to ascend by document, as
+ *       jb_postings* writes them; with a caller's own unsorted lists which postings count is unspecified, but
+ *       nothing is read outside the inputs and nothing is written outside the outputs.
+ *     - A posting (d, tf) under an entry t contributes, all in f64 with one rounding per operation:
+ *       num = (double)tf * (k1 + 1.0); den = (double)tf + (double)norm[d]; x = (double)weight[t] * (num / den);
+ *       c = (uint64_t)(x * 16777216.0), truncated.  den >= 1, so c < 2^51 and 1024 entries cannot overflow.
+ *     - score[q][d] is the u64 sum of the contributions, in units of 2^-24: an integer, so host and device agree
+ *       in any order of adds and from run to run.  A document is a candidate iff its score is > 0.
+ *     - Row q of res_doc (u32) and res_score (u64), nq x topk each, holds the res_n[q] = min(topk, candidates)
+ *       best candidates, score descending, ties by document ascending; the remaining slots are JB_ID_UNK and 0.
+ *       Every slot of every row is written, and nothing else.  1 <= topk <= JB_KW_MAXK: JB_EINVAL for 0,
+ *       JB_ELIMIT above.
+ *     - JB_EINVAL: a null pointer (arrays of capacity 0 may be NULL), an output that is an input, another output
+ *       or the work buffer, a work buffer that is too small or not 8-byte aligned; nothing is queued.  nq == 0,
+ *       ndocs == 0 and nids == 0 are valid.
+ *
+ * jb_bm25_search_device.  The contract is jb_postings_device's: it queues on `stream` and returns; it does not
+ * synchronise, allocate or read on the host, it needs no vocabulary, and it holds the ctx's shared lock only
+ * while queuing.  The number of launches depends on the arguments alone.  d_work holds nwork >=
+ * jb_bm25_work_bytes(nq, ndocs, topk) bytes: per pair of query and document tile (JB_BM25_TILE documents) a
+ * count and topk partial records, and the dense rows of form 0 (8 bytes per pair of query and document).  Two
+ * forms, chosen by JB_BM25_FORM at jb_open, write identical bytes:
+ *   form 1  k_bm25_tile, one workgroup per pair of query and tile: the tile's u64 scores in 64 KiB of LDS, the
+ *           part of each entry's list inside the tile by two binary searches, LDS atomics, then the tile's best
+ *           topk; k_bm25_merge, one workgroup per query.  No global atomics; no lane waits for another workgroup.
+ *   form 0  a memset of the dense rows, k_bm25_scatter (one lane per posting, a global atomicAdd), k_bm25_select
+ *           (the same selection per tile), k_bm25_merge.
+ * Measured on the 1 GiB corpus's index (tools/bm25_bench.py, profiles/bm25_bench.json; 73,443 documents, 77.3M
+ * postings; 1,024 seeded queries of 1 to 8 ids drawn by corpus frequency, 4,593 entries over 141.0M postings,
+ * topk 10): form 1 takes 0.96 ms (k_bm25_tile 0.90 ms, k_bm25_merge 0.03 ms) and ships as the default; form 0
+ * takes 1.75 ms (k_bm25_scatter 1.23 ms, k_bm25_select 0.42 ms, k_bm25_merge 0.03 ms and the memset), beside
+ * 6.00 ms for the cut step and 3.15 ms for jb_postings_device in the same run.  The two forms' rows were
+ * identical byte for byte and those of jb_bm25_search on every query (280 ms on the host).  The path it
+ * replaces, the postings copied to the host (71 ms) and scored by numpy there, takes 4.4 ms per query (timed on
+ * 32 queries: about 4.5 s for all).  From host text jb_search_batch takes 1.66 ms for the 1,024 queries;
+ * jb_index_set takes 11 ms.
+ *
+ * jb_index_set uploads an index (build_index's arrays) to ctx's first device, computes avgdl on the host and
+ * the norms and weights on the device with the calls above, and keeps them until the next jb_index_set,
+ * jb_index_clear or jb_close, under the ctx's exclusive lock (the jb_vocab_set precedent).  JB_ELIMIT when ndocs
+ * or npost is >= 2^32; JB_EINVAL for an index without a token (jb_bm25_avgdl's).  jb_index_info reports ndocs,
+ * nids, npost and avgdl (JB_EINVAL with no index).
+ * jb_search_batch: host query text in (q_off: u64[nq + 1] byte offsets, as doc_off), records out.  It runs plain
+ * Cut -> ids -> jb_bm25_search_device on ctx's first device through the buffers jb_keywords_batch keeps in the
+ * ctx (one more, that only grows; concurrent calls take turns); a query's entries are its tokens' ids, unknown
+ * tokens included (they do not take part).  Only the nq x topk records and res_n come back.  It needs an
+ * attached vocabulary and an attached index whose nids equals the vocabulary's size (JB_EINVAL otherwise); the
+ * cut's errors pass through. */
+#define JB_BM25_TILE 8192      /* documents per tile (one workgroup per query and tile) */
+#define JB_BM25_MAXQ 1024      /* entries of a query that are read */
+#define JB_BM25_WMAX 1048576.0f /* 2^20: the largest weight that takes part */
+/* Host only, no ctx: non-decreasing in every argument, never 0 (SIZE_MAX when the size overflows). */
+size_t jb_bm25_work_bytes(uint32_t nq, uint32_t ndocs, uint32_t topk);
+/* host only, no ctx, no GPU: the rule, and the reference the device kernels are pinned to */
+int jb_bm25_avgdl(const uint32_t *doc_len, uint32_t ndocs, double *avgdl);
+int jb_bm25_norms(const uint32_t *doc_len, uint32_t ndocs, double k1, double b, double avgdl, float *norm);
+int jb_bm25_idf(const uint64_t *post_off, uint32_t nids, uint64_t ndocs_total, float *weight);
+int jb_bm25_search(const uint32_t *post_doc, const uint32_t *post_tf, const uint64_t *post_off, uint64_t npost,
+                   uint32_t nids, const float *norm, uint32_t ndocs, const float *weight, uint32_t nweights, double k1,
+                   const uint32_t *q_id, uint64_t q_cap, const uint64_t *q_off, uint32_t nq, uint32_t topk,
+                   uint32_t *res_doc, uint64_t *res_score, uint32_t *res_n);
+int jb_bm25_norms_device(jb_ctx *ctx, const uint32_t *d_doc_len, uint32_t ndocs, double k1, double b, double avgdl,
+                         void *stream, float *d_norm);
+int jb_bm25_idf_device(jb_ctx *ctx, const uint64_t *d_post_off, uint32_t nids, uint64_t ndocs_total, void *stream,
+                       float *d_weight);
+int jb_bm25_search_device(jb_ctx *ctx, const uint32_t *d_post_doc, const uint32_t *d_post_tf, const uint64_t *d_post_off,
+                          uint64_t npost, uint32_t nids, const float *d_norm, uint32_t ndocs, const float *d_weight,
+                          uint32_t nweights, double k1, const uint32_t *d_q_id, uint64_t q_cap, const uint64_t *d_q_off,
+                          uint32_t nq, uint32_t topk, void *stream, uint32_t *d_res_doc, uint64_t *d_res_score,
+                          uint32_t *d_res_n, void *d_work, size_t nwork);
+/* host arrays in; the index stays on the device */
+int jb_index_set(jb_ctx *ctx, const uint64_t *post_off, const uint32_t *post_doc, const uint32_t *post_tf,
+                 uint64_t npost, uint32_t nids, const uint32_t *doc_len, uint64_t ndocs, double k1, double b);
+int jb_index_clear(jb_ctx *ctx);
+int jb_index_info(jb_ctx *ctx, uint64_t *ndocs, uint64_t *nids, uint64_t *npost, double *avgdl);
+/* res_doc / res_score: nq * topk host entries; res_n: nq. */
+int jb_search_batch(jb_ctx *ctx, const uint8_t *qtext, const uint64_t *q_off, uint32_t nq, int hmm, uint32_t topk,
+                    uint32_t *res_doc, uint64_t *res_score, uint32_t *res_n);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

@@ -19,6 +19,7 @@
 #include "jb_filter.h"
 #include "jb_minhash.h"
 #include "jb_postings.h"
+#include "jb_bm25.h"
 #include "jb_wc.h"
 
 // ---------------------------------------------------------------------------
@@ -244,6 +245,11 @@ extern "C" void jb_close(jb_ctx* ctx) {
         (void)hipDeviceSynchronize();
         dfree(ctx->d_sslots);
         dfree(ctx->d_spool);
+    }
+    if (ctx->index.base && !ctx->devs.empty()) {  // (a search may still be queued on a caller's stream)
+        (void)hipSetDevice(ctx->devs[0]->ordinal);
+        (void)hipDeviceSynchronize();
+        dfree(ctx->index.base);
     }
     if (std::any_of(std::begin(ctx->kw_buf), std::end(ctx->kw_buf), [](void* p) { return p != nullptr; }) &&
         !ctx->devs.empty()) {
@@ -2335,4 +2341,225 @@ extern "C" int jb_postings_batch(jb_ctx* ctx, const uint8_t* text, const uint64_
         *nposts = 0;
     }
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// BM25 search (jb_bm25.hip; the host rules, the argument checks, the work buffer's layout and the size helper
+// are jb_bm25.cpp)
+// ---------------------------------------------------------------------------
+static_assert(JB_BM25_TILE == kBm25Tile && JB_BM25_MAXQ == kBm25MaxQ, "the header's constants are the kernels'");
+
+extern "C" int jb_bm25_norms_device(jb_ctx* ctx, const uint32_t* d_doc_len, uint32_t ndocs, double k1, double b,
+                                    double avgdl, void* stream, float* d_norm) {
+    const char* who = "jb_bm25_norms_device";
+    if (const int rc = bm25_params(who, k1, b)) return rc;
+    if (const int rc = bm25_avgdl_ok(who, avgdl)) return rc;
+    if (!ctx || (ndocs && (!d_doc_len || !d_norm))) return fail(JB_EINVAL, "%s: null argument", who);
+    if (ndocs && (const void*)d_doc_len == (const void*)d_norm) return fail(JB_EINVAL, "%s: the output is the input", who);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_bm25_norms(d_doc_len, ndocs, k1, b, avgdl, d_norm, (hipStream_t)stream, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_bm25_norms(d_doc_len, ndocs, k1, b, avgdl, d_norm, (hipStream_t)stream, nullptr));
+    return JB_OK;
+}
+
+extern "C" int jb_bm25_idf_device(jb_ctx* ctx, const uint64_t* d_post_off, uint32_t nids, uint64_t ndocs_total,
+                                  void* stream, float* d_weight) {
+    const char* who = "jb_bm25_idf_device";
+    if (ndocs_total >= (1ull << 53))
+        return fail(JB_ELIMIT, "%s: %llu documents (limit 2^53)", who, (unsigned long long)ndocs_total);
+    if (!ctx || !d_post_off || (nids && !d_weight)) return fail(JB_EINVAL, "%s: null argument", who);
+    if ((const void*)d_post_off == (const void*)d_weight) return fail(JB_EINVAL, "%s: the output is the input", who);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (d->profile) {
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_bm25_idf(d_post_off, nids, ndocs_total, d_weight, (hipStream_t)stream, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_bm25_idf(d_post_off, nids, ndocs_total, d_weight, (hipStream_t)stream, nullptr));
+    return JB_OK;
+}
+
+namespace {
+// The search, queued: the caller holds the ctx's lock (shared or exclusive) and has checked the arguments.
+int bm25_queue(jb_ctx* ctx, const uint32_t* d_post_doc, const uint32_t* d_post_tf, const uint64_t* d_post_off,
+               uint64_t npost, uint32_t nids, const float* d_norm, uint32_t ndocs, const float* d_weight,
+               uint32_t nweights, double k1, const uint32_t* d_q_id, uint64_t q_cap, const uint64_t* d_q_off, uint32_t nq,
+               uint32_t topk, hipStream_t s, uint32_t* d_res_doc, uint64_t* d_res_score, uint32_t* d_res_n, void* d_work) {
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const uint32_t form = d->lc.bm25_form;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_bm25_search(d_post_doc, d_post_tf, d_post_off, npost, nids, d_norm, ndocs, d_weight, nweights, k1,
+                               d_q_id, q_cap, d_q_off, nq, topk, form, d_res_doc, d_res_score, d_res_n, d_work, s,
+                               &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_bm25_search(d_post_doc, d_post_tf, d_post_off, npost, nids, d_norm, ndocs, d_weight, nweights, k1, d_q_id,
+                           q_cap, d_q_off, nq, topk, form, d_res_doc, d_res_score, d_res_n, d_work, s, nullptr));
+    return JB_OK;
+}
+}  // namespace
+
+extern "C" int jb_bm25_search_device(jb_ctx* ctx, const uint32_t* d_post_doc, const uint32_t* d_post_tf,
+                                     const uint64_t* d_post_off, uint64_t npost, uint32_t nids, const float* d_norm,
+                                     uint32_t ndocs, const float* d_weight, uint32_t nweights, double k1,
+                                     const uint32_t* d_q_id, uint64_t q_cap, const uint64_t* d_q_off, uint32_t nq,
+                                     uint32_t topk, void* stream, uint32_t* d_res_doc, uint64_t* d_res_score,
+                                     uint32_t* d_res_n, void* d_work, size_t nwork) {
+    const char* who = "jb_bm25_search_device";
+    // (the limits come first: they need no ctx)
+    if (const int rc = bm25_topk(who, topk)) return rc;
+    if (const int rc = bm25_params(who, k1, 0.0)) return rc;
+    if (!ctx || !d_work) return fail(JB_EINVAL, "%s: null argument", who);
+    if (const int rc = bm25_search_args(who, d_post_doc, d_post_tf, d_post_off, npost, d_norm, ndocs, d_weight, nweights,
+                                        d_q_id, q_cap, d_q_off, nq, d_res_doc, d_res_score, d_res_n, d_work))
+        return rc;
+    if (((uintptr_t)d_work & 7u) != 0) return fail(JB_EINVAL, "%s: d_work must be 8-byte aligned", who);
+    const size_t need = jb_bm25_work_bytes(nq, ndocs, topk);
+    if (nwork < need)
+        return fail(JB_EINVAL, "%s: a work buffer of %llu bytes, jb_bm25_work_bytes asks for %llu", who,
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    return bm25_queue(ctx, d_post_doc, d_post_tf, d_post_off, npost, nids, d_norm, ndocs, d_weight, nweights, k1, d_q_id,
+                      q_cap, d_q_off, nq, topk, (hipStream_t)stream, d_res_doc, d_res_score, d_res_n, d_work);
+}
+
+namespace {
+// The old index may be in use by kernels queued earlier, on any stream of the device (under the exclusive lock).
+void index_drop(jb_ctx* ctx) {
+    if (!ctx->index.base) return;
+    (void)hipDeviceSynchronize();
+    dfree(ctx->index.base);
+    ctx->index = jb_ctx::Index{};
+}
+}  // namespace
+
+extern "C" int jb_index_set(jb_ctx* ctx, const uint64_t* post_off, const uint32_t* post_doc, const uint32_t* post_tf,
+                            uint64_t npost, uint32_t nids, const uint32_t* doc_len, uint64_t ndocs, double k1, double b) {
+    const char* who = "jb_index_set";
+    if (ndocs >= (1ull << 32)) return fail(JB_ELIMIT, "%s: %llu documents (limit 2^32)", who, (unsigned long long)ndocs);
+    if (npost >= (1ull << 32)) return fail(JB_ELIMIT, "%s: %llu postings (limit 2^32)", who, (unsigned long long)npost);
+    if (const int rc = bm25_params(who, k1, b)) return rc;
+    if (!ctx || !post_off || (npost && (!post_doc || !post_tf)) || (ndocs && !doc_len))
+        return fail(JB_EINVAL, "%s: null argument", who);
+    double avgdl = 0;
+    if (jb_bm25_avgdl(doc_len, (uint32_t)ndocs, &avgdl)) return fail(JB_EINVAL, "%s: an index without a token", who);
+    const uint32_t nd = (uint32_t)ndocs;
+    const size_t noff = ((size_t)nids + 1) * 8, np4 = std::max<size_t>(npost, 1) * 4, nd4 = (size_t)nd * 4,
+                 nw4 = std::max<size_t>(nids, 1) * 4;
+    std::unique_lock<std::shared_mutex> wl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    // built aside: on any error the old index stays attached
+    void* base = nullptr;
+    {
+        const hipError_t e = hipMalloc(&base, r256(noff) + 2 * r256(np4) + 2 * r256(nd4) + r256(nw4));
+        if (e != hipSuccess) return fail(JB_EDEVICE, "%s: allocating the index: %s", who, hipGetErrorString(e));
+    }
+    Arena a;
+    a.p = (uint8_t*)base;
+    jb_ctx::Index ix;
+    ix.base = base;
+    uint64_t* doff = (uint64_t*)a.take(noff);
+    uint32_t* ddoc = (uint32_t*)a.take(np4);
+    uint32_t* dtf = (uint32_t*)a.take(np4);
+    uint32_t* dlen = (uint32_t*)a.take(nd4);
+    float* dnorm = (float*)a.take(nd4);
+    float* dwt = (float*)a.take(nw4);
+    hipError_t e = hipMemcpy(doff, post_off, noff, hipMemcpyHostToDevice);
+    if (e == hipSuccess && npost) e = hipMemcpy(ddoc, post_doc, (size_t)npost * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && npost) e = hipMemcpy(dtf, post_tf, (size_t)npost * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dlen, doc_len, nd4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = run_bm25_norms(dlen, nd, k1, b, avgdl, dnorm, nullptr, nullptr);
+    if (e == hipSuccess) e = run_bm25_idf(doff, nids, ndocs, dwt, nullptr, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        dfree(base);
+        return fail(JB_EDEVICE, "%s: uploading the index: %s", who, hipGetErrorString(e));
+    }
+    ix.post_off = doff;
+    ix.post_doc = ddoc;
+    ix.post_tf = dtf;
+    ix.norm = dnorm;
+    ix.weight = dwt;
+    ix.npost = npost;
+    ix.nids = nids;
+    ix.ndocs = nd;
+    ix.k1 = k1;
+    ix.b = b;
+    ix.avgdl = avgdl;
+    index_drop(ctx);
+    ctx->index = ix;
+    return JB_OK;
+}
+
+extern "C" int jb_index_clear(jb_ctx* ctx) {
+    if (!ctx) return fail(JB_EINVAL, "jb_index_clear: null ctx");
+    std::unique_lock<std::shared_mutex> wl(ctx->lock);
+    HIPCHK(hipSetDevice(ctx->devs[0]->ordinal));
+    index_drop(ctx);
+    return JB_OK;
+}
+
+extern "C" int jb_index_info(jb_ctx* ctx, uint64_t* ndocs, uint64_t* nids, uint64_t* npost, double* avgdl) {
+    if (!ctx) return fail(JB_EINVAL, "jb_index_info: null ctx");
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    if (!ctx->index.base) return fail(JB_EINVAL, "jb_index_info: no index attached (jb_index_set)");
+    if (ndocs) *ndocs = ctx->index.ndocs;
+    if (nids) *nids = ctx->index.nids;
+    if (npost) *npost = ctx->index.npost;
+    if (avgdl) *avgdl = ctx->index.avgdl;
+    return JB_OK;
+}
+
+// Host query text in, the best documents out: batch_chain (its token ids in token order and its token offsets
+// are the queries' CSR), then the search with its work buffer and its records in the ctx's buffer [11].
+extern "C" int jb_search_batch(jb_ctx* ctx, const uint8_t* qtext, const uint64_t* q_off, uint32_t nq, int hmm,
+                               uint32_t topk, uint32_t* res_doc, uint64_t* res_score, uint32_t* res_n) {
+    const char* who = "jb_search_batch";
+    if (const int rc = bm25_topk(who, topk)) return rc;
+    if (!ctx || !q_off || (nq && (!res_doc || !res_score || !res_n))) return fail(JB_EINVAL, "%s: null argument", who);
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        if (!ctx->vocab) return fail(JB_EINVAL, "%s: no vocabulary attached (jb_vocab_set)", who);
+        if (!ctx->index.base) return fail(JB_EINVAL, "%s: no index attached (jb_index_set)", who);
+        if (ctx->index.nids != ctx->vocab->nkeys)
+            return fail(JB_EINVAL, "%s: the index has %u ids, the vocabulary %u keys", who, ctx->index.nids,
+                        (uint32_t)ctx->vocab->nkeys);
+    }
+    const size_t nrec = (size_t)nq * topk;
+    return batch_chain(ctx, who, qtext, q_off, nq, hmm, 0, [&](const BatchCsr& c, Arena*) -> int {
+        // (the lock keeps the index while the search is queued; a jb_index_set that follows waits for the device)
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        const jb_ctx::Index& ix = ctx->index;
+        if (!ix.base || !ctx->vocab || ix.nids != ctx->vocab->nkeys)
+            return fail(JB_EINVAL, "%s: the index was replaced during the call", who);
+        const Bm25Work w = bm25_layout(nq, ix.ndocs, topk);
+        const size_t nwork = ctx->devs[0]->lc.bm25_form ? w.bytes1 : w.bytes;
+        if (nwork == SIZE_MAX) return fail(JB_ELIMIT, "%s: %u queries over %u documents", who, nq, ix.ndocs);
+        Arena b;
+        if (const int r = kw_arena(ctx, 11, r256(nwork) + r256(nrec * 8) + r256(nrec * 4) + r256((size_t)nq * 4), &b))
+            return r;
+        void* work = b.take(nwork);
+        uint64_t* dscore = (uint64_t*)b.take(nrec * 8);
+        uint32_t* ddoc = (uint32_t*)b.take(nrec * 4);
+        uint32_t* dn = (uint32_t*)b.take((size_t)nq * 4);
+        if (const int r = bm25_queue(ctx, ix.post_doc, ix.post_tf, ix.post_off, ix.npost, ix.nids, ix.norm, ix.ndocs,
+                                     ix.weight, ix.nids, ix.k1, c.ids, c.tcap, c.doc_tok, nq, topk, c.st, ddoc, dscore, dn,
+                                     work))
+            return r;
+        HIPCHK(hipMemcpyAsync(res_doc, ddoc, nrec * 4, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipMemcpyAsync(res_score, dscore, nrec * 8, hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipMemcpyAsync(res_n, dn, (size_t)nq * 4, hipMemcpyDeviceToHost, c.st));
+        return JB_OK;
+    });
 }

@@ -248,6 +248,7 @@ static const uint64_t kMaxPiece = 1ull << 30;  // (a piece of several documents;
 //   JB_WC_HASHBITS the word-count fingerprint's width, 1 .. 64 (default 64; fewer to test collisions)
 //   JB_MH_FORM   jb_minhash_device's signature kernel: 0 the plain form, 1 the staged form (default)
 //   JB_POSTINGS_FORM jb_postings_device's scatter kernel: 0 from the lanes (default), 1 through LDS in runs
+//   JB_BM25_FORM jb_bm25_search_device: 0 a dense row per query and global atomics, 1 a tile's scores in LDS (default)
 static int init_launch_cfg(Device* d) {
     LaunchCfg& lc = d->lc;
     lc.zh_waves = d->ncu * std::max(zh_waves_per_cu(true, false), zh_waves_per_cu(false, false));
@@ -327,6 +328,9 @@ static int init_launch_cfg(Device* d) {
     const int pf = env_int("JB_POSTINGS_FORM", 0);
     if (pf < 0 || pf > 1) return fail(JB_EINVAL, "JB_POSTINGS_FORM=%d: want 0 or 1", pf);
     lc.post_form = (uint32_t)pf;
+    const int bf = env_int("JB_BM25_FORM", 1);
+    if (bf < 0 || bf > 1) return fail(JB_EINVAL, "JB_BM25_FORM=%d: want 0 or 1", bf);
+    lc.bm25_form = (uint32_t)bf;
     return JB_OK;
 }
 

@@ -346,13 +346,25 @@ struct jb_ctx {
     // [6] jb_cut_batch_charspans' work buffer and doc_units, [7] jb_wc_batch's work buffer,
     // [8] jb_minhash_batch's work buffer, signatures and shingle counts,
     // [9] the batch filter's work buffer and filtered span list (jb_cut_batch_filter, jb_batch_filter_set),
-    // [10] jb_postings_batch's work buffer and postings
+    // [10] jb_postings_batch's work buffer and postings, [11] jb_search_batch's work buffer and records
     std::mutex kw_mu;
-    void* kw_buf[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t kw_cap[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void* kw_buf[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t kw_cap[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // the rule jb_cut_batch_join, jb_wc_batch and jb_minhash_batch filter by (jb_batch_filter_set; under kw_mu)
     bool bfilter_on = false;
     jb_filter_rule bfilter{0, 0, 0, 0};
+    // the caller's index (jb_index_set) on the first device, one allocation: search calls read it under the
+    // shared lock, jb_index_set and jb_index_clear replace it under the exclusive one
+    struct Index {
+        void* base = nullptr;
+        const uint64_t* post_off = nullptr;
+        const uint32_t *post_doc = nullptr, *post_tf = nullptr;
+        const float *norm = nullptr, *weight = nullptr;
+        uint64_t npost = 0;
+        uint32_t nids = 0, ndocs = 0;
+        double k1 = 0, b = 0, avgdl = 0;
+    } index;
 };
 
 #pragma GCC visibility pop

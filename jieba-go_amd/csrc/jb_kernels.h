@@ -133,6 +133,7 @@ enum KernelId {
     K_MH_INIT, K_MH_HASH, K_MH_SIG, K_MH_BANDS,
     K_FILT_MARK, K_FILT_SCAN, K_FILT_WRITE,
     K_POST_HIST, K_POST_SCAN, K_POST_SCATTER, K_POST_OFF,
+    K_BM25_NORMS, K_BM25_IDF, K_BM25_TILE, K_BM25_SCATTER, K_BM25_SELECT, K_BM25_MERGE,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -181,6 +182,9 @@ struct LaunchCfg {
     uint32_t post_form;      // jb_postings_device's scatter: 0 from the lanes (default: 3.26 ms against 3.37 ms on the
                              // 1 GiB corpus, profiles/postings_bench.json), 1 through LDS in runs (JB_POSTINGS_FORM;
                              // results do not depend on it)
+    uint32_t bm25_form;      // jb_bm25_search_device: 0 a dense row per query and global atomics, 1 a document tile's
+                             // scores in LDS (default: 0.96 ms against 1.75 ms on the 1 GiB corpus's index,
+                             // profiles/bm25_bench.json) (JB_BM25_FORM; results do not depend on it)
 };
 
 // k_zh's group split: g1 groups of grp bytes, then groups of *sgrp bytes to the end.
@@ -401,6 +405,24 @@ hipError_t run_postings(const uint32_t* d_term_id, const uint32_t* d_term_cnt, c
                         const uint64_t* d_nterms, uint64_t cap, uint32_t ndocs, uint32_t nids, uint32_t doc_base,
                         uint32_t form, uint32_t* d_post_doc, uint32_t* d_post_tf, uint64_t pcap, uint64_t* d_post_off,
                         uint64_t* d_nposts, void* d_work, hipStream_t stream, KernelTimer* timer);
+
+// BM25 (jb_bm25_*_device; jb_bm25.hip, the rule's shared code is jb_bm25.h's).  A document tile is kBm25Tile
+// consecutive documents, one workgroup per pair of query and tile.
+constexpr uint32_t kBm25Tile = 8192;  // JB_BM25_TILE
+constexpr uint32_t kBm25MaxQ = 1024;  // JB_BM25_MAXQ
+// One launch each (none for no document / no id): norm[d] for d < ndocs; weight[t] for t < nids.
+hipError_t run_bm25_norms(const uint32_t* d_doc_len, uint32_t ndocs, double k1, double b, double avgdl, float* d_norm,
+                          hipStream_t stream, KernelTimer* timer);
+hipError_t run_bm25_idf(const uint64_t* d_post_off, uint32_t nids, uint64_t ndocs_total, float* d_weight,
+                        hipStream_t stream, KernelTimer* timer);
+// Enqueue the search on `stream`: per slice of up to 32,768 queries (fewer past 128 tiles) k_bm25_tile (form 1) or a memset, k_bm25_scatter
+// and k_bm25_select (form 0), none when ndocs is 0, then k_bm25_merge; nothing at all when nq is 0.  d_work holds
+// jb_bm25_work_bytes(nq, ndocs, topk) bytes (form 1 uses the first bm25_layout().bytes1 of them), 8-byte aligned.
+hipError_t run_bm25_search(const uint32_t* d_post_doc, const uint32_t* d_post_tf, const uint64_t* d_post_off,
+                           uint64_t npost, uint32_t nids, const float* d_norm, uint32_t ndocs, const float* d_weight,
+                           uint32_t nweights, double k1, const uint32_t* d_q_id, uint64_t q_cap, const uint64_t* d_q_off,
+                           uint32_t nq, uint32_t topk, uint32_t form, uint32_t* d_res_doc, uint64_t* d_res_score,
+                           uint32_t* d_res_n, void* d_work, hipStream_t stream, KernelTimer* timer);
 
 // One-workgroup path for small batches (k_small): the text and document offsets
 // are read from `text`/`doc_off` (device or mapped pinned host memory; text

@@ -43,7 +43,9 @@ const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_
                                          "k_cs_class", "k_cs_scan", "k_cs_lookup", "k_wc_claim", "k_wc_store",
                                          "k_wc_count", "k_mh_init", "k_mh_hash", "k_mh_sig", "k_mh_bands",
                                          "k_filt_mark", "k_filt_scan", "k_filt_write",
-                                         "k_post_hist", "k_post_scan", "k_post_scatter", "k_post_off"};
+                                         "k_post_hist", "k_post_scan", "k_post_scatter", "k_post_off",
+                                         "k_bm25_norms", "k_bm25_idf", "k_bm25_tile", "k_bm25_scatter", "k_bm25_select",
+                                         "k_bm25_merge"};
 
 hipError_t run_pipeline(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes,
                         const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, const LaunchCfg& lc,

@@ -980,6 +980,94 @@ func (t *Tokenizer) Postings(docs []string, useHmm bool, docBase uint32) Index {
 	return ix
 }
 
+// Hit is one result of Search: a document and its BM25 score in units of 2^-24.
+type Hit struct {
+	Doc   uint32
+	Score uint64
+}
+
+// Value is the score as a plain number.
+func (h Hit) Value() float64 { return float64(h.Score) / 16777216.0 }
+
+// SetIndex attaches an index to search (jb_index_set): Postings' result for a corpus in one batch, or the
+// batches' lists concatenated per id.  The postings, the documents' norms and the ids' BM25 weights stay on
+// the device until the next SetIndex, ClearIndex or Close.  Whoosh's defaults are k1 = 1.2, b = 0.75.
+func (t *Tokenizer) SetIndex(ix Index, k1, b float64) error {
+	t.mu.Lock()
+	defer t.mu.Unlock()
+	if len(ix.Off) == 0 || len(ix.Doc) != len(ix.Tf) {
+		return errors.New("jiebahip: SetIndex: an index without offsets, or Doc and Tf of different lengths")
+	}
+	var pd, pt, pl *C.uint32_t
+	if len(ix.Doc) > 0 {
+		pd = (*C.uint32_t)(unsafe.Pointer(&ix.Doc[0]))
+		pt = (*C.uint32_t)(unsafe.Pointer(&ix.Tf[0]))
+	}
+	if len(ix.DocLen) > 0 {
+		pl = (*C.uint32_t)(unsafe.Pointer(&ix.DocLen[0]))
+	}
+	rc := C.jb_index_set(t.ctx, (*C.uint64_t)(unsafe.Pointer(&ix.Off[0])), pd, pt, C.uint64_t(len(ix.Doc)),
+		C.uint32_t(len(ix.Off)-1), pl, C.uint64_t(len(ix.DocLen)), C.double(k1), C.double(b))
+	if rc != C.JB_OK {
+		return errors.New("jiebahip: " + lastError())
+	}
+	return nil
+}
+
+// ClearIndex detaches the index (jb_index_clear).
+func (t *Tokenizer) ClearIndex() error {
+	t.mu.Lock()
+	defer t.mu.Unlock()
+	if rc := C.jb_index_clear(t.ctx); rc != C.JB_OK {
+		return errors.New("jiebahip: " + lastError())
+	}
+	return nil
+}
+
+// Search ranks the attached index's documents for each query by BM25 (jb_search_batch): the query is cut in
+// plain mode and looked up in the attached vocabulary, and at most topK documents come back per query, best
+// first (score descending, ties by document ascending).  Cut, looked up and ranked on the GPU.
+func (t *Tokenizer) Search(queries []string, topK uint32, useHmm bool) [][]Hit {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	out := make([][]Hit, len(queries))
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	off := make([]uint64, len(queries)+1)
+	total := 0
+	for i, q := range queries {
+		total += len(q)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, q := range queries {
+		b = append(b, q...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	k := int(topK)
+	if k == 0 {
+		k = 1
+	}
+	doc := make([]uint32, len(queries)*k+1)
+	score := make([]uint64, len(queries)*k+1)
+	n := make([]uint32, len(queries)+1)
+	rc := C.jb_search_batch(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+		C.uint32_t(len(queries)), hmm, C.uint32_t(topK), (*C.uint32_t)(unsafe.Pointer(&doc[0])),
+		(*C.uint64_t)(unsafe.Pointer(&score[0])), (*C.uint32_t)(unsafe.Pointer(&n[0])))
+	if rc != C.JB_OK {
+		// JB_EPANIC: the reference panics on this input
+		panic("jiebahip: " + lastError())
+	}
+	for q := range queries {
+		for r := 0; r < int(n[q]); r++ {
+			out[q] = append(out[q], Hit{doc[q*k+r], score[q*k+r]})
+		}
+	}
+	return out
+}
+
 // CutParallel (tokenizer.go:81) returns the tokens of Cut in document order.
 // The library splits the work itself: the text goes to the device in pieces cut
 // at Han-run starts (jb_split_points), and over every device of a multi-device

@@ -192,6 +192,34 @@ Tokenizer::Index Tokenizer::Postings(const std::vector<std::string>& docs, bool 
     return ix;
 }
 
+void Tokenizer::SetIndex(const Index& ix, double k1, double b) {
+    if (ix.off.empty() || ix.doc.size() != ix.tf.size())
+        throw Error(JB_EINVAL, "SetIndex: an index without offsets, or doc and tf of different lengths");
+    check(jb_index_set(ctx_, ix.off.data(), ix.doc.data(), ix.tf.data(), ix.doc.size(), (uint32_t)(ix.off.size() - 1),
+                       ix.docLen.data(), ix.docLen.size(), k1, b));
+}
+
+void Tokenizer::ClearIndex() { check(jb_index_clear(ctx_)); }
+
+std::vector<std::vector<Tokenizer::Hit>> Tokenizer::Search(const std::vector<std::string>& queries, uint32_t topK,
+                                                           bool useHmm) {
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& q : queries) {
+        all += q;
+        off.push_back(all.size());
+    }
+    const size_t nq = queries.size(), k = topK ? topK : 1;
+    std::vector<uint32_t> doc(nq * k + 1), n(nq + 1);
+    std::vector<uint64_t> score(nq * k + 1);
+    check(jb_search_batch(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)nq, useHmm ? 1 : 0, topK, doc.data(),
+                          score.data(), n.data()));
+    std::vector<std::vector<Hit>> out(nq);
+    for (size_t q = 0; q < nq; q++)
+        for (uint32_t r = 0; r < n[q]; r++) out[q].push_back(Hit{doc[q * k + r], score[q * k + r]});
+    return out;
+}
+
 std::vector<std::vector<Tokenizer::Rank>> Tokenizer::TextRank(const std::vector<std::string>& docs,
                                                               const std::vector<uint8_t>& keep, uint32_t topK,
                                                               uint32_t span, uint32_t iters, bool useHmm) {

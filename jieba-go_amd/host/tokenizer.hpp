@@ -95,6 +95,21 @@ public:
         std::vector<uint32_t> doc, tf, docLen;
     };
     Index Postings(const std::vector<std::string>& docs, bool useHmm = true, uint32_t docBase = 0);
+    // BM25 search (jb_index_set and jb_search_batch in jiebahip.h).  SetIndex attaches an index (Postings' result
+    // for a corpus in one batch, or the batches' lists concatenated per id) to search; it stays on the device
+    // with the documents' norms and the ids' weights until the next SetIndex, ClearIndex or the tokenizer's end.
+    // Search cuts the queries in plain mode, looks their tokens up in the attached vocabulary and returns per
+    // query at most topK documents, best first (score descending, ties by document ascending); a Hit's score is
+    // in units of 2^-24 (Score() is the plain value).  Cut, looked up and ranked on the GPU: only the hits come
+    // back.
+    struct Hit {
+        uint32_t doc;
+        uint64_t score;
+        double Score() const { return (double)score / 16777216.0; }
+    };
+    void SetIndex(const Index& ix, double k1 = 1.2, double b = 0.75);
+    void ClearIndex();
+    std::vector<std::vector<Hit>> Search(const std::vector<std::string>& queries, uint32_t topK = 10, bool useHmm = true);
     // TextRank keywords (jieba.analyse.textrank; jb_textrank_batch in jiebahip.h, with the rule and its
     // differences from jieba's): per document the topK words of the attached vocabulary by PageRank over
     // the co-occurrence graph of the kept tokens within `span` positions, `iters` Jacobi rounds, best

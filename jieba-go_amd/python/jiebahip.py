@@ -45,6 +45,10 @@ JB_TC_HAN, JB_TC_ALNUM, JB_TC_NUM, JB_TC_OTHER, JB_TC_INVALID = 1, 2, 4, 8, 16  
 JB_FILTER_STOP = 1  # the filter rule's flag: drop the tokens found in the stop set
 JB_FILTER_TILE = 2048  # tokens per tile of jb_filter_device
 JB_POSTINGS_TILE = 4096  # entries per tile of jb_postings_device
+JB_BM25_TILE = 8192  # documents per tile of jb_bm25_search_device
+JB_BM25_MAXQ = 1024  # entries of a query that jb_bm25_search reads
+JB_BM25_WMAX = float(1 << 20)  # the largest weight that takes part in a search
+JB_BM25_ONE = 1 << 24  # a BM25 score's unit: score / JB_BM25_ONE is the plain value
 _CLASSES = {"han": JB_TC_HAN, "alnum": JB_TC_ALNUM, "num": JB_TC_NUM, "other": JB_TC_OTHER, "invalid": JB_TC_INVALID}
 _TOKENIZE_MODES = {"default": JB_MODE_CUT, "search": JB_MODE_SEARCH, "full": JB_MODE_FULL}
 
@@ -73,6 +77,8 @@ EXPORTS = [
     "jb_stopwords_set", "jb_stopwords_size", "jb_filter_work_bytes", "jb_filter", "jb_filter_device",
     "jb_cut_batch_filter", "jb_batch_filter_set",
     "jb_postings_work_bytes", "jb_postings", "jb_postings_device", "jb_postings_batch",
+    "jb_bm25_work_bytes", "jb_bm25_avgdl", "jb_bm25_norms", "jb_bm25_idf", "jb_bm25_search", "jb_bm25_norms_device",
+    "jb_bm25_idf_device", "jb_bm25_search_device", "jb_index_set", "jb_index_clear", "jb_index_info", "jb_search_batch",
 ]
 
 
@@ -335,6 +341,23 @@ def lib():
                                          C.c_uint64, vp, vp, vp, C.c_size_t]
         L.jb_postings_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64, vp, C.c_uint32, vp, vp,
                                         vp, vp]
+        L.jb_bm25_work_bytes.restype = C.c_size_t
+        L.jb_bm25_work_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        L.jb_bm25_avgdl.argtypes = [vp, C.c_uint32, C.POINTER(C.c_double)]
+        L.jb_bm25_norms.argtypes = [vp, C.c_uint32, C.c_double, C.c_double, C.c_double, vp]
+        L.jb_bm25_idf.argtypes = [vp, C.c_uint32, C.c_uint64, vp]
+        L.jb_bm25_search.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_double, vp,
+                                     C.c_uint64, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.jb_bm25_norms_device.argtypes = [vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_double, vp, vp]
+        L.jb_bm25_idf_device.argtypes = [vp, vp, C.c_uint32, C.c_uint64, vp, vp]
+        L.jb_bm25_search_device.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32,
+                                            C.c_double, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
+                                            C.c_size_t]
+        L.jb_index_set.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.c_double, C.c_double]
+        L.jb_index_clear.argtypes = [vp]
+        L.jb_index_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_double)]
+        L.jb_search_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp]
         L.jb_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
         L.jb_device_free.argtypes = [vp, vp]
         L.jb_device_free.restype = None
@@ -1308,6 +1331,77 @@ class Tokenizer:
         doc_len = np.concatenate(lens) if lens else np.zeros(0, np.uint32)
         return post_off, post_doc, post_tf, doc_len, ndocs
 
+    # -- BM25 search over the index ------------------------------------------
+    def bm25_norms_device(self, d_doc_len, ndocs, k1, b, avgdl, d_norm, stream_ptr=0):
+        """jb_bm25_norms_device over raw device pointers: f32 norm[d] from u32 doc_len[d]; queued on the stream."""
+        _check(lib().jb_bm25_norms_device(self.h, C.c_void_p(d_doc_len), ndocs, k1, b, avgdl, C.c_void_p(stream_ptr),
+                                          C.c_void_p(d_norm)))
+
+    def bm25_idf_device(self, d_post_off, nids, ndocs_total, d_weight, stream_ptr=0):
+        """jb_bm25_idf_device over raw device pointers: f32 weight[t] from the lists' lengths; queued on the stream."""
+        _check(lib().jb_bm25_idf_device(self.h, C.c_void_p(d_post_off), nids, ndocs_total, C.c_void_p(stream_ptr),
+                                        C.c_void_p(d_weight)))
+
+    def bm25_search_device(self, d_post_doc, d_post_tf, d_post_off, npost, nids, d_norm, ndocs, d_weight, nweights, k1,
+                           d_q_id, q_cap, d_q_off, nq, topk, d_res_doc, d_res_score, d_res_n, d_work, nwork,
+                           stream_ptr=0):
+        """jb_bm25_search_device over raw device pointers: per query of the CSR (u32 q_id, u64 q_off[nq + 1]) the
+        topk best documents of the index as u32 res_doc / u64 res_score [nq, topk] (units of 2^-24) and u32
+        res_n[nq]; queued on the stream.  d_work: bm25_work_bytes(nq, ndocs, topk) bytes."""
+        _check(lib().jb_bm25_search_device(self.h, C.c_void_p(d_post_doc), C.c_void_p(d_post_tf), C.c_void_p(d_post_off),
+                                           npost, nids, C.c_void_p(d_norm), ndocs, C.c_void_p(d_weight), nweights, k1,
+                                           C.c_void_p(d_q_id), q_cap, C.c_void_p(d_q_off), nq, topk,
+                                           C.c_void_p(stream_ptr), C.c_void_p(d_res_doc), C.c_void_p(d_res_score),
+                                           C.c_void_p(d_res_n), C.c_void_p(d_work), nwork))
+
+    def set_index(self, post_off, post_doc, post_tf, doc_len, ndocs=None, k1=1.2, b=0.75):
+        """jb_index_set: attach an index to search, replacing any earlier one: build_index's tuple unchanged
+        (tk.set_index(*tk.build_index(batches))).  The postings, the documents' norms and the ids' BM25 weights
+        stay on the device."""
+        po = np.ascontiguousarray(post_off, np.uint64)
+        pd = np.ascontiguousarray(post_doc, np.uint32)
+        pt = np.ascontiguousarray(post_tf, np.uint32)
+        dl = np.ascontiguousarray(doc_len, np.uint32)
+        if ndocs is not None and ndocs != len(dl):
+            raise ValueError(f"set_index: ndocs = {ndocs}, doc_len has {len(dl)} entries")
+        if len(pd) != len(pt):
+            raise ValueError("set_index: post_doc and post_tf differ in length")
+        p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        _check(lib().jb_index_set(self.h, po.ctypes.data, p(pd), p(pt), len(pd), len(po) - 1, p(dl), len(dl), k1, b))
+
+    def clear_index(self):
+        """jb_index_clear: detach the index."""
+        _check(lib().jb_index_clear(self.h))
+
+    def index_info(self):
+        """jb_index_info: (ndocs, nids, npost, avgdl) of the attached index."""
+        nd, ni, npo, av = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+        _check(lib().jb_index_info(self.h, C.byref(nd), C.byref(ni), C.byref(npo), C.byref(av)))
+        return nd.value, ni.value, npo.value, av.value
+
+    def search_batch(self, buf, q_off, hmm, topk=10):
+        """jb_search_batch: host query text -> (res_doc u32[nq, topk], res_score u64[nq, topk], res_n u32[nq])."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        nq = len(q_off) - 1
+        rows = max(nq, 1) * max(int(topk), 1)
+        rd, rs, rn = np.empty(rows, np.uint32), np.empty(rows, np.uint64), np.empty(max(nq, 1), np.uint32)
+        _check(lib().jb_search_batch(self.h, buf.ctypes.data, q_off.ctypes.data, nq, int(hmm), topk, rd.ctypes.data,
+                                     rs.ctypes.data, rn.ctypes.data))
+        shape = (nq, int(topk))
+        return rd[:nq * topk].reshape(shape), rs[:nq * topk].reshape(shape), rn[:nq]
+
+    def search(self, queries, topk=10, hmm=True):
+        """Rank the attached index's documents for each query (str / bytes) by BM25: per query a list of
+        (document, score), best first, at most topk.  The query is cut in plain mode and looked up in the
+        attached vocabulary; unknown tokens do not count."""
+        qs = [_b(t) for t in queries]
+        off = np.zeros(len(qs) + 1, np.uint64)
+        if qs:
+            off[1:] = np.cumsum([len(q) for q in qs], dtype=np.uint64)
+        rd, rs, rn = self.search_batch(np.frombuffer(b"".join(qs) + b"\0", np.uint8), off, hmm, topk)
+        return [[(int(rd[q, r]), int(rs[q, r]) / JB_BM25_ONE) for r in range(int(rn[q]))] for q in range(len(qs))]
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -1357,7 +1451,7 @@ class Tokenizer:
         _check(lib().jb_profile_reset(self.h))
 
     def profile_read(self):
-        cap = 64  # (more than the library's kernels: 57)
+        cap = 128  # (more than the library's kernels: 63)
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         n = (C.c_uint64 * cap)()
@@ -1630,6 +1724,62 @@ def postings(term_id, term_cnt, term_off, nids, doc_base=0, nterms=None, cap=Non
     _check(lib().jb_postings(p(ti), p(tc), to.ctypes.data, nterms, cap, nd, nids, doc_base, p(pd), p(pt), pcap,
                              po.ctypes.data, C.byref(n)))
     return pd, pt, po, n.value
+
+
+def bm25_work_bytes(nq, ndocs, topk):
+    """jb_bm25_work_bytes: bytes of the work buffer jb_bm25_search_device needs (host only)."""
+    return lib().jb_bm25_work_bytes(nq, ndocs, topk)
+
+
+def bm25_avgdl(doc_len):
+    """jb_bm25_avgdl (host only): the mean of u32 doc_len as a float."""
+    dl = np.ascontiguousarray(doc_len, np.uint32)
+    av = C.c_double()
+    _check(lib().jb_bm25_avgdl(dl.ctypes.data if dl.size else None, len(dl), C.byref(av)))
+    return av.value
+
+
+def bm25_norms(doc_len, k1, b, avgdl):
+    """jb_bm25_norms (host only): f32 norm[d] = k1 * ((1 - b) + b * doc_len[d] / avgdl)."""
+    dl = np.ascontiguousarray(doc_len, np.uint32)
+    out = np.zeros(len(dl), np.float32)
+    p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    _check(lib().jb_bm25_norms(p(dl), len(dl), k1, b, avgdl, p(out)))
+    return out
+
+
+def bm25_idf(post_off, ndocs_total):
+    """jb_bm25_idf (host only): f32 weight[t] = go_log(1 + (N - df + 0.5) / (df + 0.5)) from the lists' lengths."""
+    po = np.ascontiguousarray(post_off, np.uint64)
+    out = np.zeros(len(po) - 1, np.float32)
+    _check(lib().jb_bm25_idf(po.ctypes.data, len(po) - 1, ndocs_total, out.ctypes.data if out.size else None))
+    return out
+
+
+def bm25_search(post_doc, post_tf, post_off, norm, weight, k1, q_id, q_off, topk=10, npost=None, nids=None, ndocs=None,
+                nweights=None, q_cap=None):
+    """jb_bm25_search (host only): the search rule of jiebahip.h on host arrays.  Returns (res_doc u32[nq, topk],
+    res_score u64[nq, topk] in units of 2^-24, res_n u32[nq])."""
+    pd = np.ascontiguousarray(post_doc, np.uint32)
+    pt = np.ascontiguousarray(post_tf, np.uint32)
+    po = np.ascontiguousarray(post_off, np.uint64)
+    nm = np.ascontiguousarray(norm, np.float32)
+    wt = np.ascontiguousarray(weight, np.float32)
+    qi = np.ascontiguousarray(q_id, np.uint32)
+    qo = np.ascontiguousarray(q_off, np.uint64)
+    npost = min(len(pd), len(pt)) if npost is None else npost
+    nids = len(po) - 1 if nids is None else nids
+    ndocs = len(nm) if ndocs is None else ndocs
+    nweights = len(wt) if nweights is None else nweights
+    q_cap = len(qi) if q_cap is None else q_cap
+    nq = len(qo) - 1
+    rows = max(nq, 1) * max(int(topk), 1)
+    rd, rs, rn = np.zeros(rows, np.uint32), np.zeros(rows, np.uint64), np.zeros(max(nq, 1), np.uint32)
+    p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    _check(lib().jb_bm25_search(p(pd), p(pt), po.ctypes.data, npost, nids, p(nm), ndocs, p(wt), nweights, k1, p(qi), q_cap,
+                                qo.ctypes.data, nq, topk, rd.ctypes.data, rs.ctypes.data, rn.ctypes.data))
+    shape = (nq, int(topk))
+    return rd[:nq * topk].reshape(shape), rs[:nq * topk].reshape(shape), rn[:nq]
 
 
 def _unit(unit):
