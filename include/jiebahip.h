@@ -1268,6 +1268,115 @@ int jb_index_info(jb_ctx *ctx, uint64_t *ndocs, uint64_t *nids, uint64_t *npost,
 int jb_search_batch(jb_ctx *ctx, const uint8_t *qtext, const uint64_t *q_off, uint32_t nq, int hmm, uint32_t topk,
                     uint32_t *res_doc, uint64_t *res_score, uint32_t *res_n);
 
+/* ---- near-duplicate pairs (the end of the recipe jieba.cut -> word shingles -> MinHash -> LSH bands: join the
+ * buckets, verify the candidates, label the groups; the reference has only Cut) ---------------------------
+ * Which documents are near-duplicates of which, from the band keys and the signatures of the MinHash calls
+ * above, on the device.  It replaces copying the ndocs * B keys and ndocs * K slots to the host, grouping the
+ * keys per band, enumerating the pairs of every bucket, dropping the pairs more than one band found and
+ * counting agreeing slots there.
+ *
+ * The rule (jb_neardup on host arrays, jb_neardup_device on device arrays: one rule, bit for bit).  Inputs: key,
+ * u64[ndocs * B] row-major (key[d * B + b]) as jb_minhash_bands(_device) writes it, or the caller's own; sig,
+ * u32[ndocs * K]; 1 <= B <= JB_MH_MAXK bands; 1 <= K <= JB_MH_MAXK slots; the window 1 <= W <= JB_ND_MAXWIN;
+ * 1 <= min_agree <= K.  There is no R: the keys embody it, and B <= K is not required.  Keys and slots are
+ * data, never indices: any bit pattern is legal.
+ *  - Buckets.  Document d is in bucket (b, key[d * B + b]) of band b unless that key is JB_MH_NOKEY.  The band
+ *    is part of the bucket's identity: equal key values in different bands are different buckets.  A bucket's
+ *    members are ordered by document number; member d's rank is the number of members below d.
+ *  - Candidates.  For i < j let b* be the least band in which both keys are not JB_MH_NOKEY and are equal.  The
+ *    pair (i, j) is a candidate iff b* exists and, in that bucket, rank(j) - rank(i) <= W.  A pair is examined
+ *    in exactly one band and never reported twice.  A member pairs with at most the W members just below it:
+ *    a bucket of m members costs at most m * W, not m^2 / 2, and consecutive members are always candidates,
+ *    which keeps a bucket connected for clustering.
+ *  - Verification.  agree(i, j) is the number of slots s < K with sig[i * K + s] == sig[j * K + s]: all K
+ *    slots, not only the banded ones.  A candidate is kept iff agree >= min_agree; the threshold is an integer
+ *    and the rule has no float in it.
+ *  - Output: a CSR by the later document.  Row j holds its kept pairs ordered by (b*, i) ascending, as pair_doc
+ *    (u32, the earlier document i) and pair_agree (u32); pair_off is u64[ndocs + 1]; *npairs (u64) is the true
+ *    count.  Only positions below pcap are written to pair_doc and pair_agree, as with pcap in the postings;
+ *    pair_off is always complete.  The order does not depend on how buckets are ordered among themselves.
+ *  - Counters, stat (u64[JB_ND_NSTAT]): [JB_ND_NENTRIES] keys that are not JB_MH_NOKEY; [JB_ND_NCAND]
+ *    candidates; [JB_ND_NTRUNC] members whose rank is above W.  When ntrunc is 0 the kept pairs are exactly
+ *    the set "some band agrees and agree >= min_agree".
+ *  - Errors.  JB_EINVAL: a null pointer (arrays of capacity 0 may be NULL), B, K, W or min_agree = 0, an output
+ *    that is an input, the work buffer or another output, a work buffer that is too small or not 8-byte
+ *    aligned; nothing is queued or written.  JB_ELIMIT: B, K or W above its maximum, min_agree > K,
+ *    ndocs * B >= 2^32 - JB_ND_TILE.
+ *
+ * jb_neardup_labels (host only): label[d] (u32[ndocs]) is the least document of d's connected component over
+ * the kept pairs, by a union-find over the CSR; label[d] == d marks the document to keep.  The CSR may be the
+ * caller's: an entry >= j in row j is skipped, and offsets are clamped to pcap.
+ *
+ * jb_neardup_device.  The contract is jb_postings_device's: the call queues its kernels on `stream` and
+ * returns; it does not synchronise, allocate or read anything on the host, and it holds the ctx's shared lock
+ * only while queuing.  d_work is a caller-owned device buffer of nwork >= jb_neardup_work_bytes(ndocs, B)
+ * bytes, 8-byte aligned: 24 bytes per entry of whole tiles of JB_ND_TILE entries (two key and two entry
+ * arrays the passes alternate between; after the sort one pair holds the keep masks and the pair counts) and
+ * about 1 KiB per tile.  The helper is host only, non-decreasing in both arguments and never 0.  There are 32
+ * launches whatever the data are (three memsets and none when ndocs == 0), no lane waits for another workgroup
+ * and there are no global atomics; every value is an integer, so the bytes are the same from run to run and
+ * equal to jb_neardup's.
+ *   k_nd_hist / k_nd_scan / k_nd_scatter   a stable LSD radix sort of the entries (d, b) by (band, key), 8 bits
+ *                 per pass, nine passes: the eight key bytes, then the band; the sort of jb_postings_device
+ *                 (ballot match, wave-ordered counters in LDS) with a u64 key and the entry as payload.
+ *                 JB_MH_NOKEY ends each band.  Stability keeps a bucket's documents ascending.
+ *   k_nd_mask     a wave per 64 sorted positions; for a position q whose predecessor has its bucket, lane w < W
+ *                 looks at position q - 1 - w: same band and same key (a run is contiguous and ascending, so
+ *                 this alone gives the window and the rank), then the first-band test over the two key rows;
+ *                 the candidates' signature rows are compared 64 slots at a time.  A u64 keep mask per
+ *                 position (hence W <= 64) and its popcount per entry; position q - W - 1 counts ntrunc.
+ *   k_nd_tsum / k_nd_base / k_nd_off   the exclusive scan of the counts over the entries into u64 offsets:
+ *                 pair_off, *npairs, and the counters' sums into stat.
+ *   k_nd_write    for each set bit, highest w first (i ascending), agree again, and the pair at its offset
+ *                 when that is below pcap.
+ * One form ships (there is no JB_ND_FORM): no second form was written.
+ * Measured on the 1 GiB corpus (tools/neardup_bench.py, profiles/neardup_bench.json; 73,443 documents, a seeded
+ * tenth replaced before the cut by copies of other documents with 0 to 5 % of their tokens overwritten; n = 5,
+ * K = 128, B = 32, R = 4, W = 64, min_agree = 102): the 2.35M entries take 0.70 ms (k_nd_hist 0.13 ms, k_nd_scan
+ * 0.06 ms, k_nd_scatter 0.35 ms, k_nd_mask 0.13 ms, k_nd_write 0.07 ms, the scan's three 0.04 ms, each summed over
+ * its launches), beside 6.02 ms for the cut step, 5.97 ms for jb_minhash_device and 0.02 ms for
+ * jb_minhash_bands_device in the same run; 7,720 candidates, 3,609 pairs, ntrunc 0, 69,881 labels kept.  The
+ * outputs were those of jb_neardup over the whole input (476 ms on the host after a 3.9 ms copy; numpy's stable
+ * argsort per band, the grouping alone, 125 ms).  4,000,000 synthetic signatures generated on the device (128M
+ * entries, a tenth planted copies) take 26.9 ms, of which the sort is 19.4 ms (k_nd_scatter 15.6 ms) and k_nd_mask
+ * 6.2 ms; on the first 250,000 of those rows the host rule takes 2.9 s and the device 1.4 ms for the same bytes.
+ * From pageable host memory jb_neardup_sig takes 1.90 ms for the corpus's signatures, beside 36.6 ms for
+ * jb_minhash_batch.
+ *
+ * jb_neardup_sig: host signatures in (sig u32[ndocs * K], doc_n u32[ndocs] as jb_minhash_batch returns them).
+ * It uploads them, runs jb_minhash_bands_device (B bands of R rows) and jb_neardup_device on ctx's first device
+ * through a buffer kept in the ctx that only grows (concurrent calls take turns, as in jb_minhash_batch), and
+ * copies the results back under jb_postings_batch's cap protocol: pair_off, *npairs and stat are always
+ * complete, and when *npairs exceeds pcap the call returns JB_ELIMIT with only those written.
+ *
+ * Deliberate differences from the usual LSH join (all pairs of every bucket, every band):
+ *  - the window: a member pairs with the W members just below it, not with all of them;
+ *  - the first-agreeing-band rule: with a window, a pair beyond the window in its first common band is not
+ *    picked up by a later band.  ntrunc tells the caller when that can have happened. */
+#define JB_ND_TILE 4096 /* entries per tile (one workgroup) */
+#define JB_ND_MAXWIN 64 /* the widest window: a keep mask is one u64 */
+#define JB_ND_NSTAT 3
+#define JB_ND_NENTRIES 0
+#define JB_ND_NCAND 1
+#define JB_ND_NTRUNC 2
+/* Host only, no ctx: non-decreasing in both arguments, never 0. */
+size_t jb_neardup_work_bytes(uint32_t ndocs, uint32_t B);
+/* host only, no ctx, no GPU: the rule, and the reference the device kernels are pinned to */
+int jb_neardup(const uint64_t *key, const uint32_t *sig, uint32_t ndocs, uint32_t B, uint32_t K, uint32_t W,
+               uint32_t min_agree, uint32_t *pair_doc, uint32_t *pair_agree, uint64_t pcap, uint64_t *pair_off,
+               uint64_t *npairs, uint64_t *stat);
+int jb_neardup_device(jb_ctx *ctx, const uint64_t *d_key, const uint32_t *d_sig, uint32_t ndocs, uint32_t B, uint32_t K,
+                      uint32_t W, uint32_t min_agree, uint32_t *d_pair_doc, uint32_t *d_pair_agree, uint64_t pcap,
+                      uint64_t *d_pair_off, uint64_t *d_npairs, uint64_t *d_stat, void *d_work, size_t nwork,
+                      void *stream);
+/* host only: label u32[ndocs] */
+int jb_neardup_labels(const uint64_t *pair_off, const uint32_t *pair_doc, uint64_t pcap, uint32_t ndocs,
+                      uint32_t *label);
+/* pair_off: ndocs + 1 host entries; pair_doc / pair_agree: pcap; stat: JB_ND_NSTAT. */
+int jb_neardup_sig(jb_ctx *ctx, const uint32_t *sig, const uint32_t *doc_n, uint32_t ndocs, uint32_t K, uint32_t B,
+                   uint32_t R, uint32_t W, uint32_t min_agree, uint32_t *pair_doc, uint32_t *pair_agree, uint64_t pcap,
+                   uint64_t *pair_off, uint64_t *npairs, uint64_t *stat);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

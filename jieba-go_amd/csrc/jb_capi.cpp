@@ -18,6 +18,7 @@
 #include "jb_textrank.h"
 #include "jb_filter.h"
 #include "jb_minhash.h"
+#include "jb_neardup.h"
 #include "jb_postings.h"
 #include "jb_bm25.h"
 #include "jb_wc.h"
@@ -2339,6 +2340,115 @@ extern "C" int jb_postings_batch(jb_ctx* ctx, const uint8_t* text, const uint64_
     if (rc == JB_OK && !ran) {  // (no document: the empty index)
         for (uint64_t t = 0; t <= nids; t++) post_off[t] = 0;
         *nposts = 0;
+    }
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Near-duplicate pairs (jb_neardup.hip; the host rule, jb_neardup, jb_neardup_labels, the argument checks, the
+// work buffer's layout and the size helper are jb_neardup.cpp)
+// ---------------------------------------------------------------------------
+static_assert(JB_ND_TILE == kNdTile && JB_ND_MAXWIN == kNdMaxWin, "the header's constants are the kernels'");
+
+extern "C" int jb_neardup_device(jb_ctx* ctx, const uint64_t* d_key, const uint32_t* d_sig, uint32_t ndocs, uint32_t B,
+                                 uint32_t K, uint32_t W, uint32_t min_agree, uint32_t* d_pair_doc, uint32_t* d_pair_agree,
+                                 uint64_t pcap, uint64_t* d_pair_off, uint64_t* d_npairs, uint64_t* d_stat, void* d_work,
+                                 size_t nwork, void* stream) {
+    const char* who = "jb_neardup_device";
+    // (the limits come first: they need no ctx)
+    if (const int rc = neardup_args(who, ndocs, B, K, W, min_agree)) return rc;
+    if (!ctx || !d_pair_off || !d_npairs || !d_stat || !d_work || (ndocs && (!d_key || !d_sig)) ||
+        (pcap && (!d_pair_doc || !d_pair_agree)))
+        return fail(JB_EINVAL, "%s: null argument", who);
+    if (const int rc = neardup_alias(who, d_key, d_sig, d_pair_doc, d_pair_agree, d_pair_off, d_npairs, d_stat, d_work))
+        return rc;
+    if (((uintptr_t)d_work & 7u) != 0) return fail(JB_EINVAL, "%s: d_work must be 8-byte aligned", who);
+    const size_t need = jb_neardup_work_bytes(ndocs, B);
+    if (nwork < need)
+        return fail(JB_EINVAL, "%s: a work buffer of %llu bytes, jb_neardup_work_bytes asks for %llu", who,
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_neardup(d_key, d_sig, ndocs, B, K, W, min_agree, d_pair_doc, d_pair_agree, pcap, d_pair_off, d_npairs,
+                           d_stat, d_work, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_neardup(d_key, d_sig, ndocs, B, K, W, min_agree, d_pair_doc, d_pair_agree, pcap, d_pair_off, d_npairs,
+                       d_stat, d_work, s, nullptr));
+    return JB_OK;
+}
+
+// Host signatures in, the pairs out: the upload, jb_minhash_bands_device and jb_neardup_device with every device
+// array in the ctx's buffer [12]; pair_off, the count and the counters come back first, the pairs when they fit
+// pcap.
+extern "C" int jb_neardup_sig(jb_ctx* ctx, const uint32_t* sig, const uint32_t* doc_n, uint32_t ndocs, uint32_t K,
+                              uint32_t B, uint32_t R, uint32_t W, uint32_t min_agree, uint32_t* pair_doc,
+                              uint32_t* pair_agree, uint64_t pcap, uint64_t* pair_off, uint64_t* npairs, uint64_t* stat) {
+    const char* who = "jb_neardup_sig";
+    if (const int rc = minhash_band_args(who, K, B, R)) return rc;
+    if (const int rc = neardup_args(who, ndocs, B, K, W, min_agree)) return rc;
+    if (!ctx || !pair_off || !npairs || !stat || (ndocs && (!sig || !doc_n)) || (pcap && (!pair_doc || !pair_agree)))
+        return fail(JB_EINVAL, "%s: null argument", who);
+    if (ndocs == 0) {
+        pair_off[0] = 0;
+        *npairs = 0;
+        for (uint32_t k = 0; k < JB_ND_NSTAT; k++) stat[k] = 0;
+        return JB_OK;
+    }
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    HIPCHK(hipSetDevice(ordinal));
+    std::lock_guard<std::mutex> kg(ctx->kw_mu);
+    hipStream_t st = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        const size_t nsig = (size_t)ndocs * K * 4, ndn = (size_t)ndocs * 4, nkey = (size_t)ndocs * B * 8,
+                     nwork = jb_neardup_work_bytes(ndocs, B), noff = ((size_t)ndocs + 1) * 8;
+        Arena a;
+        if ((rc = kw_arena(ctx, 12, r256(nsig) + r256(ndn) + r256(nkey) + r256(nwork) + 2 * r256(pcap * 4) + r256(noff) +
+                                        r256(8) + r256(JB_ND_NSTAT * 8), &a)))
+            return rc;
+        uint32_t* dsig = (uint32_t*)a.take(nsig);
+        uint32_t* ddn = (uint32_t*)a.take(ndn);
+        uint64_t* dkey = (uint64_t*)a.take(nkey);
+        void* work = a.take(nwork);
+        uint32_t* dpd = (uint32_t*)a.take(pcap * 4);
+        uint32_t* dpa = (uint32_t*)a.take(pcap * 4);
+        uint64_t* dpoff = (uint64_t*)a.take(noff);
+        uint64_t* dn = (uint64_t*)a.take(8);
+        uint64_t* dstat = (uint64_t*)a.take(JB_ND_NSTAT * 8);
+        HIPCHK(hipMemcpyAsync(dsig, sig, nsig, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ddn, doc_n, ndn, hipMemcpyHostToDevice, st));
+        if ((rc = jb_minhash_bands_device(ctx, dsig, ddn, ndocs, K, B, R, st, dkey))) return rc;
+        if ((rc = jb_neardup_device(ctx, dkey, dsig, ndocs, B, K, W, min_agree, pcap ? dpd : nullptr, pcap ? dpa : nullptr,
+                                    pcap, dpoff, dn, dstat, work, nwork, st)))
+            return rc;
+        HIPCHK(hipMemcpyAsync(pair_off, dpoff, noff, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(npairs, dn, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(stat, dstat, JB_ND_NSTAT * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (*npairs > pcap)
+            return fail(JB_ELIMIT, "%s: %llu pairs, the arrays hold %llu", who, (unsigned long long)*npairs,
+                        (unsigned long long)pcap);
+        if (*npairs) {
+            HIPCHK(hipMemcpyAsync(pair_doc, dpd, *npairs * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(pair_agree, dpa, *npairs * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        return JB_OK;
+    };
+    const int rc = run();
+    if (st) {
+        (void)hipStreamSynchronize(st);  // (a copy from or to the caller's memory may be in flight)
+        (void)hipStreamDestroy(st);
     }
     return rc;
 }

@@ -134,6 +134,7 @@ enum KernelId {
     K_FILT_MARK, K_FILT_SCAN, K_FILT_WRITE,
     K_POST_HIST, K_POST_SCAN, K_POST_SCATTER, K_POST_OFF,
     K_BM25_NORMS, K_BM25_IDF, K_BM25_TILE, K_BM25_SCATTER, K_BM25_SELECT, K_BM25_MERGE,
+    K_ND_HIST, K_ND_SCAN, K_ND_SCATTER, K_ND_MASK, K_ND_TSUM, K_ND_BASE, K_ND_OFF, K_ND_WRITE,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -405,6 +406,20 @@ hipError_t run_postings(const uint32_t* d_term_id, const uint32_t* d_term_cnt, c
                         const uint64_t* d_nterms, uint64_t cap, uint32_t ndocs, uint32_t nids, uint32_t doc_base,
                         uint32_t form, uint32_t* d_post_doc, uint32_t* d_post_tf, uint64_t pcap, uint64_t* d_post_off,
                         uint64_t* d_nposts, void* d_work, hipStream_t stream, KernelTimer* timer);
+
+// Near-duplicate pairs (jb_neardup_device; jb_neardup.hip, the rule's shared code is jb_neardup.h's).  Tile =
+// kNdTile entries, one workgroup.
+constexpr uint32_t kNdTile = 4096;  // JB_ND_TILE
+constexpr uint32_t kNdMaxWin = 64;  // JB_ND_MAXWIN: one bit of a u64 keep mask per place of the window
+// Enqueue 32 launches on `stream` (three memsets and no launch when ndocs is 0): the entries (d, b) of d_key
+// (ndocs x B) sorted by (band, key), the candidates of the window W verified against d_sig (ndocs x K), the
+// kept pairs as a CSR by the later document in d_pair_doc / d_pair_agree at positions below pcap, d_pair_off
+// (ndocs + 1), *d_npairs and d_stat (JB_ND_NSTAT).  d_work holds jb_neardup_work_bytes(ndocs, B) bytes, 8-byte
+// aligned.
+hipError_t run_neardup(const uint64_t* d_key, const uint32_t* d_sig, uint32_t ndocs, uint32_t B, uint32_t K, uint32_t W,
+                       uint32_t min_agree, uint32_t* d_pair_doc, uint32_t* d_pair_agree, uint64_t pcap,
+                       uint64_t* d_pair_off, uint64_t* d_npairs, uint64_t* d_stat, void* d_work, hipStream_t stream,
+                       KernelTimer* timer);
 
 // BM25 (jb_bm25_*_device; jb_bm25.hip, the rule's shared code is jb_bm25.h's).  A document tile is kBm25Tile
 // consecutive documents, one workgroup per pair of query and tile.

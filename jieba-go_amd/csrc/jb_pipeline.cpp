@@ -45,7 +45,9 @@ const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_
                                          "k_filt_mark", "k_filt_scan", "k_filt_write",
                                          "k_post_hist", "k_post_scan", "k_post_scatter", "k_post_off",
                                          "k_bm25_norms", "k_bm25_idf", "k_bm25_tile", "k_bm25_scatter", "k_bm25_select",
-                                         "k_bm25_merge"};
+                                         "k_bm25_merge",
+                                         "k_nd_hist", "k_nd_scan", "k_nd_scatter", "k_nd_mask", "k_nd_tsum",
+                                         "k_nd_base", "k_nd_off", "k_nd_write"};
 
 hipError_t run_pipeline(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes,
                         const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, const LaunchCfg& lc,

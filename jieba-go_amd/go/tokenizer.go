@@ -590,6 +590,54 @@ func (t *Tokenizer) MinHash(texts []string, n, k int, seed uint64, useHmm bool, 
 	return sig, docN
 }
 
+// NearDuplicates groups the near-duplicates of a batch: MinHash as above, then b LSH bands of r rows, the bucket
+// join inside the window w (1 to JB_ND_MAXWIN) and the verification against all k slots on the GPU
+// (jb_neardup_sig), and the groups' labels (jb_neardup_labels).  label[d] is the least text of d's group, so
+// label[d] == d marks the one text of each group to keep.  minAgree is the least number of equal slots of a kept
+// pair; 0 means the integer nearest 0.8 k.  Never returns nil.
+func (t *Tokenizer) NearDuplicates(texts []string, n, k, b, r, w, minAgree int, seed uint64, useHmm bool, mode int) (label []uint32) {
+	label = make([]uint32, len(texts))
+	if len(texts) == 0 {
+		return label
+	}
+	sig, docN := t.MinHash(texts, n, k, seed, useHmm, mode)
+	if minAgree == 0 {
+		minAgree = (4*k + 2) / 5
+		if minAgree < 1 {
+			minAgree = 1
+		}
+	}
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	flat := sig[0][:len(texts)*k : len(texts)*k] // (MinHash's rows are slices of one array)
+	pairOff := make([]uint64, len(texts)+1)
+	var stat [C.JB_ND_NSTAT]C.uint64_t
+	var np C.uint64_t
+	pcap := 4*len(texts) + 1024
+	var pairDoc, pairAgree []uint32
+	for pass := 0; pass < 2; pass++ {
+		pairDoc = make([]uint32, pcap)
+		pairAgree = make([]uint32, pcap)
+		rc := C.jb_neardup_sig(t.ctx, (*C.uint32_t)(unsafe.Pointer(&flat[0])), (*C.uint32_t)(unsafe.Pointer(&docN[0])),
+			C.uint32_t(len(texts)), C.uint32_t(k), C.uint32_t(b), C.uint32_t(r), C.uint32_t(w), C.uint32_t(minAgree),
+			(*C.uint32_t)(unsafe.Pointer(&pairDoc[0])), (*C.uint32_t)(unsafe.Pointer(&pairAgree[0])), C.uint64_t(pcap),
+			(*C.uint64_t)(unsafe.Pointer(&pairOff[0])), &np, &stat[0])
+		if rc == C.JB_ELIMIT && uint64(np) > uint64(pcap) && pass == 0 {
+			pcap = int(np) // (the arrays were too small: the count is known now)
+			continue
+		}
+		if rc != C.JB_OK {
+			panic("jiebahip: " + lastError())
+		}
+		break
+	}
+	if rc := C.jb_neardup_labels((*C.uint64_t)(unsafe.Pointer(&pairOff[0])), (*C.uint32_t)(unsafe.Pointer(&pairDoc[0])),
+		np, C.uint32_t(len(texts)), (*C.uint32_t)(unsafe.Pointer(&label[0]))); rc != C.JB_OK {
+		panic("jiebahip: " + lastError())
+	}
+	return label
+}
+
 // FilterRule is jb_filter_rule: DropClasses holds C.JB_TC_* bits, MinRunes and MaxRunes (0: no upper bound) are at
 // most 255, and Stop drops the tokens found in the stop set (SetStopWords).
 type FilterRule struct {

@@ -350,6 +350,35 @@ Tokenizer::MinHashResult Tokenizer::MinHash(const std::vector<std::string>& docs
     return r;
 }
 
+Tokenizer::NearDupResult Tokenizer::NearDuplicates(const std::vector<std::string>& docs, uint32_t n, uint32_t K, uint32_t B,
+                                                   uint32_t R, uint32_t W, uint32_t minAgree, uint64_t seed, bool useHmm,
+                                                   int mode) {
+    const MinHashResult mh = MinHash(docs, n, K, seed, useHmm, mode);
+    const uint32_t nd = (uint32_t)docs.size();
+    if (minAgree == 0) minAgree = std::max<uint32_t>(1, (4 * K + 2) / 5);
+    NearDupResult r;
+    r.pairOff.resize((size_t)nd + 1);
+    r.label.resize((size_t)nd + 1);  // (+ 1: never an empty vector, its address is passed)
+    uint64_t np = 0, cap = std::max<uint64_t>(1024, 4ull * nd);
+    for (int pass = 0; pass < 2; pass++) {
+        r.pairDoc.resize(cap);
+        r.pairAgree.resize(cap);
+        const int rc = jb_neardup_sig(ctx_, mh.sig.data(), mh.docN.data(), nd, K, B, R, W, minAgree, r.pairDoc.data(),
+                                      r.pairAgree.data(), cap, r.pairOff.data(), &np, r.stat);
+        if (rc == JB_ELIMIT && np > cap && pass == 0) {  // (the arrays were too small: the count is known now)
+            cap = np;
+            continue;
+        }
+        check(rc);
+        break;
+    }
+    r.pairDoc.resize(np);
+    r.pairAgree.resize(np);
+    check(jb_neardup_labels(r.pairOff.data(), r.pairDoc.data(), np, nd, r.label.data()));
+    r.label.resize(nd);
+    return r;
+}
+
 std::vector<std::vector<Tokenizer::Token>> Tokenizer::Tokenize(const std::vector<std::string>& docs, bool useHmm, int mode,
                                                                int unit) {
     std::string all;

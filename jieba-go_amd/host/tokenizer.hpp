@@ -178,6 +178,20 @@ public:
     };
     MinHashResult MinHash(const std::vector<std::string>& docs, uint32_t n = 5, uint32_t K = 128, uint64_t seed = 1,
                           bool useHmm = true, int mode = JB_MODE_CUT);
+    // Near-duplicate groups (jb_neardup_sig and jb_neardup_labels in jiebahip.h): MinHash as above, then LSH
+    // bands of R rows, the bucket join inside the window W and the verification against all K slots on the GPU.
+    // label[d] is the least document of d's group: label[d] == d marks the one document of each group to keep.
+    // Row j of the CSR (pairOff, pairDoc, pairAgree) lists the earlier documents kept as near-duplicates of j.
+    // minAgree == 0 means the integer nearest 0.8 K.
+    struct NearDupResult {
+        std::vector<uint32_t> label;      // docs.size()
+        std::vector<uint64_t> pairOff;    // docs.size() + 1
+        std::vector<uint32_t> pairDoc, pairAgree;
+        uint64_t stat[JB_ND_NSTAT];
+    };
+    NearDupResult NearDuplicates(const std::vector<std::string>& docs, uint32_t n = 5, uint32_t K = 128, uint32_t B = 32,
+                                 uint32_t R = 4, uint32_t W = 64, uint32_t minAgree = 0, uint64_t seed = 1,
+                                 bool useHmm = true, int mode = JB_MODE_CUT);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

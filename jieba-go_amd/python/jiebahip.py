@@ -49,6 +49,10 @@ JB_BM25_TILE = 8192  # documents per tile of jb_bm25_search_device
 JB_BM25_MAXQ = 1024  # entries of a query that jb_bm25_search reads
 JB_BM25_WMAX = float(1 << 20)  # the largest weight that takes part in a search
 JB_BM25_ONE = 1 << 24  # a BM25 score's unit: score / JB_BM25_ONE is the plain value
+JB_ND_TILE = 4096  # entries per tile of jb_neardup_device
+JB_ND_MAXWIN = 64  # the widest window of the near-duplicate calls
+JB_ND_NSTAT = 3  # the near-duplicate calls' counters: entries, candidates, members beyond the window
+JB_ND_NENTRIES, JB_ND_NCAND, JB_ND_NTRUNC = 0, 1, 2
 _CLASSES = {"han": JB_TC_HAN, "alnum": JB_TC_ALNUM, "num": JB_TC_NUM, "other": JB_TC_OTHER, "invalid": JB_TC_INVALID}
 _TOKENIZE_MODES = {"default": JB_MODE_CUT, "search": JB_MODE_SEARCH, "full": JB_MODE_FULL}
 
@@ -79,6 +83,7 @@ EXPORTS = [
     "jb_postings_work_bytes", "jb_postings", "jb_postings_device", "jb_postings_batch",
     "jb_bm25_work_bytes", "jb_bm25_avgdl", "jb_bm25_norms", "jb_bm25_idf", "jb_bm25_search", "jb_bm25_norms_device",
     "jb_bm25_idf_device", "jb_bm25_search_device", "jb_index_set", "jb_index_clear", "jb_index_info", "jb_search_batch",
+    "jb_neardup_work_bytes", "jb_neardup", "jb_neardup_device", "jb_neardup_labels", "jb_neardup_sig",
 ]
 
 
@@ -358,6 +363,15 @@ def lib():
         L.jb_index_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_double)]
         L.jb_search_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp, vp]
+        L.jb_neardup_work_bytes.restype = C.c_size_t
+        L.jb_neardup_work_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        L.jb_neardup.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64,
+                                 vp, vp, vp]
+        L.jb_neardup_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
+                                        C.c_uint64, vp, vp, vp, vp, C.c_size_t, vp]
+        L.jb_neardup_labels.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp]
+        L.jb_neardup_sig.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     vp, vp, C.c_uint64, vp, vp, vp]
         L.jb_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
         L.jb_device_free.argtypes = [vp, vp]
         L.jb_device_free.restype = None
@@ -1402,6 +1416,55 @@ class Tokenizer:
         rd, rs, rn = self.search_batch(np.frombuffer(b"".join(qs) + b"\0", np.uint8), off, hmm, topk)
         return [[(int(rd[q, r]), int(rs[q, r]) / JB_BM25_ONE) for r in range(int(rn[q]))] for q in range(len(qs))]
 
+    # -- near-duplicate pairs ----------------------------------------------------
+    def neardup_device(self, d_key, d_sig, ndocs, B, K, W, min_agree, d_pair_doc, d_pair_agree, pcap, d_pair_off,
+                       d_npairs, d_stat, d_work, nwork, stream_ptr=0):
+        """jb_neardup_device over raw device pointers: the band keys (u64[ndocs, B]) joined per bucket inside the
+        window W and verified against the signatures (u32[ndocs, K]): the kept pairs as a CSR by the later document
+        (u32 earlier documents and agree counts at positions below pcap, u64 pair_off[ndocs + 1], a u64 count and
+        u64 stat[JB_ND_NSTAT]); queued on the stream.  d_work: neardup_work_bytes(ndocs, B) bytes."""
+        _check(lib().jb_neardup_device(self.h, C.c_void_p(d_key), C.c_void_p(d_sig), ndocs, B, K, W, min_agree,
+                                       C.c_void_p(d_pair_doc), C.c_void_p(d_pair_agree), pcap, C.c_void_p(d_pair_off),
+                                       C.c_void_p(d_npairs), C.c_void_p(d_stat), C.c_void_p(d_work), nwork,
+                                       C.c_void_p(stream_ptr)))
+
+    def near_duplicates(self, sig, doc_n, B, R, W=64, min_agree=None, pcap=None):
+        """jb_neardup_sig: host signatures (uint32[ndocs, K]) and shingle counts -> (pair_off u64[ndocs + 1],
+        pair_doc u32[n], pair_agree u32[n], stat u64[JB_ND_NSTAT]): row j lists the earlier documents i kept as
+        near-duplicates of j.  min_agree defaults to the integer nearest 0.8 K.  With `pcap` given the arrays hold
+        that many pairs and a longer result raises JbError(JB_ELIMIT); otherwise they are grown to the count the
+        first call reports."""
+        sig = np.ascontiguousarray(sig, np.uint32)
+        doc_n = np.ascontiguousarray(doc_n, np.uint32)
+        nd, K = sig.shape
+        if min_agree is None:
+            min_agree = _default_agree(K)
+        cap = max(1024, 4 * nd) if pcap is None else pcap
+        pair_off = np.zeros(nd + 1, np.uint64)
+        stat = np.zeros(JB_ND_NSTAT, np.uint64)
+        n = C.c_uint64()
+        p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        for _ in range(2):
+            pd, pa = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+            rc = lib().jb_neardup_sig(self.h, p(sig), p(doc_n), nd, K, B, R, W, min_agree, p(pd), p(pa), cap,
+                                      pair_off.ctypes.data, C.byref(n), stat.ctypes.data)
+            if rc == JB_ELIMIT and n.value > cap and pcap is None:
+                cap = n.value
+                continue
+            _check(rc)
+            break
+        return pair_off, pd[:n.value], pa[:n.value], stat
+
+    def dedup(self, texts, n=5, K=128, B=32, R=4, W=64, min_agree=None, seed=1, mode="cut", hmm=True):
+        """Near-duplicate groups of a batch of texts (str / bytes): cut, MinHash over shingles of n words, LSH
+        bands and the bucket join on the GPU, then the groups' labels.  Returns (label uint32[ndocs], keep
+        bool[ndocs]): label[d] is the least document of d's group and keep[d] = (label[d] == d) marks the one
+        document of each group to keep.  min_agree defaults to the integer nearest 0.8 K."""
+        sig, doc_n = self.minhash(texts, n, K, seed, mode, hmm)
+        pair_off, pair_doc, _, _ = self.near_duplicates(sig, doc_n, B, R, W, min_agree)
+        label = neardup_labels(pair_off, pair_doc)
+        return label, label == np.arange(len(label), dtype=np.uint32)
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -1724,6 +1787,50 @@ def postings(term_id, term_cnt, term_off, nids, doc_base=0, nterms=None, cap=Non
     _check(lib().jb_postings(p(ti), p(tc), to.ctypes.data, nterms, cap, nd, nids, doc_base, p(pd), p(pt), pcap,
                              po.ctypes.data, C.byref(n)))
     return pd, pt, po, n.value
+
+
+def _default_agree(K):
+    """The integer nearest 0.8 K, at least 1: the near-duplicate calls' default threshold."""
+    return max(1, (4 * int(K) + 2) // 5)
+
+
+def neardup_work_bytes(ndocs, B):
+    """jb_neardup_work_bytes: bytes of the work buffer jb_neardup_device needs (host only)."""
+    return lib().jb_neardup_work_bytes(ndocs, B)
+
+
+def neardup(key, sig, W=64, min_agree=None, pcap=None):
+    """jb_neardup (host only): the near-duplicate rule of jiebahip.h on host arrays (band keys uint64[ndocs, B],
+    signatures uint32[ndocs, K]).  Returns (pair_doc, pair_agree, pair_off u64[ndocs + 1], npairs, stat
+    u64[JB_ND_NSTAT]); without `pcap` the arrays hold exactly the npairs pairs, with it they have pcap entries,
+    of which min(npairs, pcap) are written.  min_agree defaults to the integer nearest 0.8 K."""
+    key = np.ascontiguousarray(key, np.uint64)
+    sig = np.ascontiguousarray(sig, np.uint32)
+    (nd, B), K = key.shape, sig.shape[1]
+    if sig.shape[0] != nd:
+        raise ValueError("neardup: key and sig have different numbers of rows")
+    if min_agree is None:
+        min_agree = _default_agree(K)
+    po, st, n = np.zeros(nd + 1, np.uint64), np.zeros(JB_ND_NSTAT, np.uint64), C.c_uint64()
+    p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    for cap in ((0, None) if pcap is None else (pcap,)):
+        cap = n.value if cap is None else cap
+        pd, pa = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        _check(lib().jb_neardup(p(key), p(sig), nd, B, K, W, min_agree, p(pd), p(pa), cap, po.ctypes.data, C.byref(n),
+                                st.ctypes.data))
+    return pd, pa, po, n.value, st
+
+
+def neardup_labels(pair_off, pair_doc, pcap=None):
+    """jb_neardup_labels (host only): label uint32[ndocs], the least document of each document's connected
+    component over the pairs of the CSR (pair_off u64[ndocs + 1], pair_doc u32); pcap defaults to len(pair_doc)."""
+    po = np.ascontiguousarray(pair_off, np.uint64)
+    pd = np.ascontiguousarray(pair_doc, np.uint32)
+    nd = len(po) - 1
+    label = np.zeros(nd, np.uint32)
+    _check(lib().jb_neardup_labels(po.ctypes.data, pd.ctypes.data if pd.size else None, len(pd) if pcap is None else pcap,
+                                   nd, label.ctypes.data if nd else None))
+    return label
 
 
 def bm25_work_bytes(nq, ndocs, topk):
