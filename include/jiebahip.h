@@ -1377,6 +1377,139 @@ int jb_neardup_sig(jb_ctx *ctx, const uint32_t *sig, const uint32_t *doc_n, uint
                    uint32_t R, uint32_t W, uint32_t min_agree, uint32_t *pair_doc, uint32_t *pair_agree, uint64_t pcap,
                    uint64_t *pair_off, uint64_t *npairs, uint64_t *stat);
 
+/* ---- collocations: adjacent-pair counts and new-word scores (gensim's Phrases; the first step of Chinese
+ * "new word discovery") -------------------------------------------------------------------------
+ *
+ * Everything above sees only the words the dictionary knows; a word it lacks comes out in pieces.  jb_add_word
+ * changes that, and these calls say what to add: how often token a is directly followed by token b over a
+ * corpus, against how often each occurs alone.  The pairs and the corpus-wide token count per id are accumulated
+ * on the device over any number of batches, scored there, and only the candidates are read back.
+ *
+ * The rule.  jb_colloc_count / jb_colloc_score (host only, no ctx, no GPU) and the device agree exactly.
+ *  - Inputs: those of jb_textrank_device.  ids (ids_cap valid entries), doc_tok (u64[ndocs + 1], non-decreasing),
+ *    ntok, an optional keep (u8[nkeep]), a flag word, and with JB_COLLOC_CONTIG the spans start / end (u32; both
+ *    may be NULL without the flag).  Token k exists iff k < min(ntok, ids_cap).  Document d's tokens are
+ *    [doc_tok[d], doc_tok[d+1]) clamped to that bound; a token before doc_tok[0], or at or past doc_tok[ndocs],
+ *    belongs to no document and takes no part in anything.  The ids are not trusted: any u32 is an id.
+ *  - Unigrams.  Every existing token of a document with id < nuni does uni[id] += 1 (uni: u64[nuni], the
+ *    caller's), whatever keep and the flags say, so that p(a) is the corpus probability.  N (`known`) is the
+ *    number of such tokens, accumulated over the batches.
+ *  - Pairs.  (k, k+1) takes part iff both tokens exist and lie in the same document, both ids are < nuni (so
+ *    neither is JB_ID_UNK), with nkeep > 0 both ids are < nkeep with keep[id] != 0 (nkeep == 0: keep may be NULL,
+ *    every id is kept), and with JB_COLLOC_CONTIG end[k] == start[k+1]: no dropped whitespace, no filtered
+ *    token and no overlap lies between them, which makes a+b a substring of the text.  The key is
+ *    (uint64_t)a << 32 | b, ordered: (a, b) is not (b, a).  Each pair adds 1 to its key's u64 count.
+ *  - Table.  A caller-owned device buffer of jb_colloc_table_bytes(nslots) bytes, 32-byte aligned: a header
+ *    with a magic word and the totals, then nslots slots of key and count; nslots is a power of two >= 8
+ *    (JB_ELIMIT above 2^30).  New keys are accepted while fewer than nslots / 2 slots are claimed; a pair whose
+ *    key finds no slot is dropped.  The totals are u64 and exact: tokens (the tokens that exist), known (N),
+ *    pairs, dropped and distinct (the keys claimed).  The sum of the counts plus dropped is pairs, and the sum
+ *    of uni is known, always.  A key that is in the table carries its exact count: dropped pairs belong only to
+ *    keys that are not in the table.  With dropped == 0 the result is complete, independent of the order of the
+ *    adds and the same from run to run.  Which keys survive a full table, and where a key sits, is not
+ *    determined and nothing exposes it.
+ *  - Score.  For a key's count c, ca = uni[a], cb = uni[b], N, min_count m >= 1 (JB_EINVAL for 0), a float
+ *    threshold and a scorer, the pair is no candidate when a or b >= nuni, c < m, ca or cb is 0, c >= N, or any
+ *    of c, ca, cb, N is >= 2^53 (the arrays are the caller's and are not trusted).  All arithmetic is f64 with
+ *    one rounding per operation and no fused multiply-add; log is jb_go_log.
+ *      JB_COLLOC_NPMI   pa = ca/N, pb = cb/N, pab = c/N; s = log(pab / (pa*pb)) / (0.0 - log(pab)): gensim's
+ *                       npmi_scorer, in [-1, 1]
+ *      JB_COLLOC_RATIO  s = (((double)(c - m) / ca) / cb) * N: Mikolov's score in gensim's operation order
+ *      JB_COLLOC_COUNT  s = (double)c: the most frequent pairs, and the way to dump a table
+ *    score = (float)s, and the pair is a candidate iff score >= threshold (false for NaN).
+ *  - Order of a result: score descending, then count descending, then a ascending, then b ascending.
+ *
+ * jb_colloc_table_bytes and jb_colloc_work_bytes are host only, non-decreasing in their arguments and never 0
+ * (SIZE_MAX where the size does not fit; a slot count that is not valid is sized as the next valid one).
+ *
+ * jb_colloc_init_device queues the kernels that empty a table and zero d_uni (u64[nuni]).
+ *
+ * jb_colloc_add_device adds one batch with jb_wc_add_device's and jb_terms_device's contract: it queues on
+ * `stream` and returns without synchronising, allocating, reading on the host or using the per-device
+ * workspace, and takes the shared lock only while queuing.  Four launches whatever the data (none when ids_cap
+ * is 0), and no lane ever waits for another; it writes nothing outside the table, d_uni and
+ * d_work.  d_ntok is a device u64; d_work holds jb_colloc_work_bytes(ids_cap, ndocs) bytes, 4-byte aligned;
+ * d_table is 32-byte aligned and d_uni 8-byte aligned: JB_EINVAL otherwise, and for unknown flags, with nothing
+ * queued.  JB_ELIMIT for ids_cap >= 2^32 - JB_COLLOC_TILE.  A buffer without a valid header is left untouched,
+ * and so are d_uni and d_work then.  The count pass has two forms with identical results (JB_COLLOC_COMBINE,
+ * read at jb_open): 0 is one global atomic per pair and per unigram, 1 (the default) combines a workgroup's adds
+ * in two direct-mapped tables of JB_COLLOC_LDS entries in LDS first, over a share of at least JB_COLLOC_SHARE
+ * tiles of JB_COLLOC_TILE tokens; an entry that finds another key's tag goes to memory itself.
+ *
+ * jb_colloc_score_device is one pass over the slots, queued on `stream`: the candidates go to d_cand_a,
+ * d_cand_b (u32), d_cand_cnt (u64) and d_cand_score (f32) of capacity ccap in no promised order; *d_ncand (a
+ * device u64) always counts the complete set, entries with index >= ccap are not written, and nothing else is
+ * written.  N is read from the table's header on the device.
+ *
+ * jb_colloc_read synchronises `stream`, runs the score pass into a buffer of its own (growing it and
+ * repeating the pass when the candidates outnumber it), copies back only the candidates, sorts them on the
+ * host into the order above and keeps the first topn (0: all).  The table is left unchanged.  JB_EINVAL when
+ * the buffer holds no table.  jb_colloc_result_free frees the arrays (malloc'd) and zeroes the struct.
+ *
+ * jb_colloc_count is the rule of the add on host arrays: uni[id] += 1 into the caller's uni, and out holds every
+ * pair in the table sorted by key (score = (float)count) with the batch's totals.  nslots (0: no limit, else as
+ * above) gives the drop behaviour, with keys accepted in token order.  jb_colloc_score is the score rule over
+ * host arrays of n pairs, N given; out holds the candidates in the rule's order, the totals 0.
+ *
+ * jb_colloc_batch: host text in.  It uploads, runs plain Cut -> ids -> add on ctx's first device through the
+ * buffers jb_keywords_batch keeps in the ctx; concurrent calls take turns.  It needs an attached vocabulary
+ * (JB_EINVAL), a batch under 2 GiB (JB_ELIMIT) and doc_off non-decreasing; the cut's errors pass through.
+ * While a batch filter is set (jb_batch_filter_set) it filters between the cut and the ids, as jb_wc_batch
+ * does; with JB_COLLOC_CONTIG a pair across a filtered-out token then does not count, by the rule itself.
+ *
+ * Deliberate differences from gensim's Phrases:
+ *  - JB_COLLOC_RATIO multiplies by N, the corpus's known tokens, where gensim puts the vocabulary's size;
+ *  - pairs are ordered and counted per adjacent position, not per sentence with a delimiter set, and no pair
+ *    is merged while counting: the next round (add the words, cut again) finds the three-piece words;
+ *  - nothing is pruned while counting: a full table drops new keys and says how many pairs that cost.
+ *
+ * Measured (tools/colloc_bench.py, profiles/colloc_bench.json) on the 1 GiB corpus, 139,547,178 plain-mode ids under
+ * the 964,284-key vocabulary its word counts give, 62,835,284 distinct pairs among 139,473,735 in a table of 2^28
+ * slots (4.0 GiB, load 0.23; 2^26 slots dropped 31,235,490 pairs): jb_colloc_add_device 16.29 ms in the combining
+ * form, the default, against 132.74 ms with one global atomic per add, into a table that holds the pairs already;
+ * 225.82 ms against 342.68 ms into an empty one; beside 6.05 ms for the cut step, 1.79 ms for jb_ids_device and
+ * 9.19 ms for jb_wc_add_device.  jb_colloc_score_device 1.08 ms for 54,331 candidates (NPMI, min_count 5,
+ * threshold 0.5).  Both forms' tables were identical over the whole corpus and equal to jb_colloc_count over its
+ * first 64 MiB.  The ids copied to the host take 86 ms and np.unique over the pair keys about 1.7 s. */
+#define JB_COLLOC_CONTIG 1u
+#define JB_COLLOC_NPMI 0
+#define JB_COLLOC_RATIO 1
+#define JB_COLLOC_COUNT 2
+#define JB_COLLOC_TILE 256   /* tokens per tile */
+#define JB_COLLOC_LDS 2048   /* entries of each of the combining form's two LDS tables */
+#define JB_COLLOC_SHARE 64   /* the combining form: a workgroup's share is at least this many tiles */
+typedef struct jb_colloc_result {
+    uint32_t *a, *b;  /* n each: the pair's ids */
+    uint64_t *count;  /* n */
+    float *score;     /* n */
+    uint64_t n;
+    uint64_t tokens, known, pairs, dropped, distinct;
+} jb_colloc_result;
+
+size_t jb_colloc_table_bytes(uint64_t nslots);
+size_t jb_colloc_work_bytes(uint64_t max_tokens, uint32_t ndocs);
+int jb_colloc_init_device(jb_ctx *ctx, void *d_table, size_t ntable, uint64_t nslots, uint64_t *d_uni, uint32_t nuni,
+                          void *stream);
+int jb_colloc_add_device(jb_ctx *ctx, void *d_table, size_t ntable, uint64_t *d_uni, uint32_t nuni,
+                         const uint32_t *d_ids, uint64_t ids_cap, const uint64_t *d_doc_tok, const uint64_t *d_ntok,
+                         uint32_t ndocs, const uint8_t *d_keep, uint32_t nkeep, uint32_t flags, const uint32_t *d_start,
+                         const uint32_t *d_end, void *stream, void *d_work, size_t nwork);
+int jb_colloc_score_device(jb_ctx *ctx, const void *d_table, size_t ntable, const uint64_t *d_uni, uint32_t nuni,
+                           int scorer, uint64_t min_count, float threshold, uint32_t *d_cand_a, uint32_t *d_cand_b,
+                           uint64_t *d_cand_cnt, float *d_cand_score, uint64_t ccap, uint64_t *d_ncand, void *stream);
+int jb_colloc_read(jb_ctx *ctx, const void *d_table, size_t ntable, const uint64_t *d_uni, uint32_t nuni, int scorer,
+                   uint64_t min_count, float threshold, uint64_t topn, void *stream, jb_colloc_result *out);
+void jb_colloc_result_free(jb_colloc_result *r);
+int jb_colloc_count(const uint32_t *ids, uint64_t ids_cap, const uint64_t *doc_tok, uint64_t ntok, uint32_t ndocs,
+                    const uint8_t *keep, uint32_t nkeep, uint32_t flags, const uint32_t *start, const uint32_t *end,
+                    uint64_t nslots, uint64_t *uni, uint32_t nuni, jb_colloc_result *out);
+int jb_colloc_score(const uint32_t *a, const uint32_t *b, const uint64_t *count, uint64_t n, const uint64_t *uni,
+                    uint32_t nuni, uint64_t N, int scorer, uint64_t min_count, float threshold, uint64_t topn,
+                    jb_colloc_result *out);
+int jb_colloc_batch(jb_ctx *ctx, const uint8_t *text, const uint64_t *doc_off, uint32_t ndocs, int hmm,
+                    const uint8_t *keep, uint32_t nkeep, uint32_t flags, void *d_table, size_t ntable, uint64_t *d_uni,
+                    uint32_t nuni);
+
 /* Error state of the last jb_cut_device / jb_cut_device_into pipeline on ctx's first
  * device (from any thread): synchronises `stream` (the one that call was queued on) and
  * the pipeline, then returns JB_OK, JB_EPANIC (input on which the reference panics:

@@ -21,6 +21,7 @@
 #include "jb_neardup.h"
 #include "jb_postings.h"
 #include "jb_bm25.h"
+#include "jb_colloc.h"
 #include "jb_wc.h"
 
 // ---------------------------------------------------------------------------
@@ -2340,6 +2341,257 @@ extern "C" int jb_postings_batch(jb_ctx* ctx, const uint8_t* text, const uint64_
     if (rc == JB_OK && !ran) {  // (no document: the empty index)
         for (uint64_t t = 0; t <= nids; t++) post_off[t] = 0;
         *nposts = 0;
+    }
+    return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Collocations (jb_colloc.hip; the host rules, jb_colloc_count and jb_colloc_score, the argument checks, the
+// sort of a result and the size helpers are jb_colloc.cpp)
+// ---------------------------------------------------------------------------
+static_assert(JB_COLLOC_TILE == kClTile && JB_COLLOC_LDS == kClLds && JB_COLLOC_SHARE == kClShare,
+              "the header's constants are the kernels'");
+
+namespace {
+
+// What every call that is handed a table checks: JB_OK, or JB_EINVAL with the thread's message set.
+int colloc_table_args(const char* who, const void* d_table, size_t ntable, const void* d_uni, uint32_t nuni) {
+    if (!d_table) return fail(JB_EINVAL, "%s: null table", who);
+    if (((uintptr_t)d_table & 31u) != 0) return fail(JB_EINVAL, "%s: d_table must be 32-byte aligned", who);
+    if (ntable < jb_cl_bytes(JB_CL_MIN_SLOTS))
+        return fail(JB_EINVAL, "%s: a table buffer of %llu bytes, the smallest table has %llu", who,
+                    (unsigned long long)ntable, (unsigned long long)jb_cl_bytes(JB_CL_MIN_SLOTS));
+    if (nuni && !d_uni) return fail(JB_EINVAL, "%s: null d_uni", who);
+    if (((uintptr_t)d_uni & 7u) != 0) return fail(JB_EINVAL, "%s: d_uni must be 8-byte aligned", who);
+    return JB_OK;
+}
+
+// The slots a buffer of ntable bytes has room for: the score pass's grid (the kernel reads the header itself).
+uint64_t colloc_room(size_t ntable) { return (ntable - JB_CL_HDR_BYTES) / JB_CL_SLOT_BYTES; }
+
+}  // namespace
+
+extern "C" int jb_colloc_init_device(jb_ctx* ctx, void* d_table, size_t ntable, uint64_t nslots, uint64_t* d_uni,
+                                     uint32_t nuni, void* stream) {
+    const char* who = "jb_colloc_init_device";
+    if (!ctx) return fail(JB_EINVAL, "%s: null ctx", who);
+    if (const int rc = colloc_slots(who, nslots)) return rc;
+    if (const int rc = colloc_table_args(who, d_table, ntable, d_uni, nuni)) return rc;
+    if (ntable < jb_cl_bytes(nslots))
+        return fail(JB_EINVAL, "%s: a table buffer of %llu bytes, jb_colloc_table_bytes asks for %llu", who,
+                    (unsigned long long)ntable, (unsigned long long)jb_cl_bytes(nslots));
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    HIPCHK(run_colloc_init(d_table, nslots, d_uni, nuni, d->ncu, (hipStream_t)stream));
+    return JB_OK;
+}
+
+extern "C" int jb_colloc_add_device(jb_ctx* ctx, void* d_table, size_t ntable, uint64_t* d_uni, uint32_t nuni,
+                                    const uint32_t* d_ids, uint64_t ids_cap, const uint64_t* d_doc_tok,
+                                    const uint64_t* d_ntok, uint32_t ndocs, const uint8_t* d_keep, uint32_t nkeep,
+                                    uint32_t flags, const uint32_t* d_start, const uint32_t* d_end, void* stream,
+                                    void* d_work, size_t nwork) {
+    const char* who = "jb_colloc_add_device";
+    if (const int rc = colloc_add_args(who, d_ids, ids_cap, d_doc_tok, d_keep, nkeep, flags, d_start, d_end, d_uni, nuni))
+        return rc;
+    if (!ctx || !d_ntok || (ids_cap && !d_work)) return fail(JB_EINVAL, "%s: null argument", who);
+    if (const int rc = colloc_table_args(who, d_table, ntable, d_uni, nuni)) return rc;
+    if (((uintptr_t)d_work & 3u) != 0) return fail(JB_EINVAL, "%s: d_work must be 4-byte aligned", who);
+    const size_t need = jb_colloc_work_bytes(ids_cap, ndocs);
+    if (ids_cap && nwork < need)
+        return fail(JB_EINVAL, "%s: a work buffer of %llu bytes, jb_colloc_work_bytes asks for %llu", who,
+                    (unsigned long long)nwork, (unsigned long long)need);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    const bool combine = d->lc.colloc_combine != 0;
+    if (d->profile) {  // (the timer's event lists are the device's, under its lock)
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_colloc_add(d_table, ntable, d_uni, nuni, d_ids, ids_cap, d_doc_tok, d_ntok, ndocs, d_keep, nkeep, flags,
+                              d_start, d_end, combine, d_work, d->ncu, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_colloc_add(d_table, ntable, d_uni, nuni, d_ids, ids_cap, d_doc_tok, d_ntok, ndocs, d_keep, nkeep, flags,
+                          d_start, d_end, combine, d_work, d->ncu, s, nullptr));
+    return JB_OK;
+}
+
+extern "C" int jb_colloc_score_device(jb_ctx* ctx, const void* d_table, size_t ntable, const uint64_t* d_uni, uint32_t nuni,
+                                      int scorer, uint64_t min_count, float threshold, uint32_t* d_cand_a,
+                                      uint32_t* d_cand_b, uint64_t* d_cand_cnt, float* d_cand_score, uint64_t ccap,
+                                      uint64_t* d_ncand, void* stream) {
+    const char* who = "jb_colloc_score_device";
+    if (const int rc = colloc_score_args(who, d_uni, nuni, scorer, min_count)) return rc;
+    if (!ctx || !d_ncand || (ccap && (!d_cand_a || !d_cand_b || !d_cand_cnt || !d_cand_score)))
+        return fail(JB_EINVAL, "%s: null argument", who);
+    if (const int rc = colloc_table_args(who, d_table, ntable, d_uni, nuni)) return rc;
+    if (((uintptr_t)d_ncand & 7u) != 0 || ((uintptr_t)d_cand_cnt & 7u) != 0 || ((uintptr_t)d_cand_a & 3u) != 0 ||
+        ((uintptr_t)d_cand_b & 3u) != 0 || ((uintptr_t)d_cand_score & 3u) != 0)
+        return fail(JB_EINVAL, "%s: a candidate array is not aligned to its entries", who);
+    std::shared_lock<std::shared_mutex> rl(ctx->lock);
+    Device* d = ctx->devs[0].get();
+    HIPCHK(hipSetDevice(d->ordinal));
+    const hipStream_t s = (hipStream_t)stream;
+    if (d->profile) {
+        std::lock_guard<std::mutex> g(d->mu);
+        HIPCHK(run_colloc_score(d_table, ntable, colloc_room(ntable), d_uni, nuni, scorer, min_count, threshold, d_cand_a,
+                                d_cand_b, d_cand_cnt, d_cand_score, ccap, d_ncand, d->ncu, s, &d->timer));
+        return JB_OK;
+    }
+    HIPCHK(run_colloc_score(d_table, ntable, colloc_room(ntable), d_uni, nuni, scorer, min_count, threshold, d_cand_a,
+                            d_cand_b, d_cand_cnt, d_cand_score, ccap, d_ncand, d->ncu, s, nullptr));
+    return JB_OK;
+}
+
+extern "C" int jb_colloc_read(jb_ctx* ctx, const void* d_table, size_t ntable, const uint64_t* d_uni, uint32_t nuni,
+                              int scorer, uint64_t min_count, float threshold, uint64_t topn, void* stream,
+                              jb_colloc_result* out) {
+    const char* who = "jb_colloc_read";
+    if (!ctx || !out) return fail(JB_EINVAL, "%s: null argument", who);
+    memset(out, 0, sizeof *out);
+    if (const int rc = colloc_score_args(who, d_uni, nuni, scorer, min_count)) return rc;
+    if (const int rc = colloc_table_args(who, d_table, ntable, d_uni, nuni)) return rc;
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    HIPCHK(hipSetDevice(ordinal));
+    const hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipStreamSynchronize(st));
+    JbClHeader h;
+    HIPCHK(hipMemcpy(&h, d_table, sizeof h, hipMemcpyDeviceToHost));
+    if (h.magic != JB_CL_MAGIC || !jb_cl_slots_ok(h.nslots) || jb_cl_bytes(h.nslots) > ntable)
+        return fail(JB_EINVAL, "%s: the buffer holds no table (jb_colloc_init_device)", who);
+    // the candidates are at most the claimed keys; the buffer starts smaller and grows to the count once
+    uint64_t ccap = std::max<uint64_t>(1u, std::min<uint64_t>(std::min<uint64_t>(h.ctr[JB_CL_DISTINCT], h.nslots), 1u << 16));
+    uint64_t ncand = 0;
+    uint8_t* buf = nullptr;
+    auto run = [&]() -> int {
+        for (int pass = 0; pass < 2; pass++) {
+            // the candidate count, the counts (u64), then a, b (u32) and the scores (f32)
+            HIPCHK(hipMalloc(&buf, 8u + ccap * 20u));
+            uint64_t* dn = (uint64_t*)buf;
+            uint64_t* cc = dn + 1;
+            uint32_t* ca = (uint32_t*)(cc + ccap);
+            if (const int rc = jb_colloc_score_device(ctx, d_table, ntable, d_uni, nuni, scorer, min_count, threshold, ca,
+                                                      ca + ccap, cc, (float*)(ca + 2u * ccap), ccap, dn, stream))
+                return rc;
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipMemcpy(&ncand, dn, 8, hipMemcpyDeviceToHost));
+            if (ncand <= ccap) break;
+            if (pass == 1) return fail(JB_EDEVICE, "%s: the table changed while it was read", who);
+            (void)hipFree(buf);
+            buf = nullptr;
+            ccap = ncand;
+        }
+        if (const int rc = colloc_alloc(who, ncand, out)) return rc;
+        if (ncand) {
+            const uint64_t* cc = (const uint64_t*)buf + 1;
+            const uint32_t* ca = (const uint32_t*)(cc + ccap);
+            HIPCHK(hipMemcpy(out->count, cc, ncand * 8u, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out->a, ca, ncand * 4u, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out->b, ca + ccap, ncand * 4u, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(out->score, ca + 2u * ccap, ncand * 4u, hipMemcpyDeviceToHost));
+        }
+        return JB_OK;
+    };
+    int rc = run();
+    if (buf) (void)hipFree(buf);
+    if (rc == JB_OK) {
+        try {
+            colloc_sort(out, topn);
+        } catch (const std::bad_alloc&) {
+            rc = fail(JB_ENOMEM, "%s: out of host memory", who);
+        }
+    }
+    if (rc) {
+        jb_colloc_result_free(out);
+        return rc;
+    }
+    out->tokens = h.ctr[JB_CL_TOKENS];
+    out->known = h.ctr[JB_CL_KNOWN];
+    out->pairs = h.ctr[JB_CL_PAIRS];
+    out->dropped = h.ctr[JB_CL_DROPPED];
+    out->distinct = h.ctr[JB_CL_DISTINCT];
+    return JB_OK;
+}
+
+// Host text in, the batch's pairs and unigrams into the table and d_uni: the plain cut into the ctx's buffer [0],
+// the batch filter's step when one is set, then jb_ids_device and jb_colloc_add_device with the ids, the keep mask
+// and the work buffer in [13].
+extern "C" int jb_colloc_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
+                               const uint8_t* keep, uint32_t nkeep, uint32_t flags, void* d_table, size_t ntable,
+                               uint64_t* d_uni, uint32_t nuni) {
+    const char* who = "jb_colloc_batch";
+    if (!ctx || !doc_off || (nkeep && !keep)) return fail(JB_EINVAL, "%s: null argument", who);
+    if (flags & ~JB_COLLOC_CONTIG) return fail(JB_EINVAL, "%s: flags %#x (JB_COLLOC_CONTIG)", who, flags);
+    if (const int rc = colloc_table_args(who, d_table, ntable, d_uni, nuni)) return rc;
+    for (uint32_t k = 0; k < ndocs; k++)
+        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
+    const uint64_t nb = doc_off[ndocs] - doc_off[0];
+    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
+    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
+    int ordinal;
+    {
+        std::shared_lock<std::shared_mutex> rl(ctx->lock);
+        if (!ctx->vocab) return fail(JB_EINVAL, "%s: no vocabulary attached (jb_vocab_set)", who);
+        ordinal = ctx->devs[0]->ordinal;
+    }
+    if (ndocs == 0) return JB_OK;
+    HIPCHK(hipSetDevice(ordinal));
+    std::vector<uint64_t> rel;
+    try {
+        rel.resize((size_t)ndocs + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
+    }
+    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
+    uint64_t cap = std::max<uint64_t>(nb, 1);  // (a batch of n bytes has at most n tokens)
+    std::lock_guard<std::mutex> kg(ctx->kw_mu);
+    hipStream_t st = nullptr;
+    auto run = [&]() -> int {
+        int rc;
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
+        Arena a;
+        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * cap * 4), &a))) return rc;
+        uint8_t* dt = (uint8_t*)a.take(nb + 64);
+        uint64_t* doff = (uint64_t*)a.take(ndoc8);
+        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
+        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the token count)
+        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
+        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
+        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+        if ((rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt))) return rc;
+        if ((rc = jb_device_status(ctx, st))) return rc;  // (waits; the cut's errors, JB_EPANIC included)
+        uint64_t ntok = 0;
+        HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
+        if (ctx->bfilter_on &&
+            (rc = batch_filter_step(ctx, who, ctx->bfilter, dt, nb, ndocs, st, ntok, &dse, &cap, &dtok, &dcnt)))
+            return rc;
+        const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);  // (the rest follows the token count)
+        const size_t nwork = jb_colloc_work_bytes(tcap, ndocs);
+        Arena b;
+        if ((rc = kw_arena(ctx, 13, r256(tcap * 4) + r256(std::max<size_t>(nkeep, 1)) + r256(nwork), &b))) return rc;
+        uint32_t* did = (uint32_t*)b.take(tcap * 4);
+        uint8_t* dkeep = (uint8_t*)b.take(std::max<size_t>(nkeep, 1));
+        void* dwork = b.take(nwork);
+        if (nkeep) HIPCHK(hipMemcpyAsync(dkeep, keep, nkeep, hipMemcpyHostToDevice, st));
+        if ((rc = jb_ids_device(ctx, dt, nb, dse, dse + cap, dcnt, tcap, st, did))) return rc;
+        if ((rc = jb_colloc_add_device(ctx, d_table, ntable, d_uni, nuni, did, tcap, dtok, dcnt, ndocs, dkeep, nkeep, flags,
+                                       dse, dse + cap, st, dwork, nwork)))
+            return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        return JB_OK;
+    };
+    const int rc = run();
+    if (st) {
+        (void)hipStreamSynchronize(st);  // (the copies from the caller's memory may be in flight)
+        (void)hipStreamDestroy(st);
     }
     return rc;
 }

@@ -249,6 +249,8 @@ static const uint64_t kMaxPiece = 1ull << 30;  // (a piece of several documents;
 //   JB_MH_FORM   jb_minhash_device's signature kernel: 0 the plain form, 1 the staged form (default)
 //   JB_POSTINGS_FORM jb_postings_device's scatter kernel: 0 from the lanes (default), 1 through LDS in runs
 //   JB_BM25_FORM jb_bm25_search_device: 0 a dense row per query and global atomics, 1 a tile's scores in LDS (default)
+//   JB_COLLOC_COMBINE jb_colloc_add_device's count pass: 0 one global atomic per pair and per unigram, 1 combined in
+//                 LDS (default)
 static int init_launch_cfg(Device* d) {
     LaunchCfg& lc = d->lc;
     lc.zh_waves = d->ncu * std::max(zh_waves_per_cu(true, false), zh_waves_per_cu(false, false));
@@ -331,6 +333,9 @@ static int init_launch_cfg(Device* d) {
     const int bf = env_int("JB_BM25_FORM", 1);
     if (bf < 0 || bf > 1) return fail(JB_EINVAL, "JB_BM25_FORM=%d: want 0 or 1", bf);
     lc.bm25_form = (uint32_t)bf;
+    const int clc = env_int("JB_COLLOC_COMBINE", 1);
+    if (clc < 0 || clc > 1) return fail(JB_EINVAL, "JB_COLLOC_COMBINE=%d: want 0 or 1", clc);
+    lc.colloc_combine = (uint32_t)clc;
     return JB_OK;
 }
 

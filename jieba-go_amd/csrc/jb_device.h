@@ -347,12 +347,13 @@ struct jb_ctx {
     // [8] jb_minhash_batch's work buffer, signatures and shingle counts,
     // [9] the batch filter's work buffer and filtered span list (jb_cut_batch_filter, jb_batch_filter_set),
     // [10] jb_postings_batch's work buffer and postings, [11] jb_search_batch's work buffer and records,
-    // [12] jb_neardup_sig's signatures, keys, work buffer and pairs
+    // [12] jb_neardup_sig's signatures, keys, work buffer and pairs,
+    // [13] jb_colloc_batch's ids, keep mask and work buffer
     std::mutex kw_mu;
-    void* kw_buf[13] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t kw_cap[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    // the rule jb_cut_batch_join, jb_wc_batch and jb_minhash_batch filter by (jb_batch_filter_set; under kw_mu)
+    void* kw_buf[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t kw_cap[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // the rule jb_cut_batch_join, jb_wc_batch, jb_minhash_batch and jb_colloc_batch filter by (jb_batch_filter_set; under kw_mu)
     bool bfilter_on = false;
     jb_filter_rule bfilter{0, 0, 0, 0};
     // the caller's index (jb_index_set) on the first device, one allocation: search calls read it under the

@@ -135,6 +135,7 @@ enum KernelId {
     K_POST_HIST, K_POST_SCAN, K_POST_SCATTER, K_POST_OFF,
     K_BM25_NORMS, K_BM25_IDF, K_BM25_TILE, K_BM25_SCATTER, K_BM25_SELECT, K_BM25_MERGE,
     K_ND_HIST, K_ND_SCAN, K_ND_SCATTER, K_ND_MASK, K_ND_TSUM, K_ND_BASE, K_ND_OFF, K_ND_WRITE,
+    K_CL_ZERO, K_CL_BOUNDS, K_CL_CLAIM, K_CL_COUNT, K_CL_SCORE,
     K_NUM
 };
 extern const char* const kKernelNames[K_NUM];
@@ -186,6 +187,9 @@ struct LaunchCfg {
     uint32_t bm25_form;      // jb_bm25_search_device: 0 a dense row per query and global atomics, 1 a document tile's
                              // scores in LDS (default: 0.96 ms against 1.75 ms on the 1 GiB corpus's index,
                              // profiles/bm25_bench.json) (JB_BM25_FORM; results do not depend on it)
+    uint32_t colloc_combine; // jb_colloc_add_device's count pass: 0 one global atomic per pair and per unigram, 1
+                             // combined in LDS (default: 16.29 ms against 132.74 ms on the 1 GiB corpus,
+                             // profiles/colloc_bench.json) (JB_COLLOC_COMBINE; results do not depend on it)
 };
 
 // k_zh's group split: g1 groups of grp bytes, then groups of *sgrp bytes to the end.
@@ -420,6 +424,26 @@ hipError_t run_neardup(const uint64_t* d_key, const uint32_t* d_sig, uint32_t nd
                        uint32_t min_agree, uint32_t* d_pair_doc, uint32_t* d_pair_agree, uint64_t pcap,
                        uint64_t* d_pair_off, uint64_t* d_npairs, uint64_t* d_stat, void* d_work, hipStream_t stream,
                        KernelTimer* timer);
+
+// Collocations (jb_colloc_*_device; jb_colloc.hip, the table and the rule's shared code are jb_colloc.h's).
+constexpr uint32_t kClTile = 256;   // JB_COLLOC_TILE
+constexpr uint32_t kClLds = 2048;   // JB_COLLOC_LDS: entries of each of form 1's two tables, 32 KiB of LDS in all
+constexpr uint32_t kClShare = 64;   // JB_COLLOC_SHARE: form 1's least share of a workgroup, in tiles
+// Enqueue the kernel that empties a table of nslots slots and zeroes d_uni.
+hipError_t run_colloc_init(void* d_table, uint64_t nslots, uint64_t* d_uni, uint32_t nuni, uint32_t ncu,
+                           hipStream_t stream);
+// Enqueue the four launches (none when ids_cap is 0) that add the tokens k < min(*d_ntok, ids_cap) of an id list to
+// the table of d_table and to d_uni.  d_work holds jb_colloc_work_bytes(ids_cap, ndocs) bytes, 4-byte aligned.
+hipError_t run_colloc_add(void* d_table, uint64_t ntable, uint64_t* d_uni, uint32_t nuni, const uint32_t* d_ids,
+                          uint64_t ids_cap, const uint64_t* d_doc_tok, const uint64_t* d_ntok, uint32_t ndocs,
+                          const uint8_t* d_keep, uint32_t nkeep, uint32_t flags, const uint32_t* d_start,
+                          const uint32_t* d_end, bool combine, void* d_work, uint32_t ncu, hipStream_t stream,
+                          KernelTimer* timer);
+// Enqueue a memset of *d_ncand and the score pass over the table's slots (nslots_hint sizes the grid only).
+hipError_t run_colloc_score(const void* d_table, uint64_t ntable, uint64_t nslots_hint, const uint64_t* d_uni, uint32_t nuni,
+                            int scorer, uint64_t min_count, float threshold, uint32_t* d_cand_a, uint32_t* d_cand_b,
+                            uint64_t* d_cand_cnt, float* d_cand_score, uint64_t ccap, uint64_t* d_ncand, uint32_t ncu,
+                            hipStream_t stream, KernelTimer* timer);
 
 // BM25 (jb_bm25_*_device; jb_bm25.hip, the rule's shared code is jb_bm25.h's).  A document tile is kBm25Tile
 // consecutive documents, one workgroup per pair of query and tile.

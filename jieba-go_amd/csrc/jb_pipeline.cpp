@@ -47,7 +47,8 @@ const char* const kKernelNames[K_NUM] = {"k_docbits", "k_mark_walk", "k_zh", "k_
                                          "k_bm25_norms", "k_bm25_idf", "k_bm25_tile", "k_bm25_scatter", "k_bm25_select",
                                          "k_bm25_merge",
                                          "k_nd_hist", "k_nd_scan", "k_nd_scatter", "k_nd_mask", "k_nd_tsum",
-                                         "k_nd_base", "k_nd_off", "k_nd_write"};
+                                         "k_nd_base", "k_nd_off", "k_nd_write",
+                                         "k_cl_zero", "k_cl_bounds", "k_cl_claim", "k_cl_count", "k_cl_score"};
 
 hipError_t run_pipeline(const DevImage& im, const Work& w, const uint8_t* d_text, uint64_t nbytes,
                         const uint64_t* d_doc_off, uint32_t ndocs, bool hmm, const LaunchCfg& lc,

@@ -638,6 +638,89 @@ func (t *Tokenizer) NearDuplicates(texts []string, n, k, b, r, w, minAgree int, 
 	return label
 }
 
+// Colloc is one collocation: word A directly followed by word B, Count times, with its Score.
+type Colloc struct {
+	A, B  string
+	Count uint64
+	Score float32
+}
+
+// Collocations counts how often word a is directly followed by word b over a batch of texts, against how often
+// each occurs alone, and scores the pairs (C.JB_COLLOC_NPMI, C.JB_COLLOC_RATIO, C.JB_COLLOC_COUNT), all on the
+// GPU under the attached vocabulary, whose keys (what SetVocab was given) name the pairs: best first, by score,
+// count and ids; only the candidates with at least minCount occurrences and a score of at least threshold come
+// back, the first topn of them (0: all).  contiguous counts a pair only when the two tokens touch in the text,
+// so that A + B is a substring: the top pairs the dictionary lacks are the words to AddWord.  nslots sizes the
+// pair table (a power of two; new pairs are accepted while fewer than half are taken); exact is false when
+// pairs were dropped for lack of room.  With mini_dict.txt and the vocabulary {abc, 一刹那, 这},
+// Collocations([]string{"这一刹那 abc abc"}, keys, C.JB_COLLOC_COUNT, 1, 0, 0, false, false, 1024) is
+// {这 一刹那 1} {一刹那 abc 1} {abc abc 1} in the order of the ids (tests/c_abi_colloc.c).  Never returns nil.
+func (t *Tokenizer) Collocations(texts []string, keys []string, scorer int, minCount uint64, threshold float32, topn uint64, contiguous, useHmm bool, nslots uint64) (pairs []Colloc, exact bool) {
+	t.mu.RLock()
+	defer t.mu.RUnlock()
+	pairs = []Colloc{}
+	nv := int64(C.jb_vocab_size(t.ctx))
+	if nv < 0 || nv != int64(len(keys)) {
+		panic("jiebahip: Collocations: keys are not the attached vocabulary's (SetVocab)")
+	}
+	off := make([]uint64, len(texts)+1)
+	total := 0
+	for i, d := range texts {
+		total += len(d)
+		off[i+1] = uint64(total)
+	}
+	b := make([]byte, 0, total+1)
+	for _, d := range texts {
+		b = append(b, d...)
+	}
+	b = append(b, 0) // (never an empty slice: its address is passed)
+	hmm := C.int(0)
+	if useHmm {
+		hmm = 1
+	}
+	flags := C.uint32_t(0)
+	if contiguous {
+		flags = C.JB_COLLOC_CONTIG
+	}
+	nuni := C.uint32_t(nv)
+	ntable := C.jb_colloc_table_bytes(C.uint64_t(nslots))
+	var table, uni unsafe.Pointer
+	if C.jb_device_alloc(t.ctx, ntable, &table) != C.JB_OK {
+		panic("jiebahip: " + lastError())
+	}
+	defer C.jb_device_free(t.ctx, table)
+	if C.jb_device_alloc(t.ctx, C.size_t(nv)*8+8, &uni) != C.JB_OK {
+		panic("jiebahip: " + lastError())
+	}
+	defer C.jb_device_free(t.ctx, uni)
+	var r C.jb_colloc_result
+	rc := C.jb_colloc_init_device(t.ctx, table, ntable, C.uint64_t(nslots), (*C.uint64_t)(uni), nuni, nil)
+	if rc == C.JB_OK {
+		rc = C.jb_colloc_batch(t.ctx, (*C.uint8_t)(unsafe.Pointer(&b[0])), (*C.uint64_t)(unsafe.Pointer(&off[0])),
+			C.uint32_t(len(texts)), hmm, nil, 0, flags, table, ntable, (*C.uint64_t)(uni), nuni)
+	}
+	if rc == C.JB_OK {
+		rc = C.jb_colloc_read(t.ctx, table, ntable, (*C.uint64_t)(uni), nuni, C.int(scorer), C.uint64_t(minCount),
+			C.float(threshold), C.uint64_t(topn), nil, &r)
+	}
+	if rc != C.JB_OK {
+		// JB_EINVAL: an unknown scorer, minCount 0 or a bad nslots; JB_EPANIC: the reference panics on this input
+		panic("jiebahip: " + lastError())
+	}
+	defer C.jb_colloc_result_free(&r)
+	n := int(r.n)
+	if n > 0 {
+		ia := unsafe.Slice((*uint32)(unsafe.Pointer(r.a)), n)
+		ib := unsafe.Slice((*uint32)(unsafe.Pointer(r.b)), n)
+		cnt := unsafe.Slice((*uint64)(unsafe.Pointer(r.count)), n)
+		sc := unsafe.Slice((*float32)(unsafe.Pointer(r.score)), n)
+		for i := 0; i < n; i++ {
+			pairs = append(pairs, Colloc{keys[ia[i]], keys[ib[i]], cnt[i], sc[i]})
+		}
+	}
+	return pairs, r.dropped == 0
+}
+
 // FilterRule is jb_filter_rule: DropClasses holds C.JB_TC_* bits, MinRunes and MaxRunes (0: no upper bound) are at
 // most 255, and Stop drops the tokens found in the stop set (SetStopWords).
 type FilterRule struct {

@@ -379,6 +379,45 @@ Tokenizer::NearDupResult Tokenizer::NearDuplicates(const std::vector<std::string
     return r;
 }
 
+std::vector<Tokenizer::Colloc> Tokenizer::Collocations(const std::vector<std::string>& docs,
+                                                       const std::vector<std::string>& keys, int scorer,
+                                                       uint64_t minCount, float threshold, uint64_t topn, bool contiguous,
+                                                       const std::vector<uint8_t>& keep, bool useHmm, uint64_t nslots) {
+    const int64_t nv = jb_vocab_size(ctx_);
+    if (nv < 0) throw Error(JB_EINVAL, "Collocations: no vocabulary attached (SetVocab)");
+    if ((uint64_t)nv != keys.size()) throw Error(JB_EINVAL, "Collocations: keys are not the attached vocabulary's");
+    std::string all;
+    std::vector<uint64_t> off(1, 0);
+    for (const auto& d : docs) {
+        all += d;
+        off.push_back(all.size());
+    }
+    const uint32_t nuni = (uint32_t)nv;
+    const size_t ntable = jb_colloc_table_bytes(nslots);
+    void *table = nullptr, *uni = nullptr;
+    check(jb_device_alloc(ctx_, ntable, &table));
+    int rc = jb_device_alloc(ctx_, (size_t)nuni * 8 + 8, &uni);
+    jb_colloc_result r;
+    if (rc == JB_OK) rc = jb_colloc_init_device(ctx_, table, ntable, nslots, (uint64_t*)uni, nuni, nullptr);
+    if (rc == JB_OK)
+        rc = jb_colloc_batch(ctx_, (const uint8_t*)all.data(), off.data(), (uint32_t)docs.size(), useHmm ? 1 : 0,
+                             keep.empty() ? nullptr : keep.data(), (uint32_t)keep.size(), contiguous ? JB_COLLOC_CONTIG : 0u,
+                             table, ntable, (uint64_t*)uni, nuni);
+    if (rc == JB_OK)
+        rc = jb_colloc_read(ctx_, table, ntable, (const uint64_t*)uni, nuni, scorer, minCount, threshold, topn, nullptr, &r);
+    jb_device_free(ctx_, uni);
+    jb_device_free(ctx_, table);
+    check(rc);
+    std::vector<Colloc> out;
+    out.reserve(r.n);
+    for (uint64_t i = 0; i < r.n; i++) out.push_back({keys[r.a[i]], keys[r.b[i]], r.count[i], r.score[i]});
+    const uint64_t dropped = r.dropped;
+    jb_colloc_result_free(&r);
+    if (dropped)
+        throw Error(JB_ELIMIT, "Collocations: " + std::to_string(dropped) + " pairs dropped for lack of room: pairs are missing");
+    return out;
+}
+
 std::vector<std::vector<Tokenizer::Token>> Tokenizer::Tokenize(const std::vector<std::string>& docs, bool useHmm, int mode,
                                                                int unit) {
     std::string all;

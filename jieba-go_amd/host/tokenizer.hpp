@@ -192,6 +192,23 @@ public:
     NearDupResult NearDuplicates(const std::vector<std::string>& docs, uint32_t n = 5, uint32_t K = 128, uint32_t B = 32,
                                  uint32_t R = 4, uint32_t W = 64, uint32_t minAgree = 0, uint64_t seed = 1,
                                  bool useHmm = true, int mode = JB_MODE_CUT);
+    // Collocations (jb_colloc_batch and jb_colloc_read in jiebahip.h): how often word a is directly followed by
+    // word b over the documents, against how often each occurs alone, counted and scored on the GPU under the
+    // attached vocabulary, whose keys (what SetVocab was given) name the pairs: best first, by score, count and ids.
+    // scorer is JB_COLLOC_NPMI, JB_COLLOC_RATIO or JB_COLLOC_COUNT; contiguous counts a pair only when the two
+    // tokens touch in the text, so that a + b is a substring: the top pairs the dictionary lacks are the words to
+    // AddWord.  keep (one byte per key, empty: all) limits the pairs to kept words.  Throws when pairs were
+    // dropped for lack of room in the table of nslots slots (a power of two; four times the distinct pairs).
+    struct Colloc {
+        std::string a, b;
+        uint64_t count;
+        float score;
+    };
+    std::vector<Colloc> Collocations(const std::vector<std::string>& docs, const std::vector<std::string>& keys,
+                                     int scorer = JB_COLLOC_NPMI, uint64_t minCount = 5, float threshold = 0.5f,
+                                     uint64_t topn = 0, bool contiguous = false,
+                                     const std::vector<uint8_t>& keep = {}, bool useHmm = true,
+                                     uint64_t nslots = 1u << 20);
     // CutParallel (tokenizer.go:81).  Blocks are segmented in parallel on the
     // GPU; numWorkers is accepted for API compatibility.  Output is always in
     // text order (ordered=false in the reference is a block permutation).

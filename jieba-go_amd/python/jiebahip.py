@@ -52,6 +52,12 @@ JB_BM25_ONE = 1 << 24  # a BM25 score's unit: score / JB_BM25_ONE is the plain v
 JB_ND_TILE = 4096  # entries per tile of jb_neardup_device
 JB_ND_MAXWIN = 64  # the widest window of the near-duplicate calls
 JB_ND_NSTAT = 3  # the near-duplicate calls' counters: entries, candidates, members beyond the window
+JB_COLLOC_CONTIG = 1  # the collocation calls' flag: a pair counts only when end[k] == start[k+1]
+JB_COLLOC_NPMI, JB_COLLOC_RATIO, JB_COLLOC_COUNT = 0, 1, 2
+JB_COLLOC_TILE = 256  # tokens per tile of jb_colloc_add_device
+JB_COLLOC_LDS = 2048  # entries of each of the combining count pass's two LDS tables
+JB_COLLOC_SHARE = 64  # the combining count pass: a workgroup's share is at least this many tiles
+_SCORERS = {"npmi": JB_COLLOC_NPMI, "ratio": JB_COLLOC_RATIO, "count": JB_COLLOC_COUNT}
 JB_ND_NENTRIES, JB_ND_NCAND, JB_ND_NTRUNC = 0, 1, 2
 _CLASSES = {"han": JB_TC_HAN, "alnum": JB_TC_ALNUM, "num": JB_TC_NUM, "other": JB_TC_OTHER, "invalid": JB_TC_INVALID}
 _TOKENIZE_MODES = {"default": JB_MODE_CUT, "search": JB_MODE_SEARCH, "full": JB_MODE_FULL}
@@ -84,6 +90,9 @@ EXPORTS = [
     "jb_bm25_work_bytes", "jb_bm25_avgdl", "jb_bm25_norms", "jb_bm25_idf", "jb_bm25_search", "jb_bm25_norms_device",
     "jb_bm25_idf_device", "jb_bm25_search_device", "jb_index_set", "jb_index_clear", "jb_index_info", "jb_search_batch",
     "jb_neardup_work_bytes", "jb_neardup", "jb_neardup_device", "jb_neardup_labels", "jb_neardup_sig",
+    "jb_colloc_table_bytes", "jb_colloc_work_bytes", "jb_colloc_init_device", "jb_colloc_add_device",
+    "jb_colloc_score_device", "jb_colloc_read", "jb_colloc_result_free", "jb_colloc_count", "jb_colloc_score",
+    "jb_colloc_batch",
 ]
 
 
@@ -145,6 +154,44 @@ class WcResult:
     def __repr__(self):
         return (f"WcResult({len(self.keys)} keys, tokens={self.tokens}, bad={self.bad}, long={self.long}, "
                 f"dropped={self.dropped}, collided={self.collided})")
+
+
+class jb_colloc_result(C.Structure):
+    _fields_ = [("a", C.POINTER(C.c_uint32)), ("b", C.POINTER(C.c_uint32)), ("count", C.POINTER(C.c_uint64)),
+                ("score", C.POINTER(C.c_float)), ("n", C.c_uint64), ("tokens", C.c_uint64), ("known", C.c_uint64),
+                ("pairs", C.c_uint64), ("dropped", C.c_uint64), ("distinct", C.c_uint64)]
+
+
+class CollocResult:
+    """A collocation result: a, b (uint32 ids), count (uint64) and score (float32), one entry per pair in the
+    rule's order, and the five totals (tokens, known, pairs, dropped, distinct)."""
+
+    def __init__(self, r):
+        n = r.n
+        self.a = np.ctypeslib.as_array(r.a, (max(n, 1),))[:n].copy()
+        self.b = np.ctypeslib.as_array(r.b, (max(n, 1),))[:n].copy()
+        self.count = np.ctypeslib.as_array(r.count, (max(n, 1),))[:n].copy()
+        self.score = np.ctypeslib.as_array(r.score, (max(n, 1),))[:n].copy()
+        self.tokens, self.known, self.pairs, self.dropped, self.distinct = (
+            r.tokens, r.known, r.pairs, r.dropped, r.distinct)
+
+    def totals(self):
+        return (self.tokens, self.known, self.pairs, self.dropped, self.distinct)
+
+    def __len__(self):
+        return len(self.a)
+
+    def __repr__(self):
+        return (f"CollocResult({len(self.a)} pairs, tokens={self.tokens}, known={self.known}, pairs={self.pairs}, "
+                f"dropped={self.dropped}, distinct={self.distinct})")
+
+
+def _scorer(scorer):
+    if isinstance(scorer, str):
+        if scorer not in _SCORERS:
+            raise ValueError(f"scorer {scorer!r}: one of 'npmi', 'ratio', 'count'")
+        return _SCORERS[scorer]
+    return int(scorer)
 
 
 class jb_filter_rule(C.Structure):
@@ -372,6 +419,25 @@ def lib():
         L.jb_neardup_labels.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp]
         L.jb_neardup_sig.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      vp, vp, C.c_uint64, vp, vp, vp]
+        L.jb_colloc_table_bytes.restype = C.c_size_t
+        L.jb_colloc_table_bytes.argtypes = [C.c_uint64]
+        L.jb_colloc_work_bytes.restype = C.c_size_t
+        L.jb_colloc_work_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        L.jb_colloc_init_device.argtypes = [vp, vp, C.c_size_t, C.c_uint64, vp, C.c_uint32, vp]
+        L.jb_colloc_add_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint32, vp,
+                                           C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_size_t]
+        L.jb_colloc_score_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_int, C.c_uint64, C.c_float, vp, vp,
+                                             vp, vp, C.c_uint64, vp, vp]
+        L.jb_colloc_read.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_int, C.c_uint64, C.c_float, C.c_uint64, vp,
+                                     C.POINTER(jb_colloc_result)]
+        L.jb_colloc_result_free.argtypes = [C.POINTER(jb_colloc_result)]
+        L.jb_colloc_result_free.restype = None
+        L.jb_colloc_count.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp,
+                                      C.c_uint64, vp, C.c_uint32, C.POINTER(jb_colloc_result)]
+        L.jb_colloc_score.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_int, C.c_uint64, C.c_float,
+                                      C.c_uint64, C.POINTER(jb_colloc_result)]
+        L.jb_colloc_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp,
+                                      C.c_uint32]
         L.jb_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
         L.jb_device_free.argtypes = [vp, vp]
         L.jb_device_free.restype = None
@@ -534,6 +600,8 @@ class Vocab:
 
 class Tokenizer:
     """jieba-go Tokenizer over the MI355X path."""
+
+    _vocab_keys = None  # the attached vocabulary's keys by id (set_vocab)
 
     def __init__(self, cfg):
         h = C.c_void_p()
@@ -780,11 +848,15 @@ class Tokenizer:
         any earlier one.  None removes it; an empty list attaches an empty vocabulary."""
         if keys is None and packed is None:
             _check(lib().jb_vocab_set(self.h, None, None, 0))
+            self._vocab_keys = None
             return
         buf, off = packed if packed is not None else pack_keys(keys)
         buf = np.ascontiguousarray(buf, np.uint8)
         off = np.ascontiguousarray(off, np.uint64)
         _check(lib().jb_vocab_set(self.h, buf.ctypes.data, off.ctypes.data, len(off) - 1))
+        # (the keys by id, for the calls that name ids: collocations, find_new_words)
+        raw = bytes(buf[:int(off[-1])])
+        self._vocab_keys = [raw[int(off[i]):int(off[i + 1])] for i in range(len(off) - 1)]
 
     @property
     def vocab_size(self):
@@ -1465,6 +1537,108 @@ class Tokenizer:
         label = neardup_labels(pair_off, pair_doc)
         return label, label == np.arange(len(label), dtype=np.uint32)
 
+    # -- collocations: adjacent-pair counts and new-word scores ---------------
+    def colloc_init_device(self, d_table, ntable, nslots, d_uni, nuni, stream_ptr=0):
+        """jb_colloc_init_device: an empty pair table of nslots slots (a power of two >= 8) in the device buffer
+        d_table (ntable >= colloc_table_bytes(nslots) bytes, 32-byte aligned), and d_uni (u64[nuni]) zeroed."""
+        _check(lib().jb_colloc_init_device(self.h, C.c_void_p(d_table), ntable, nslots, C.c_void_p(d_uni), nuni,
+                                           C.c_void_p(stream_ptr)))
+
+    def colloc_add_device(self, d_table, ntable, d_uni, nuni, d_ids, ids_cap, d_doc_tok, d_ntok, ndocs, d_keep, nkeep,
+                          flags, d_start, d_end, d_work, nwork, stream_ptr=0):
+        """jb_colloc_add_device over raw device pointers: the unigrams and adjacent pairs of the tokens
+        k < min(*d_ntok, ids_cap) added to d_uni and the table; queued on the stream.  d_work:
+        colloc_work_bytes(ids_cap, ndocs) bytes."""
+        _check(lib().jb_colloc_add_device(self.h, C.c_void_p(d_table), ntable, C.c_void_p(d_uni), nuni,
+                                          C.c_void_p(d_ids), ids_cap, C.c_void_p(d_doc_tok), C.c_void_p(d_ntok), ndocs,
+                                          C.c_void_p(d_keep), nkeep, flags, C.c_void_p(d_start), C.c_void_p(d_end),
+                                          C.c_void_p(stream_ptr), C.c_void_p(d_work), nwork))
+
+    def colloc_score_device(self, d_table, ntable, d_uni, nuni, scorer, min_count, threshold, d_cand_a, d_cand_b,
+                            d_cand_cnt, d_cand_score, ccap, d_ncand, stream_ptr=0):
+        """jb_colloc_score_device over raw device pointers: the table's candidates under a scorer ("npmi", "ratio",
+        "count" or a JB_COLLOC_* value) into arrays of capacity ccap, *d_ncand the complete count; queued."""
+        _check(lib().jb_colloc_score_device(self.h, C.c_void_p(d_table), ntable, C.c_void_p(d_uni), nuni,
+                                            _scorer(scorer), min_count, threshold, C.c_void_p(d_cand_a),
+                                            C.c_void_p(d_cand_b), C.c_void_p(d_cand_cnt), C.c_void_p(d_cand_score), ccap,
+                                            C.c_void_p(d_ncand), C.c_void_p(stream_ptr)))
+
+    def colloc_read(self, d_table, ntable, d_uni, nuni, scorer="npmi", min_count=5, threshold=0.5, topn=0,
+                    stream_ptr=0):
+        """jb_colloc_read: synchronise the stream, score on the device and read the candidates back sorted: a
+        CollocResult.  The table stays as it is."""
+        r = jb_colloc_result()
+        _check(lib().jb_colloc_read(self.h, C.c_void_p(d_table), ntable, C.c_void_p(d_uni), nuni, _scorer(scorer),
+                                    min_count, threshold, topn, C.c_void_p(stream_ptr), C.byref(r)))
+        try:
+            return CollocResult(r)
+        finally:
+            lib().jb_colloc_result_free(C.byref(r))
+
+    def colloc_batch(self, buf, doc_off, hmm, d_table, ntable, d_uni, nuni, keep=None, flags=0):
+        """jb_colloc_batch: a host batch cut in plain mode, numbered by the attached vocabulary and added to the
+        table and d_uni; the batch filter applies when one is set."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        keep = np.zeros(0, np.uint8) if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+        _check(lib().jb_colloc_batch(self.h, buf.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1, int(hmm),
+                                     keep.ctypes.data if len(keep) else None, len(keep), flags, C.c_void_p(d_table),
+                                     ntable, C.c_void_p(d_uni), nuni))
+
+    def _collocations(self, batches, scorer, min_count, threshold, topn, contiguous, keep, hmm, nslots):
+        nuni = self.vocab_size
+        if nuni <= 0:
+            raise JbError(JB_EINVAL, "collocations: no vocabulary attached (set_vocab, fit_vocab)")
+        ntable = colloc_table_bytes(nslots)
+        d_table, d_uni = C.c_void_p(), C.c_void_p()
+        _check(lib().jb_device_alloc(self.h, ntable, C.byref(d_table)))
+        try:
+            _check(lib().jb_device_alloc(self.h, nuni * 8, C.byref(d_uni)))
+            self.colloc_init_device(d_table.value, ntable, nslots, d_uni.value, nuni)
+            for batch in batches:
+                docs = [_b(t) for t in batch]
+                if not docs:
+                    continue
+                off = np.zeros(len(docs) + 1, np.uint64)
+                off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+                self.colloc_batch(np.frombuffer(b"".join(docs) + b"\0", np.uint8), off, hmm, d_table.value, ntable,
+                                  d_uni.value, nuni, keep, JB_COLLOC_CONTIG if contiguous else 0)
+            r = self.colloc_read(d_table.value, ntable, d_uni.value, nuni, scorer, min_count, threshold, topn)
+        finally:
+            lib().jb_device_free(self.h, d_uni)
+            lib().jb_device_free(self.h, d_table)
+        if r.dropped:
+            raise JbError(JB_ELIMIT, f"collocations: {r.dropped} pairs dropped for lack of room: pairs are missing "
+                                     f"(raise nslots)")
+        return r
+
+    def collocations(self, batches, scorer="npmi", min_count=5, threshold=0.5, topn=0, contiguous=False, keep=None,
+                     hmm=True, nslots=1 << 24):
+        """The collocations of a corpus given as an iterable of batches, each a list of documents (str / bytes):
+        a list of (key_a, key_b, count, score), best first, the keys (bytes) those of the attached vocabulary
+        (set_vocab, fit_vocab), counted and scored on the GPU.  contiguous counts a pair only when the two tokens
+        touch in the text; keep (u8 per id) limits the pairs to kept ids; nslots sizes the pair table (new pairs
+        are accepted while fewer than half are taken).  JbError when pairs were dropped for lack of room."""
+        r = self._collocations(batches, scorer, min_count, threshold, topn, contiguous, keep, hmm, nslots)
+        keys = self._vocab_keys
+        return [(keys[int(a)], keys[int(b)], int(c), float(s)) for a, b, c, s in zip(r.a, r.b, r.count, r.score)]
+
+    def find_new_words(self, batches, scorer="npmi", min_count=5, threshold=0.5, topn=0, hmm=False, nslots=1 << 24):
+        """collocations with contiguous=True over the vocabulary keys whose every rune is Han: the concatenations
+        a+b (str) the dictionary lacks (dict_get absent or 0), best first, ready for AddWord.  hmm is off by
+        default: the HMM itself glues runs of single runes, which hides the pairs this looks for."""
+        keep = np.array([1 if is_han_key(k) else 0 for k in self._vocab_keys or []], np.uint8)
+        out, seen = [], set()
+        for a, b, _, _ in self.collocations(batches, scorer, min_count, threshold, 0, True, keep, hmm, nslots):
+            w = (a + b).decode("utf-8")
+            if w in seen or self.dict_get(w):
+                continue
+            seen.add(w)
+            out.append(w)
+            if topn and len(out) == topn:
+                break
+        return out
+
     def device_status(self, stream_ptr=0):
         """jb_device_status: raises JbError when the last device pipeline hit an error."""
         _check(lib().jb_device_status(self.h, C.c_void_p(stream_ptr)))
@@ -1956,3 +2130,72 @@ def textrank(ids, doc_tok, term_id, term_off, keep, span=5, iters=10, topk=20, n
                              ki.ctypes.data, ks.ctypes.data, kn.ctypes.data))
     shape = (nd, int(topk))
     return ki[:nd * topk].reshape(shape), ks[:nd * topk].reshape(shape), kn[:nd]
+
+
+def is_han_key(key):
+    """Is every rune of the key Han, by the class test jb_filter uses (jb_is_han's ranges)?"""
+    try:
+        t = _b(key).decode("utf-8")
+    except UnicodeDecodeError:
+        return False
+    return len(t) > 0 and all(_is_han(ord(ch)) for ch in t)
+
+
+# jb_is_han's ranges (jb_common.h: Unicode 13.0.0 Script=Han), the test jb_filter's class JB_TC_HAN uses
+_HAN_RANGES = ((0x2E80, 0x2E99), (0x2E9B, 0x2EF3), (0x2F00, 0x2FD5), (0x3005, 0x3005), (0x3007, 0x3007),
+               (0x3021, 0x3029), (0x3038, 0x303B), (0x3400, 0x4DBF), (0x4E00, 0x9FFC), (0xF900, 0xFA6D),
+               (0xFA70, 0xFAD9), (0x16FF0, 0x16FF1), (0x20000, 0x2A6DD), (0x2A700, 0x2B734), (0x2B740, 0x2B81D),
+               (0x2B820, 0x2CEA1), (0x2CEB0, 0x2EBE0), (0x2F800, 0x2FA1D), (0x30000, 0x3134A))
+
+
+def _is_han(r):
+    return any(lo <= r <= hi for lo, hi in _HAN_RANGES)
+
+
+def colloc_table_bytes(nslots):
+    """jb_colloc_table_bytes: the bytes of a pair table of nslots slots."""
+    return lib().jb_colloc_table_bytes(nslots)
+
+
+def colloc_work_bytes(max_tokens, ndocs):
+    """jb_colloc_work_bytes: the bytes of jb_colloc_add_device's work buffer."""
+    return lib().jb_colloc_work_bytes(max_tokens, ndocs)
+
+
+def colloc_count(ids, doc_tok, uni, keep=None, flags=0, starts=None, ends=None, ntok=None, ids_cap=None, nslots=0):
+    """jb_colloc_count, the rule of the add on host arrays (no GPU): uni (uint64, modified in place) gets the
+    unigrams, and a CollocResult holds every pair in the table sorted by key with the batch's totals."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    doc_tok = np.ascontiguousarray(doc_tok, dtype=np.uint64)
+    assert uni.dtype == np.uint64 and uni.flags.c_contiguous
+    keep = np.zeros(0, np.uint8) if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+    ids_cap = len(ids) if ids_cap is None else ids_cap
+    ntok = ids_cap if ntok is None else ntok
+    st = None if starts is None else np.ascontiguousarray(starts, dtype=np.uint32)
+    en = None if ends is None else np.ascontiguousarray(ends, dtype=np.uint32)
+    r = jb_colloc_result()
+    _check(lib().jb_colloc_count(ids.ctypes.data if len(ids) else None, ids_cap, doc_tok.ctypes.data, ntok,
+                                 len(doc_tok) - 1, keep.ctypes.data if len(keep) else None, len(keep), flags,
+                                 None if st is None else st.ctypes.data, None if en is None else en.ctypes.data, nslots,
+                                 uni.ctypes.data if len(uni) else None, len(uni), C.byref(r)))
+    try:
+        return CollocResult(r)
+    finally:
+        lib().jb_colloc_result_free(C.byref(r))
+
+
+def colloc_score(a, b, count, uni, N, scorer="npmi", min_count=5, threshold=0.5, topn=0, nuni=None):
+    """jb_colloc_score, the score rule on host arrays (no GPU): the candidates in the rule's order."""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    count = np.ascontiguousarray(count, dtype=np.uint64)
+    uni = np.ascontiguousarray(uni, dtype=np.uint64)
+    nuni = len(uni) if nuni is None else nuni
+    r = jb_colloc_result()
+    _check(lib().jb_colloc_score(a.ctypes.data if len(a) else None, b.ctypes.data if len(a) else None,
+                                 count.ctypes.data if len(a) else None, len(a), uni.ctypes.data if len(uni) else None, nuni,
+                                 N, _scorer(scorer), min_count, threshold, topn, C.byref(r)))
+    try:
+        return CollocResult(r)
+    finally:
+        lib().jb_colloc_result_free(C.byref(r))
