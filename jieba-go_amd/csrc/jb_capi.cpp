@@ -3,7 +3,8 @@
 // Argument checks, the context's lock, and one call into the layers below: the image builder
 // (jb_image.cpp), the devices (jb_device.cpp), host batches (jb_small.cpp, jb_hostbatch.cpp) and
 // the kernels' launch interface (jb_kernels.h).  The planners' entry points are in jb_plan.cpp,
-// jb_last_error in jb_err.cpp.  No segmentation happens on the CPU: without a usable HIP device
+// jb_last_error in jb_err.cpp, the host-text analytics calls (jb_*_batch, jb_cut_batch_join and its
+// like) in jb_batch.cpp.  No segmentation happens on the CPU: without a usable HIP device
 // every cut returns JB_EDEVICE.
 #include <stdio.h>
 #include <string.h>
@@ -227,10 +228,6 @@ extern "C" int jb_open(const jb_config* cfg, jb_ctx** out) {
     jb_config c = *cfg;
     c.nlog = 0;  // (jb_image_build applied the log table)
     return jb_open_image(img, &c, out);
-}
-
-namespace {
-void joined_drop_cache();  // (the page-locked block jb_joined_free keeps, below)
 }
 
 extern "C" void jb_close(jb_ctx* ctx) {
@@ -1152,237 +1149,6 @@ extern "C" int jb_textrank_device(jb_ctx* ctx, const uint32_t* d_ids, uint64_t i
 }
 
 // ---------------------------------------------------------------------------
-// host text in: jb_keywords_batch, jb_df_batch
-// ---------------------------------------------------------------------------
-namespace {
-
-// A part of one of the ctx's grow-only buffers, cut into 256-byte aligned pieces.
-struct Arena {
-    uint8_t* p = nullptr;
-    size_t off = 0;
-    void* take(size_t nbytes) {
-        void* r = p + off;
-        off += (nbytes + 255u) & ~(size_t)255u;
-        return r;
-    }
-};
-size_t r256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
-// ctx->kw_buf[which], grown to `need` bytes (under kw_mu).
-int kw_arena(jb_ctx* ctx, int which, size_t need, Arena* a) {
-    if (ctx->kw_cap[which] < need) {
-        dfree(ctx->kw_buf[which]);
-        ctx->kw_buf[which] = nullptr;
-        ctx->kw_cap[which] = 0;
-        HIPCHK(hipMalloc(&ctx->kw_buf[which], need));
-        ctx->kw_cap[which] = need;
-    }
-    *a = Arena{};
-    a->p = (uint8_t*)ctx->kw_buf[which];
-    return JB_OK;
-}
-
-// The batch filter's step between a host-batch call's cut and its own step (jb_batch_filter_set,
-// jb_cut_batch_filter; under kw_mu): jb_filter_device over the cut's span list, with its work buffer and the
-// filtered list in the ctx's buffer [9].  On return the caller's names for the span list (starts at *dse, ends
-// at *dse + *cap, *dtok, the count at *dcnt) are the filtered list's; (*dcnt)[1] is spare, as the cut's is, and
-// (*dcnt)[2 .. 6] are the statistics.  ntok is the cut's count.
-int batch_filter_step(jb_ctx* ctx, const char* who, const jb_filter_rule& rule, const uint8_t* dt, uint64_t nb,
-                      uint32_t ndocs, hipStream_t st, uint64_t ntok, uint32_t** dse, uint64_t* cap, uint64_t** dtok,
-                      uint64_t** dcnt) {
-    const uint64_t tcap = std::max<uint64_t>(std::min(ntok, *cap), 1);  // (kept tokens never exceed the cut's)
-    if (const int r = filter_args(who, nb, tcap, &rule, true)) return r;  // (the stop set is jb_filter_device's check)
-    const size_t nwork = jb_filter_work_bytes(tcap, ndocs), ndoc8 = ((size_t)ndocs + 1) * 8;
-    Arena f;
-    if (const int r = kw_arena(ctx, 9, r256(nwork) + r256(2 * tcap * 4) + r256(ndoc8) + r256(64), &f)) return r;
-    void* work = f.take(nwork);
-    uint32_t* ose = (uint32_t*)f.take(2 * tcap * 4);
-    uint64_t* otok = (uint64_t*)f.take(ndoc8);
-    uint64_t* ocnt = (uint64_t*)f.take(64);
-    if (const int r = jb_filter_device(ctx, dt, nb, *dse, *dse + *cap, *dtok, *dcnt, tcap, ndocs, &rule, st, ose, ose + tcap,
-                                       nullptr, tcap, otok, ocnt, ocnt + 2, work, nwork))
-        return r;
-    *dse = ose;
-    *cap = tcap;
-    *dtok = otok;
-    *dcnt = ocnt;
-    return JB_OK;
-}
-
-// What the chain leaves on the device for the call's last step.
-struct BatchCsr {
-    hipStream_t st;
-    const uint32_t *term_id, *term_cnt;  // tcap entries each
-    const uint64_t* term_off;            // ndocs + 1
-    const uint64_t* nterms;
-    uint64_t tcap;
-    const uint32_t* ids;      // tcap entries, in token order
-    const uint64_t* doc_tok;  // ndocs + 1
-    const uint64_t* ntok;
-};
-
-// The front of the host-text calls: plain Cut -> ids -> terms of one batch on a stream of the first
-// device, through the public entry points (each takes the ctx's lock for itself), in the ctx's buffers
-// [0] (sized by the batch's bytes, with `extra0` bytes for the caller behind the chain's own) and [1]
-// (sized by its token count).  `last(csr, extra)` queues the call's own step and its copies back; the
-// stream is synchronised after it.  `who` names the entry point in the messages.
-template <class Last>
-int batch_chain(jb_ctx* ctx, const char* who, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                size_t extra0, Last last) {
-    for (uint32_t k = 0; k < ndocs; k++)
-        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
-    const uint64_t nb = doc_off[ndocs] - doc_off[0];
-    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
-    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
-    int ordinal;
-    {
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        if (!ctx->vocab) return fail(JB_EINVAL, "%s: no vocabulary attached (jb_vocab_set)", who);
-        ordinal = ctx->devs[0]->ordinal;
-    }
-    if (ndocs == 0) return JB_OK;
-    HIPCHK(hipSetDevice(ordinal));
-    std::vector<uint64_t> rel;
-    try {
-        rel.resize((size_t)ndocs + 1);
-    } catch (const std::bad_alloc&) {
-        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
-    }
-    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
-    const uint64_t cap = std::max<uint64_t>(nb, 1);  // (a batch of n bytes has at most n tokens)
-    std::lock_guard<std::mutex> kg(ctx->kw_mu);
-    hipStream_t st = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
-        Arena a;
-        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 3 * r256(ndoc8) + r256(16) + r256(2 * cap * 4) + extra0, &a))) return rc;
-        uint8_t* dt = (uint8_t*)a.take(nb + 64);
-        uint64_t* doff = (uint64_t*)a.take(ndoc8);
-        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
-        uint64_t* dtoff = (uint64_t*)a.take(ndoc8);
-        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the token count, the term count)
-        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
-        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
-        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-        if ((rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt))) return rc;
-        if ((rc = jb_device_status(ctx, st))) return rc;  // (waits; the cut's errors, JB_EPANIC included)
-        // the token count sizes the rest: 28 bytes per token instead of per byte of text
-        uint64_t ntok = 0;
-        HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
-        const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);
-        const size_t nwork = terms_work_bytes(tcap, ndocs);
-        Arena b;
-        if ((rc = kw_arena(ctx, 1, r256(tcap * 4) + r256(2 * tcap * 4) + r256(nwork), &b))) return rc;
-        uint32_t* did = (uint32_t*)b.take(tcap * 4);
-        uint32_t* dterm = (uint32_t*)b.take(2 * tcap * 4);  // (term ids, term counts)
-        void* dwork = b.take(nwork);
-        if ((rc = jb_ids_device(ctx, dt, nb, dse, dse + cap, dcnt, tcap, st, did))) return rc;
-        if ((rc = jb_terms_device(ctx, did, tcap, dtok, dcnt, ndocs, st, dterm, dterm + tcap, tcap, dtoff, dcnt + 1,
-                                  dwork, nwork)))
-            return rc;
-        if ((rc = last(BatchCsr{st, dterm, dterm + tcap, dtoff, dcnt + 1, tcap, did, dtok, dcnt}, &a))) return rc;
-        HIPCHK(hipStreamSynchronize(st));
-        return JB_OK;
-    };
-    const int rc = run();
-    if (st) {
-        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
-        (void)hipStreamDestroy(st);
-    }
-    return rc;
-}
-
-}  // namespace
-
-// Host text in, keywords out: batch_chain, then jb_keywords_device and the records' way back.
-extern "C" int jb_keywords_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                                 const float* weights, uint32_t nweights, uint32_t topk, uint32_t* kw_id,
-                                 float* kw_score, uint32_t* kw_cnt, uint32_t* kw_n) {
-    // (the limits of topk come first: they need no ctx)
-    if (topk == 0) return fail(JB_EINVAL, "jb_keywords_batch: topk is 0");
-    if (topk > kKwMaxK) return fail(JB_ELIMIT, "jb_keywords_batch: topk %u (limit JB_KW_MAXK = %u)", topk, kKwMaxK);
-    if (!ctx || !doc_off || (nweights && !weights) || (ndocs && (!kw_id || !kw_score || !kw_cnt || !kw_n)))
-        return fail(JB_EINVAL, "jb_keywords_batch: null argument");
-    const size_t nrec = (size_t)ndocs * topk;
-    const size_t extra = r256((3 * nrec + ndocs) * 4) + r256(std::max<size_t>(nweights, 1) * 4);
-    return batch_chain(ctx, "jb_keywords_batch", text, doc_off, ndocs, hmm, extra, [&](const BatchCsr& c, Arena* a) -> int {
-        uint32_t* dkw = (uint32_t*)a->take((3 * nrec + ndocs) * 4);  // (ids, scores, counts, kw_n)
-        float* dw = (float*)a->take(std::max<size_t>(nweights, 1) * 4);
-        if (nweights) HIPCHK(hipMemcpyAsync(dw, weights, (size_t)nweights * 4, hipMemcpyHostToDevice, c.st));
-        if (const int rc = jb_keywords_device(ctx, c.term_id, c.term_cnt, c.term_off, ndocs, c.tcap, dw, nweights, topk,
-                                              c.st, dkw, (float*)(dkw + nrec), dkw + 2 * nrec, dkw + 3 * nrec))
-            return rc;
-        HIPCHK(hipMemcpyAsync(kw_id, dkw, nrec * 4, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipMemcpyAsync(kw_score, dkw + nrec, nrec * 4, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipMemcpyAsync(kw_cnt, dkw + 2 * nrec, nrec * 4, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipMemcpyAsync(kw_n, dkw + 3 * nrec, (size_t)ndocs * 4, hipMemcpyDeviceToHost, c.st));
-        return JB_OK;
-    });
-}
-
-// Host text in, the batch's document frequencies added to df: batch_chain, then jb_df_device into the
-// ctx's third buffer and ndf counters back.
-extern "C" int jb_df_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                           uint32_t* df, uint32_t ndf) {
-    if (!ctx) return fail(JB_EINVAL, "jb_df_batch: null ctx");
-    if (!doc_off) return fail(JB_EINVAL, "jb_df_batch: null doc_off");
-    if (ndf && !df) return fail(JB_EINVAL, "jb_df_batch: null df");
-    std::vector<uint32_t> got;
-    try {
-        got.resize(ndf);
-    } catch (const std::bad_alloc&) {
-        return fail(JB_ENOMEM, "out of host memory for %u counters", ndf);
-    }
-    bool ran = false;
-    const int rc = batch_chain(ctx, "jb_df_batch", text, doc_off, ndocs, hmm, 0, [&](const BatchCsr& c, Arena*) -> int {
-        if (ndf == 0) return JB_OK;
-        Arena b;
-        if (const int r = kw_arena(ctx, 2, (size_t)ndf * 4, &b)) return r;
-        uint32_t* ddf = (uint32_t*)b.p;
-        HIPCHK(hipMemsetAsync(ddf, 0, (size_t)ndf * 4, c.st));
-        if (const int r = jb_df_device(ctx, c.term_id, c.nterms, c.tcap, ddf, ndf, c.st)) return r;
-        HIPCHK(hipMemcpyAsync(got.data(), ddf, (size_t)ndf * 4, hipMemcpyDeviceToHost, c.st));
-        ran = true;
-        return JB_OK;
-    });
-    if (rc == JB_OK && ran)
-        for (uint32_t k = 0; k < ndf; k++) df[k] += got[k];
-    return rc;
-}
-
-// Host text in, TextRank keywords out: batch_chain, then jb_textrank_device with the keep mask, the
-// records and the work buffer in the ctx's fourth buffer, and the records' way back.
-extern "C" int jb_textrank_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                                 const uint8_t* keep, uint32_t nkeep, uint32_t span, uint32_t iters, uint32_t topk,
-                                 uint32_t* kw_id, float* kw_score, uint32_t* kw_n) {
-    if (const int rc = textrank_args("jb_textrank_batch", 0, 0, span, iters, topk)) return rc;
-    if (!ctx || !doc_off || (nkeep && !keep) || (ndocs && (!kw_id || !kw_score || !kw_n)))
-        return fail(JB_EINVAL, "jb_textrank_batch: null argument");
-    const size_t nrec = (size_t)ndocs * topk;
-    return batch_chain(ctx, "jb_textrank_batch", text, doc_off, ndocs, hmm, 0, [&](const BatchCsr& c, Arena*) -> int {
-        const size_t nwork = textrank_work_bytes(c.tcap, c.tcap, ndocs);
-        Arena b;
-        if (const int r = kw_arena(ctx, 3, r256(std::max<size_t>(nkeep, 1)) + r256((2 * nrec + ndocs) * 4) + r256(nwork), &b))
-            return r;
-        uint8_t* dkeep = (uint8_t*)b.take(std::max<size_t>(nkeep, 1));
-        uint32_t* dkw = (uint32_t*)b.take((2 * nrec + ndocs) * 4);  // (ids, scores, kw_n)
-        void* dwork = b.take(nwork);
-        if (nkeep) HIPCHK(hipMemcpyAsync(dkeep, keep, nkeep, hipMemcpyHostToDevice, c.st));
-        if (const int r = jb_textrank_device(ctx, c.ids, c.tcap, c.doc_tok, c.ntok, ndocs, c.term_id, c.term_off, c.tcap,
-                                             dkeep, nkeep, span, iters, topk, c.st, dkw, (float*)(dkw + nrec),
-                                             dkw + 2 * nrec, dwork, nwork))
-            return r;
-        HIPCHK(hipMemcpyAsync(kw_id, dkw, nrec * 4, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipMemcpyAsync(kw_score, dkw + nrec, nrec * 4, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipMemcpyAsync(kw_n, dkw + 2 * nrec, (size_t)ndocs * 4, hipMemcpyDeviceToHost, c.st));
-        return JB_OK;
-    });
-}
-
-// ---------------------------------------------------------------------------
 // joined text (jb_join.hip; the host rule, jb_join, is jb_join.cpp)
 // ---------------------------------------------------------------------------
 static_assert(JB_JOIN_TILE == kJoinTile && JB_JOIN_LONG == kJoinLong && JB_JOIN_MAXSEP == kJoinMaxSep,
@@ -1419,180 +1185,6 @@ extern "C" int jb_join_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nbyte
     HIPCHK(run_join(d_text, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, sep, seplen, term, termlen, staged, d_out,
                     out_cap, d_out_doc_off, d_nout, d_work, s, nullptr));
     return JB_OK;
-}
-
-// jb_joined::text is page-locked, so that the copy back runs at the link's rate and touches no fresh page.
-// Pinning a gigabyte costs far more than the whole call, so jb_joined_free keeps the largest block it was
-// handed (one per process) and the next jb_cut_batch_join takes it; jb_close lets it go.  A block starts
-// with a header that holds its capacity.
-namespace {
-constexpr size_t kJoinedHdr = 64;
-std::mutex g_joined_mu;
-uint8_t* g_joined_block = nullptr;  // (under g_joined_mu)
-size_t g_joined_cap = 0;
-
-int joined_alloc(uint64_t nbytes, uint8_t** text) {
-    uint8_t* b = nullptr;
-    {
-        std::lock_guard<std::mutex> g(g_joined_mu);
-        if (g_joined_block && g_joined_cap >= nbytes) {
-            b = g_joined_block;
-            g_joined_block = nullptr;
-        }
-    }
-    if (!b) {
-        HIPCHK(hipHostMalloc(&b, kJoinedHdr + std::max<uint64_t>(nbytes, 1), hipHostMallocDefault));
-        *(uint64_t*)b = nbytes;
-    }
-    *text = b + kJoinedHdr;
-    return JB_OK;
-}
-
-void joined_release(uint8_t* text) {
-    if (!text) return;
-    uint8_t* b = text - kJoinedHdr;
-    {
-        std::lock_guard<std::mutex> g(g_joined_mu);
-        if (!g_joined_block || g_joined_cap < *(uint64_t*)b) {
-            std::swap(b, g_joined_block);
-            g_joined_cap = *(uint64_t*)g_joined_block;
-        }
-    }
-    hfree(b);  // (the smaller of the two, or nothing)
-}
-
-void joined_drop_cache() {
-    uint8_t* b;
-    {
-        std::lock_guard<std::mutex> g(g_joined_mu);
-        b = g_joined_block;
-        g_joined_block = nullptr;
-        g_joined_cap = 0;
-    }
-    hfree(b);
-}
-}  // namespace
-
-extern "C" void jb_joined_free(jb_joined* j) {
-    if (!j) return;
-    joined_release(j->text);
-    free(j->doc_off);
-    memset(j, 0, sizeof *j);
-}
-
-// Host text in, joined text out: the cut of `mode` into the ctx's buffers [0] (and, when full mode's list
-// is longer than the batch has bytes, [1]), jb_join_device into [4] with its work buffer and offsets in
-// [5], and nout, the offsets and the nout bytes back.  The join runs again when its output was larger
-// than [4] had room for.
-extern "C" int jb_cut_batch_join(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                                 int mode, const uint8_t* sep, uint32_t seplen, const uint8_t* term, uint32_t termlen,
-                                 jb_joined* out) {
-    const char* who = "jb_cut_batch_join";
-    if (!ctx || !doc_off || !out) return fail(JB_EINVAL, "%s: null argument", who);
-    memset(out, 0, sizeof *out);
-    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
-        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
-    for (uint32_t k = 0; k < ndocs; k++)
-        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
-    const uint64_t nb = doc_off[ndocs] - doc_off[0];
-    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
-    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
-    if (const int rc = join_args(who, nb, 0, sep, seplen, term, termlen)) return rc;
-    int ordinal;
-    {
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        ordinal = ctx->devs[0]->ordinal;
-    }
-    out->doc_off = (uint64_t*)calloc((size_t)ndocs + 1, 8);
-    if (!out->doc_off) return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
-    out->ndocs = ndocs;
-    if (ndocs == 0) return JB_OK;
-    HIPCHK(hipSetDevice(ordinal));
-    std::vector<uint64_t> rel;
-    try {
-        rel.resize((size_t)ndocs + 1);
-    } catch (const std::bad_alloc&) {
-        jb_joined_free(out);
-        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
-    }
-    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
-    uint64_t cap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
-    std::lock_guard<std::mutex> kg(ctx->kw_mu);
-    hipStream_t st = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
-        Arena a;
-        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * cap * 4), &a))) return rc;
-        uint8_t* dt = (uint8_t*)a.take(nb + 64);
-        uint64_t* doff = (uint64_t*)a.take(ndoc8);
-        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
-        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the span count, the output's byte count)
-        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
-        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
-        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-        uint64_t ntok = 0;
-        for (int pass = 0;; pass++) {
-            if (mode == JB_MODE_CUT)
-                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
-            else if (mode == JB_MODE_SEARCH)
-                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
-            else
-                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + cap, cap, dtok, dcnt);
-            if (rc) return rc;
-            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
-            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
-            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > cap && pass == 0) {
-                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
-                cap = ntok;
-                Arena b;
-                if ((rc = kw_arena(ctx, 1, r256(2 * cap * 4), &b))) return rc;
-                dse = (uint32_t*)b.take(2 * cap * 4);
-                continue;
-            }
-            if (rc) return rc;
-            break;
-        }
-        if (ctx->bfilter_on &&
-            (rc = batch_filter_step(ctx, who, ctx->bfilter, dt, nb, ndocs, st, ntok, &dse, &cap, &dtok, &dcnt)))
-            return rc;
-        if (const int r = join_args(who, nb, cap, sep, seplen, term, termlen)) return r;
-        const size_t nwork = join_work_bytes(cap, ndocs);
-        Arena w;
-        if ((rc = kw_arena(ctx, 5, r256(nwork) + r256(ndoc8), &w))) return rc;
-        void* dwork = w.take(nwork);
-        uint64_t* dooff = (uint64_t*)w.take(ndoc8);
-        // a first guess at the output's size: the text (plain mode without replaced bytes gives less), a
-        // separator per token and a terminator per document
-        uint64_t ocap = std::max<uint64_t>(ctx->kw_cap[4], nb + std::min(ntok, cap) * seplen + (uint64_t)ndocs * termlen + 256);
-        uint64_t nout = 0;
-        for (int pass = 0; pass < 2; pass++) {
-            Arena o;
-            if ((rc = kw_arena(ctx, 4, ocap, &o))) return rc;
-            if ((rc = jb_join_device(ctx, dt, nb, dse, dse + cap, dtok, dcnt, cap, ndocs, sep, seplen, term, termlen, st,
-                                     o.p, ocap, dooff, dcnt + 1, dwork, nwork)))
-                return rc;
-            HIPCHK(hipMemcpyAsync(&nout, dcnt + 1, 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (nout <= ocap) break;
-            ocap = nout;  // (replaced bytes or overlapping spans: the complete size is known now)
-        }
-        if ((rc = joined_alloc(nout, &out->text))) return rc;
-        out->nbytes = nout;
-        if (nout) HIPCHK(hipMemcpyAsync(out->text, ctx->kw_buf[4], nout, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(out->doc_off, dooff, ndoc8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        return JB_OK;
-    };
-    const int rc = run();
-    if (st) {
-        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
-        (void)hipStreamDestroy(st);
-    }
-    if (rc) jb_joined_free(out);
-    return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -1633,130 +1225,9 @@ extern "C" int jb_charspans_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t 
     return JB_OK;
 }
 
-// Host text in, character spans out: the cut of `mode` into the ctx's buffers [0] (and, when full mode's
-// list is longer than the batch has bytes, [1]), jb_charspans_device in place on the span arrays with its
-// work buffer and doc_units in [6], and the count, the converted spans, doc_tok and doc_units back.
-extern "C" int jb_cut_batch_charspans(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                                      int mode, int unit, uint32_t* cstart, uint32_t* cend, uint64_t cap,
-                                      uint64_t* doc_tok, uint64_t* ntokens, uint32_t* doc_units) {
-    const char* who = "jb_cut_batch_charspans";
-    if (!ctx || !doc_off || !doc_tok || !ntokens || (cap && (!cstart || !cend)) || (ndocs && !doc_units))
-        return fail(JB_EINVAL, "%s: null argument", who);
-    *ntokens = 0;
-    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
-        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
-    for (uint32_t k = 0; k < ndocs; k++)
-        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
-    const uint64_t nb = doc_off[ndocs] - doc_off[0];
-    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
-    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
-    if (const int rc = charspans_args(who, nb, 0, unit)) return rc;
-    if (ndocs == 0) {
-        doc_tok[0] = 0;
-        return JB_OK;
-    }
-    int ordinal;
-    {
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        ordinal = ctx->devs[0]->ordinal;
-    }
-    HIPCHK(hipSetDevice(ordinal));
-    std::vector<uint64_t> rel;
-    try {
-        rel.resize((size_t)ndocs + 1);
-    } catch (const std::bad_alloc&) {
-        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
-    }
-    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
-    uint64_t dcap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
-    std::lock_guard<std::mutex> kg(ctx->kw_mu);
-    hipStream_t st = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
-        Arena a;
-        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * dcap * 4), &a))) return rc;
-        uint8_t* dt = (uint8_t*)a.take(nb + 64);
-        uint64_t* doff = (uint64_t*)a.take(ndoc8);
-        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
-        uint64_t* dcnt = (uint64_t*)a.take(16);            // (the span count)
-        uint32_t* dse = (uint32_t*)a.take(2 * dcap * 4);  // (starts, ends)
-        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
-        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-        uint64_t ntok = 0;
-        for (int pass = 0;; pass++) {
-            if (mode == JB_MODE_CUT)
-                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + dcap, dcap, dtok, dcnt);
-            else if (mode == JB_MODE_SEARCH)
-                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + dcap, dcap, dtok, dcnt);
-            else
-                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + dcap, dcap, dtok, dcnt);
-            if (rc) return rc;
-            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
-            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
-            if ((rc == JB_OK || (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > dcap)) && ntok > cap) {
-                // the caller's arrays are too small: say so before a regrow and a second cut
-                *ntokens = ntok;
-                return fail(JB_ELIMIT, "%llu tokens do not fit the %llu-token output arrays", (unsigned long long)ntok,
-                            (unsigned long long)cap);
-            }
-            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > dcap && pass == 0) {
-                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
-                dcap = ntok;
-                Arena b;
-                if ((rc = kw_arena(ctx, 1, r256(2 * dcap * 4), &b))) return rc;
-                dse = (uint32_t*)b.take(2 * dcap * 4);
-                continue;
-            }
-            if (rc) return rc;
-            break;
-        }
-        *ntokens = ntok;
-        if (const int r = charspans_args(who, nb, dcap, unit)) return r;
-        const size_t nwork = charspans_work_bytes(nb, ndocs);
-        Arena w;
-        if ((rc = kw_arena(ctx, 6, r256(nwork) + r256((size_t)ndocs * 4), &w))) return rc;
-        void* dwork = w.take(nwork);
-        uint32_t* dunits = (uint32_t*)w.take((size_t)ndocs * 4);
-        if ((rc = jb_charspans_device(ctx, dt, nb, doff, ndocs, dse, dse + dcap, dtok, dcnt, dcap, unit, st, dse,
-                                      dse + dcap, dunits, dwork, nwork)))
-            return rc;
-        if (ntok) {
-            HIPCHK(hipMemcpyAsync(cstart, dse, ntok * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(cend, dse + dcap, ntok * 4, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipMemcpyAsync(doc_tok, dtok, ndoc8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(doc_units, dunits, (size_t)ndocs * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        return JB_OK;
-    };
-    const int rc = run();
-    if (st) {
-        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
-        (void)hipStreamDestroy(st);
-    }
-    return rc;
-}
-
 // ---------------------------------------------------------------------------
 // word counts (jb_wc.hip; the host rule, jb_wc_count, the reader and the size helpers are jb_wc.cpp)
 // ---------------------------------------------------------------------------
-namespace {
-
-// What every call that is handed a table checks: JB_OK, or JB_EINVAL with the thread's message set.
-int wc_table_args(const char* who, const void* d_table, size_t ntable) {
-    if (!d_table) return fail(JB_EINVAL, "%s: null table", who);
-    if (((uintptr_t)d_table & 31u) != 0) return fail(JB_EINVAL, "%s: d_table must be 32-byte aligned", who);
-    if (ntable < jb_wc_bytes(JB_WC_MIN_SLOTS, 0))
-        return fail(JB_EINVAL, "%s: a table buffer of %llu bytes, the smallest table has %llu", who,
-                    (unsigned long long)ntable, (unsigned long long)jb_wc_bytes(JB_WC_MIN_SLOTS, 0));
-    return JB_OK;
-}
-
-}  // namespace
-
 extern "C" int jb_device_alloc(jb_ctx* ctx, size_t n, void** p) {
     if (!ctx || !p) return fail(JB_EINVAL, "jb_device_alloc: null argument");
     *p = nullptr;
@@ -1860,92 +1331,6 @@ extern "C" int jb_wc_read(jb_ctx* ctx, const void* d_table, size_t ntable, void*
     return rc;
 }
 
-// Host text in, the batch's tokens into the table: the cut of `mode` into the ctx's buffers [0] (and, when
-// full mode's list is longer than the batch has bytes, [1]), then jb_wc_add_device with its work buffer in [7].
-extern "C" int jb_wc_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm, int mode,
-                           void* d_table, size_t ntable) {
-    const char* who = "jb_wc_batch";
-    if (!ctx || !doc_off) return fail(JB_EINVAL, "%s: null argument", who);
-    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
-        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
-    if (const int rc = wc_table_args(who, d_table, ntable)) return rc;
-    for (uint32_t k = 0; k < ndocs; k++)
-        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
-    const uint64_t nb = doc_off[ndocs] - doc_off[0];
-    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
-    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
-    int ordinal;
-    {
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        ordinal = ctx->devs[0]->ordinal;
-    }
-    if (ndocs == 0) return JB_OK;
-    HIPCHK(hipSetDevice(ordinal));
-    std::vector<uint64_t> rel;
-    try {
-        rel.resize((size_t)ndocs + 1);
-    } catch (const std::bad_alloc&) {
-        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
-    }
-    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
-    uint64_t cap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
-    std::lock_guard<std::mutex> kg(ctx->kw_mu);
-    hipStream_t st = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
-        Arena a;
-        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * cap * 4), &a))) return rc;
-        uint8_t* dt = (uint8_t*)a.take(nb + 64);
-        uint64_t* doff = (uint64_t*)a.take(ndoc8);
-        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
-        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the span count)
-        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
-        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
-        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-        uint64_t ntok = 0;
-        for (int pass = 0;; pass++) {
-            if (mode == JB_MODE_CUT)
-                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
-            else if (mode == JB_MODE_SEARCH)
-                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
-            else
-                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + cap, cap, dtok, dcnt);
-            if (rc) return rc;
-            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
-            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
-            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > cap && pass == 0) {
-                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
-                cap = ntok;
-                Arena b;
-                if ((rc = kw_arena(ctx, 1, r256(2 * cap * 4), &b))) return rc;
-                dse = (uint32_t*)b.take(2 * cap * 4);
-                continue;
-            }
-            if (rc) return rc;
-            break;
-        }
-        if (ctx->bfilter_on &&
-            (rc = batch_filter_step(ctx, who, ctx->bfilter, dt, nb, ndocs, st, ntok, &dse, &cap, &dtok, &dcnt)))
-            return rc;
-        const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);  // (the work buffer follows the token count)
-        const size_t nwork = jb_wc_work_bytes(tcap);
-        Arena w;
-        if ((rc = kw_arena(ctx, 7, nwork, &w))) return rc;
-        if ((rc = jb_wc_add_device(ctx, d_table, ntable, dt, nb, dse, dse + cap, dcnt, tcap, st, w.p, nwork))) return rc;
-        HIPCHK(hipStreamSynchronize(st));
-        return JB_OK;
-    };
-    const int rc = run();
-    if (st) {
-        (void)hipStreamSynchronize(st);  // (the copy from the caller's memory may be in flight)
-        (void)hipStreamDestroy(st);
-    }
-    return rc;
-}
-
 // ---------------------------------------------------------------------------
 // MinHash signatures (jb_minhash.hip; the host rule, jb_minhash, jb_minhash_params, jb_minhash_bands and the
 // size helper are jb_minhash.cpp)
@@ -2003,101 +1388,6 @@ extern "C" int jb_minhash_bands_device(jb_ctx* ctx, const uint32_t* d_sig, const
     return JB_OK;
 }
 
-// Host text in, signatures out: the cut of `mode` into the ctx's buffers [0] (and, when full mode's list is
-// longer than the batch has bytes, [1]), then jb_minhash_device with its work buffer, sig and doc_n in [8];
-// only sig and doc_n come back.
-extern "C" int jb_minhash_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                                int mode, uint32_t n, uint32_t K, uint64_t seed, uint32_t* sig, uint32_t* doc_n) {
-    const char* who = "jb_minhash_batch";
-    if (!ctx || !doc_off || (ndocs && (!sig || !doc_n))) return fail(JB_EINVAL, "%s: null argument", who);
-    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
-        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
-    if (const int rc = minhash_args(who, 0, 0, n, K)) return rc;
-    for (uint32_t k = 0; k < ndocs; k++)
-        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
-    const uint64_t nb = doc_off[ndocs] - doc_off[0];
-    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
-    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
-    int ordinal;
-    {
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        ordinal = ctx->devs[0]->ordinal;
-    }
-    if (ndocs == 0) return JB_OK;
-    HIPCHK(hipSetDevice(ordinal));
-    std::vector<uint64_t> rel;
-    try {
-        rel.resize((size_t)ndocs + 1);
-    } catch (const std::bad_alloc&) {
-        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
-    }
-    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
-    uint64_t cap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
-    std::lock_guard<std::mutex> kg(ctx->kw_mu);
-    hipStream_t st = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
-        Arena a;
-        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * cap * 4), &a))) return rc;
-        uint8_t* dt = (uint8_t*)a.take(nb + 64);
-        uint64_t* doff = (uint64_t*)a.take(ndoc8);
-        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
-        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the span count)
-        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
-        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
-        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-        uint64_t ntok = 0;
-        for (int pass = 0;; pass++) {
-            if (mode == JB_MODE_CUT)
-                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
-            else if (mode == JB_MODE_SEARCH)
-                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt);
-            else
-                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + cap, cap, dtok, dcnt);
-            if (rc) return rc;
-            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
-            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
-            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > cap && pass == 0) {
-                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
-                cap = ntok;
-                Arena b;
-                if ((rc = kw_arena(ctx, 1, r256(2 * cap * 4), &b))) return rc;
-                dse = (uint32_t*)b.take(2 * cap * 4);
-                continue;
-            }
-            if (rc) return rc;
-            break;
-        }
-        if (ctx->bfilter_on &&
-            (rc = batch_filter_step(ctx, who, ctx->bfilter, dt, nb, ndocs, st, ntok, &dse, &cap, &dtok, &dcnt)))
-            return rc;
-        const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);  // (the work buffer follows the token count)
-        if (const int r = minhash_args(who, nb, tcap, n, K)) return r;
-        const size_t nwork = jb_minhash_work_bytes(tcap, ndocs), nsig = (size_t)ndocs * K * 4, ndn = (size_t)ndocs * 4;
-        Arena w;
-        if ((rc = kw_arena(ctx, 8, r256(nwork) + r256(nsig) + r256(ndn), &w))) return rc;
-        void* dwork = w.take(nwork);
-        uint32_t* dsig = (uint32_t*)w.take(nsig);
-        uint32_t* ddn = (uint32_t*)w.take(ndn);
-        if ((rc = jb_minhash_device(ctx, dt, nb, dse, dse + cap, dtok, dcnt, tcap, ndocs, n, K, seed, st, dsig, ddn, dwork,
-                                    nwork)))
-            return rc;
-        HIPCHK(hipMemcpyAsync(sig, dsig, nsig, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(doc_n, ddn, ndn, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        return JB_OK;
-    };
-    const int rc = run();
-    if (st) {
-        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
-        (void)hipStreamDestroy(st);
-    }
-    return rc;
-}
-
 // ---------------------------------------------------------------------------
 // The token filter (jb_filter.hip; the host rule, jb_filter, the argument checks and the size helper are
 // jb_filter.cpp; the stop set, jb_stopwords_set, is with jb_vocab_set above)
@@ -2138,118 +1428,6 @@ extern "C" int jb_filter_device(jb_ctx* ctx, const uint8_t* d_text, uint64_t nby
     HIPCHK(run_filter(d_text, nbytes, d_start, d_end, d_doc_tok, d_ntok, cap, ndocs, *rule, ctx->dstop, d_out_start,
                       d_out_end, d_out_src, out_cap, d_out_doc_tok, d_out_ntok, d_stats, d_work, s, nullptr));
     return JB_OK;
-}
-
-extern "C" int jb_batch_filter_set(jb_ctx* ctx, const jb_filter_rule* rule) {
-    const char* who = "jb_batch_filter_set";
-    if (!ctx) return fail(JB_EINVAL, "%s: null ctx", who);
-    if (rule)  // (a stop set is asked for when a batch call runs the rule)
-        if (const int rc = filter_args(who, 0, 0, rule, true)) return rc;
-    std::lock_guard<std::mutex> kg(ctx->kw_mu);
-    ctx->bfilter_on = rule != nullptr;
-    ctx->bfilter = rule ? *rule : jb_filter_rule{0, 0, 0, 0};
-    return JB_OK;
-}
-
-// Host text in, the filtered spans out: the cut of `mode` into the ctx's buffers [0] (and, when full mode's
-// list is longer than the batch has bytes, [1]), the filter into [9], and the count, the statistics and, when
-// the count fits the caller's arrays, the spans and doc_tok back.
-extern "C" int jb_cut_batch_filter(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                                   int mode, const jb_filter_rule* rule, uint32_t* start, uint32_t* end, uint64_t cap,
-                                   uint64_t* doc_tok, uint64_t* ntokens, uint64_t* stats) {
-    const char* who = "jb_cut_batch_filter";
-    if (!ctx || !doc_off || !doc_tok || !ntokens || (cap && (!start || !end))) return fail(JB_EINVAL, "%s: null argument", who);
-    if (mode != JB_MODE_CUT && mode != JB_MODE_SEARCH && mode != JB_MODE_FULL)
-        return fail(JB_EINVAL, "%s: mode %d (JB_MODE_CUT, JB_MODE_SEARCH or JB_MODE_FULL)", who, mode);
-    if (const int rc = filter_args(who, 0, 0, rule, true)) return rc;
-    for (uint32_t k = 0; k < ndocs; k++)
-        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
-    const uint64_t nb = doc_off[ndocs] - doc_off[0];
-    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
-    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
-    int ordinal;
-    {
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        ordinal = ctx->devs[0]->ordinal;
-        if ((rule->flags & JB_FILTER_STOP) && !ctx->stopw)
-            return fail(JB_EINVAL, "%s: JB_FILTER_STOP without a stop set (jb_stopwords_set)", who);
-    }
-    *ntokens = 0;
-    if (stats) memset(stats, 0, 40);
-    if (ndocs == 0) {
-        doc_tok[0] = 0;
-        return JB_OK;
-    }
-    HIPCHK(hipSetDevice(ordinal));
-    std::vector<uint64_t> rel;
-    try {
-        rel.resize((size_t)ndocs + 1);
-    } catch (const std::bad_alloc&) {
-        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
-    }
-    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
-    uint64_t dcap = std::max<uint64_t>(nb, 1);  // (plain and search mode: a batch of n bytes has at most n spans)
-    std::lock_guard<std::mutex> kg(ctx->kw_mu);
-    hipStream_t st = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
-        Arena a;
-        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * dcap * 4), &a))) return rc;
-        uint8_t* dt = (uint8_t*)a.take(nb + 64);
-        uint64_t* doff = (uint64_t*)a.take(ndoc8);
-        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
-        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the span count)
-        uint32_t* dse = (uint32_t*)a.take(2 * dcap * 4);  // (starts, ends)
-        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
-        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-        uint64_t ntok = 0;
-        for (int pass = 0;; pass++) {
-            if (mode == JB_MODE_CUT)
-                rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + dcap, dcap, dtok, dcnt);
-            else if (mode == JB_MODE_SEARCH)
-                rc = jb_cut_device_search_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + dcap, dcap, dtok, dcnt);
-            else
-                rc = jb_cut_device_full_into(ctx, dt, nb, doff, ndocs, st, dse, dse + dcap, dcap, dtok, dcnt);
-            if (rc) return rc;
-            rc = jb_device_status(ctx, st);  // (waits; the cut's errors, JB_EPANIC included)
-            HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
-            if (rc == JB_ELIMIT && mode == JB_MODE_FULL && ntok > dcap && pass == 0) {
-                // full mode's list is longer than the arrays: larger ones in the buffer sized by tokens, once more
-                dcap = ntok;
-                Arena b;
-                if ((rc = kw_arena(ctx, 1, r256(2 * dcap * 4), &b))) return rc;
-                dse = (uint32_t*)b.take(2 * dcap * 4);
-                continue;
-            }
-            if (rc) return rc;
-            break;
-        }
-        if ((rc = batch_filter_step(ctx, who, *rule, dt, nb, ndocs, st, ntok, &dse, &dcap, &dtok, &dcnt))) return rc;
-        uint64_t head[7];  // (the count, a spare word, the statistics)
-        HIPCHK(hipMemcpyAsync(head, dcnt, sizeof head, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        *ntokens = head[0];
-        if (stats) memcpy(stats, head + 2, 40);
-        if (head[0] > cap)
-            return fail(JB_ELIMIT, "%s: %llu tokens, the arrays hold %llu", who, (unsigned long long)head[0],
-                        (unsigned long long)cap);
-        if (head[0]) {
-            HIPCHK(hipMemcpyAsync(start, dse, head[0] * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(end, dse + dcap, head[0] * 4, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipMemcpyAsync(doc_tok, dtok, ndoc8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        return JB_OK;
-    };
-    const int rc = run();
-    if (st) {
-        (void)hipStreamSynchronize(st);  // (copies from and to the caller's memory may be in flight)
-        (void)hipStreamDestroy(st);
-    }
-    return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -2293,58 +1471,6 @@ extern "C" int jb_postings_device(jb_ctx* ctx, const uint32_t* d_term_id, const 
     return JB_OK;
 }
 
-// Host text in, the batch's postings out: batch_chain, then jb_postings_device with its work buffer and its
-// outputs in the ctx's buffer [10]; post_off and the count come back first, the lists when they fit pcap.
-extern "C" int jb_postings_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                                 uint32_t doc_base, uint64_t pcap, uint64_t* post_off, uint32_t nids,
-                                 uint32_t* post_doc, uint32_t* post_tf, uint64_t* nposts, uint32_t* doc_len) {
-    const char* who = "jb_postings_batch";
-    if (!ctx || !doc_off || !post_off || !nposts || (pcap && (!post_doc || !post_tf)))
-        return fail(JB_EINVAL, "%s: null argument", who);
-    if (const int rc = postings_args(who, 0, ndocs, doc_base)) return rc;
-    bool ran = false;
-    const int rc = batch_chain(ctx, who, text, doc_off, ndocs, hmm, 0, [&](const BatchCsr& c, Arena*) -> int {
-        const size_t nwork = jb_postings_work_bytes(c.tcap, nids, ndocs), noff = ((size_t)nids + 1) * 8;
-        Arena b;
-        if (const int r = kw_arena(ctx, 10, r256(nwork) + r256(2 * c.tcap * 4) + r256(noff) + r256(8), &b)) return r;
-        void* work = b.take(nwork);
-        uint32_t* dpost = (uint32_t*)b.take(2 * c.tcap * 4);  // (documents, term frequencies)
-        uint64_t* dpoff = (uint64_t*)b.take(noff);
-        uint64_t* dn = (uint64_t*)b.take(8);
-        if (const int r = jb_postings_device(ctx, c.term_id, c.term_cnt, c.term_off, c.nterms, c.tcap, ndocs, nids,
-                                             doc_base, c.st, dpost, dpost + c.tcap, c.tcap, dpoff, dn, work, nwork))
-            return r;
-        std::vector<uint64_t> dtok;
-        if (doc_len) {
-            try {
-                dtok.resize((size_t)ndocs + 1);
-            } catch (const std::bad_alloc&) {
-                return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
-            }
-            HIPCHK(hipMemcpyAsync(dtok.data(), c.doc_tok, dtok.size() * 8, hipMemcpyDeviceToHost, c.st));
-        }
-        HIPCHK(hipMemcpyAsync(post_off, dpoff, noff, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipMemcpyAsync(nposts, dn, 8, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipStreamSynchronize(c.st));
-        ran = true;
-        if (*nposts > pcap)
-            return fail(JB_ELIMIT, "%s: %llu postings, the arrays hold %llu", who, (unsigned long long)*nposts,
-                        (unsigned long long)pcap);
-        if (doc_len)
-            for (uint32_t k = 0; k < ndocs; k++) doc_len[k] = (uint32_t)(dtok[k + 1] - dtok[k]);
-        if (*nposts) {
-            HIPCHK(hipMemcpyAsync(post_doc, dpost, *nposts * 4, hipMemcpyDeviceToHost, c.st));
-            HIPCHK(hipMemcpyAsync(post_tf, dpost + c.tcap, *nposts * 4, hipMemcpyDeviceToHost, c.st));
-        }
-        return JB_OK;
-    });
-    if (rc == JB_OK && !ran) {  // (no document: the empty index)
-        for (uint64_t t = 0; t <= nids; t++) post_off[t] = 0;
-        *nposts = 0;
-    }
-    return rc;
-}
-
 // ---------------------------------------------------------------------------
 // Collocations (jb_colloc.hip; the host rules, jb_colloc_count and jb_colloc_score, the argument checks, the
 // sort of a result and the size helpers are jb_colloc.cpp)
@@ -2353,18 +1479,6 @@ static_assert(JB_COLLOC_TILE == kClTile && JB_COLLOC_LDS == kClLds && JB_COLLOC_
               "the header's constants are the kernels'");
 
 namespace {
-
-// What every call that is handed a table checks: JB_OK, or JB_EINVAL with the thread's message set.
-int colloc_table_args(const char* who, const void* d_table, size_t ntable, const void* d_uni, uint32_t nuni) {
-    if (!d_table) return fail(JB_EINVAL, "%s: null table", who);
-    if (((uintptr_t)d_table & 31u) != 0) return fail(JB_EINVAL, "%s: d_table must be 32-byte aligned", who);
-    if (ntable < jb_cl_bytes(JB_CL_MIN_SLOTS))
-        return fail(JB_EINVAL, "%s: a table buffer of %llu bytes, the smallest table has %llu", who,
-                    (unsigned long long)ntable, (unsigned long long)jb_cl_bytes(JB_CL_MIN_SLOTS));
-    if (nuni && !d_uni) return fail(JB_EINVAL, "%s: null d_uni", who);
-    if (((uintptr_t)d_uni & 7u) != 0) return fail(JB_EINVAL, "%s: d_uni must be 8-byte aligned", who);
-    return JB_OK;
-}
 
 // The slots a buffer of ntable bytes has room for: the score pass's grid (the kernel reads the header itself).
 uint64_t colloc_room(size_t ntable) { return (ntable - JB_CL_HDR_BYTES) / JB_CL_SLOT_BYTES; }
@@ -2519,83 +1633,6 @@ extern "C" int jb_colloc_read(jb_ctx* ctx, const void* d_table, size_t ntable, c
     return JB_OK;
 }
 
-// Host text in, the batch's pairs and unigrams into the table and d_uni: the plain cut into the ctx's buffer [0],
-// the batch filter's step when one is set, then jb_ids_device and jb_colloc_add_device with the ids, the keep mask
-// and the work buffer in [13].
-extern "C" int jb_colloc_batch(jb_ctx* ctx, const uint8_t* text, const uint64_t* doc_off, uint32_t ndocs, int hmm,
-                               const uint8_t* keep, uint32_t nkeep, uint32_t flags, void* d_table, size_t ntable,
-                               uint64_t* d_uni, uint32_t nuni) {
-    const char* who = "jb_colloc_batch";
-    if (!ctx || !doc_off || (nkeep && !keep)) return fail(JB_EINVAL, "%s: null argument", who);
-    if (flags & ~JB_COLLOC_CONTIG) return fail(JB_EINVAL, "%s: flags %#x (JB_COLLOC_CONTIG)", who, flags);
-    if (const int rc = colloc_table_args(who, d_table, ntable, d_uni, nuni)) return rc;
-    for (uint32_t k = 0; k < ndocs; k++)
-        if (doc_off[k] > doc_off[k + 1]) return fail(JB_EINVAL, "%s: doc_off decreases at %u", who, k);
-    const uint64_t nb = doc_off[ndocs] - doc_off[0];
-    if (nb && !text) return fail(JB_EINVAL, "%s: null text", who);
-    if (nb >= (1ull << 31)) return fail(JB_ELIMIT, "batch of %llu bytes (limit 2 GiB)", (unsigned long long)nb);
-    int ordinal;
-    {
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        if (!ctx->vocab) return fail(JB_EINVAL, "%s: no vocabulary attached (jb_vocab_set)", who);
-        ordinal = ctx->devs[0]->ordinal;
-    }
-    if (ndocs == 0) return JB_OK;
-    HIPCHK(hipSetDevice(ordinal));
-    std::vector<uint64_t> rel;
-    try {
-        rel.resize((size_t)ndocs + 1);
-    } catch (const std::bad_alloc&) {
-        return fail(JB_ENOMEM, "out of host memory for %u document offsets", ndocs);
-    }
-    for (uint32_t k = 0; k <= ndocs; k++) rel[k] = doc_off[k] - doc_off[0];
-    uint64_t cap = std::max<uint64_t>(nb, 1);  // (a batch of n bytes has at most n tokens)
-    std::lock_guard<std::mutex> kg(ctx->kw_mu);
-    hipStream_t st = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        const size_t ndoc8 = ((size_t)ndocs + 1) * 8;
-        Arena a;
-        if ((rc = kw_arena(ctx, 0, r256(nb + 64) + 2 * r256(ndoc8) + r256(16) + r256(2 * cap * 4), &a))) return rc;
-        uint8_t* dt = (uint8_t*)a.take(nb + 64);
-        uint64_t* doff = (uint64_t*)a.take(ndoc8);
-        uint64_t* dtok = (uint64_t*)a.take(ndoc8);
-        uint64_t* dcnt = (uint64_t*)a.take(16);  // (the token count)
-        uint32_t* dse = (uint32_t*)a.take(2 * cap * 4);  // (starts, ends)
-        HIPCHK(hipMemsetAsync(dt + nb, 0, 64, st));
-        if (nb) HIPCHK(hipMemcpyAsync(dt, text + doc_off[0], nb, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(doff, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-        if ((rc = jb_cut_device_into(ctx, dt, nb, doff, ndocs, hmm, st, dse, dse + cap, cap, dtok, dcnt))) return rc;
-        if ((rc = jb_device_status(ctx, st))) return rc;  // (waits; the cut's errors, JB_EPANIC included)
-        uint64_t ntok = 0;
-        HIPCHK(hipMemcpy(&ntok, dcnt, 8, hipMemcpyDeviceToHost));
-        if (ctx->bfilter_on &&
-            (rc = batch_filter_step(ctx, who, ctx->bfilter, dt, nb, ndocs, st, ntok, &dse, &cap, &dtok, &dcnt)))
-            return rc;
-        const uint64_t tcap = std::max<uint64_t>(std::min(ntok, cap), 1);  // (the rest follows the token count)
-        const size_t nwork = jb_colloc_work_bytes(tcap, ndocs);
-        Arena b;
-        if ((rc = kw_arena(ctx, 13, r256(tcap * 4) + r256(std::max<size_t>(nkeep, 1)) + r256(nwork), &b))) return rc;
-        uint32_t* did = (uint32_t*)b.take(tcap * 4);
-        uint8_t* dkeep = (uint8_t*)b.take(std::max<size_t>(nkeep, 1));
-        void* dwork = b.take(nwork);
-        if (nkeep) HIPCHK(hipMemcpyAsync(dkeep, keep, nkeep, hipMemcpyHostToDevice, st));
-        if ((rc = jb_ids_device(ctx, dt, nb, dse, dse + cap, dcnt, tcap, st, did))) return rc;
-        if ((rc = jb_colloc_add_device(ctx, d_table, ntable, d_uni, nuni, did, tcap, dtok, dcnt, ndocs, dkeep, nkeep, flags,
-                                       dse, dse + cap, st, dwork, nwork)))
-            return rc;
-        HIPCHK(hipStreamSynchronize(st));
-        return JB_OK;
-    };
-    const int rc = run();
-    if (st) {
-        (void)hipStreamSynchronize(st);  // (the copies from the caller's memory may be in flight)
-        (void)hipStreamDestroy(st);
-    }
-    return rc;
-}
-
 // ---------------------------------------------------------------------------
 // Near-duplicate pairs (jb_neardup.hip; the host rule, jb_neardup, jb_neardup_labels, the argument checks, the
 // work buffer's layout and the size helper are jb_neardup.cpp)
@@ -2632,77 +1669,6 @@ extern "C" int jb_neardup_device(jb_ctx* ctx, const uint64_t* d_key, const uint3
     HIPCHK(run_neardup(d_key, d_sig, ndocs, B, K, W, min_agree, d_pair_doc, d_pair_agree, pcap, d_pair_off, d_npairs,
                        d_stat, d_work, s, nullptr));
     return JB_OK;
-}
-
-// Host signatures in, the pairs out: the upload, jb_minhash_bands_device and jb_neardup_device with every device
-// array in the ctx's buffer [12]; pair_off, the count and the counters come back first, the pairs when they fit
-// pcap.
-extern "C" int jb_neardup_sig(jb_ctx* ctx, const uint32_t* sig, const uint32_t* doc_n, uint32_t ndocs, uint32_t K,
-                              uint32_t B, uint32_t R, uint32_t W, uint32_t min_agree, uint32_t* pair_doc,
-                              uint32_t* pair_agree, uint64_t pcap, uint64_t* pair_off, uint64_t* npairs, uint64_t* stat) {
-    const char* who = "jb_neardup_sig";
-    if (const int rc = minhash_band_args(who, K, B, R)) return rc;
-    if (const int rc = neardup_args(who, ndocs, B, K, W, min_agree)) return rc;
-    if (!ctx || !pair_off || !npairs || !stat || (ndocs && (!sig || !doc_n)) || (pcap && (!pair_doc || !pair_agree)))
-        return fail(JB_EINVAL, "%s: null argument", who);
-    if (ndocs == 0) {
-        pair_off[0] = 0;
-        *npairs = 0;
-        for (uint32_t k = 0; k < JB_ND_NSTAT; k++) stat[k] = 0;
-        return JB_OK;
-    }
-    int ordinal;
-    {
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        ordinal = ctx->devs[0]->ordinal;
-    }
-    HIPCHK(hipSetDevice(ordinal));
-    std::lock_guard<std::mutex> kg(ctx->kw_mu);
-    hipStream_t st = nullptr;
-    auto run = [&]() -> int {
-        int rc;
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        const size_t nsig = (size_t)ndocs * K * 4, ndn = (size_t)ndocs * 4, nkey = (size_t)ndocs * B * 8,
-                     nwork = jb_neardup_work_bytes(ndocs, B), noff = ((size_t)ndocs + 1) * 8;
-        Arena a;
-        if ((rc = kw_arena(ctx, 12, r256(nsig) + r256(ndn) + r256(nkey) + r256(nwork) + 2 * r256(pcap * 4) + r256(noff) +
-                                        r256(8) + r256(JB_ND_NSTAT * 8), &a)))
-            return rc;
-        uint32_t* dsig = (uint32_t*)a.take(nsig);
-        uint32_t* ddn = (uint32_t*)a.take(ndn);
-        uint64_t* dkey = (uint64_t*)a.take(nkey);
-        void* work = a.take(nwork);
-        uint32_t* dpd = (uint32_t*)a.take(pcap * 4);
-        uint32_t* dpa = (uint32_t*)a.take(pcap * 4);
-        uint64_t* dpoff = (uint64_t*)a.take(noff);
-        uint64_t* dn = (uint64_t*)a.take(8);
-        uint64_t* dstat = (uint64_t*)a.take(JB_ND_NSTAT * 8);
-        HIPCHK(hipMemcpyAsync(dsig, sig, nsig, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ddn, doc_n, ndn, hipMemcpyHostToDevice, st));
-        if ((rc = jb_minhash_bands_device(ctx, dsig, ddn, ndocs, K, B, R, st, dkey))) return rc;
-        if ((rc = jb_neardup_device(ctx, dkey, dsig, ndocs, B, K, W, min_agree, pcap ? dpd : nullptr, pcap ? dpa : nullptr,
-                                    pcap, dpoff, dn, dstat, work, nwork, st)))
-            return rc;
-        HIPCHK(hipMemcpyAsync(pair_off, dpoff, noff, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(npairs, dn, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(stat, dstat, JB_ND_NSTAT * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (*npairs > pcap)
-            return fail(JB_ELIMIT, "%s: %llu pairs, the arrays hold %llu", who, (unsigned long long)*npairs,
-                        (unsigned long long)pcap);
-        if (*npairs) {
-            HIPCHK(hipMemcpyAsync(pair_doc, dpd, *npairs * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(pair_agree, dpa, *npairs * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-        }
-        return JB_OK;
-    };
-    const int rc = run();
-    if (st) {
-        (void)hipStreamSynchronize(st);  // (a copy from or to the caller's memory may be in flight)
-        (void)hipStreamDestroy(st);
-    }
-    return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -2749,8 +1715,8 @@ extern "C" int jb_bm25_idf_device(jb_ctx* ctx, const uint64_t* d_post_off, uint3
     return JB_OK;
 }
 
-namespace {
-// The search, queued: the caller holds the ctx's lock (shared or exclusive) and has checked the arguments.
+// The search, queued: the caller holds the ctx's lock (shared or exclusive) and has checked the arguments
+// (jb_search_batch, in jb_batch.cpp, queues it too).
 int bm25_queue(jb_ctx* ctx, const uint32_t* d_post_doc, const uint32_t* d_post_tf, const uint64_t* d_post_off,
                uint64_t npost, uint32_t nids, const float* d_norm, uint32_t ndocs, const float* d_weight,
                uint32_t nweights, double k1, const uint32_t* d_q_id, uint64_t q_cap, const uint64_t* d_q_off, uint32_t nq,
@@ -2769,7 +1735,6 @@ int bm25_queue(jb_ctx* ctx, const uint32_t* d_post_doc, const uint32_t* d_post_t
                            q_cap, d_q_off, nq, topk, form, d_res_doc, d_res_score, d_res_n, d_work, s, nullptr));
     return JB_OK;
 }
-}  // namespace
 
 extern "C" int jb_bm25_search_device(jb_ctx* ctx, const uint32_t* d_post_doc, const uint32_t* d_post_tf,
                                      const uint64_t* d_post_off, uint64_t npost, uint32_t nids, const float* d_norm,
@@ -2881,47 +1846,4 @@ extern "C" int jb_index_info(jb_ctx* ctx, uint64_t* ndocs, uint64_t* nids, uint6
     if (npost) *npost = ctx->index.npost;
     if (avgdl) *avgdl = ctx->index.avgdl;
     return JB_OK;
-}
-
-// Host query text in, the best documents out: batch_chain (its token ids in token order and its token offsets
-// are the queries' CSR), then the search with its work buffer and its records in the ctx's buffer [11].
-extern "C" int jb_search_batch(jb_ctx* ctx, const uint8_t* qtext, const uint64_t* q_off, uint32_t nq, int hmm,
-                               uint32_t topk, uint32_t* res_doc, uint64_t* res_score, uint32_t* res_n) {
-    const char* who = "jb_search_batch";
-    if (const int rc = bm25_topk(who, topk)) return rc;
-    if (!ctx || !q_off || (nq && (!res_doc || !res_score || !res_n))) return fail(JB_EINVAL, "%s: null argument", who);
-    {
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        if (!ctx->vocab) return fail(JB_EINVAL, "%s: no vocabulary attached (jb_vocab_set)", who);
-        if (!ctx->index.base) return fail(JB_EINVAL, "%s: no index attached (jb_index_set)", who);
-        if (ctx->index.nids != ctx->vocab->nkeys)
-            return fail(JB_EINVAL, "%s: the index has %u ids, the vocabulary %u keys", who, ctx->index.nids,
-                        (uint32_t)ctx->vocab->nkeys);
-    }
-    const size_t nrec = (size_t)nq * topk;
-    return batch_chain(ctx, who, qtext, q_off, nq, hmm, 0, [&](const BatchCsr& c, Arena*) -> int {
-        // (the lock keeps the index while the search is queued; a jb_index_set that follows waits for the device)
-        std::shared_lock<std::shared_mutex> rl(ctx->lock);
-        const jb_ctx::Index& ix = ctx->index;
-        if (!ix.base || !ctx->vocab || ix.nids != ctx->vocab->nkeys)
-            return fail(JB_EINVAL, "%s: the index was replaced during the call", who);
-        const Bm25Work w = bm25_layout(nq, ix.ndocs, topk);
-        const size_t nwork = ctx->devs[0]->lc.bm25_form ? w.bytes1 : w.bytes;
-        if (nwork == SIZE_MAX) return fail(JB_ELIMIT, "%s: %u queries over %u documents", who, nq, ix.ndocs);
-        Arena b;
-        if (const int r = kw_arena(ctx, 11, r256(nwork) + r256(nrec * 8) + r256(nrec * 4) + r256((size_t)nq * 4), &b))
-            return r;
-        void* work = b.take(nwork);
-        uint64_t* dscore = (uint64_t*)b.take(nrec * 8);
-        uint32_t* ddoc = (uint32_t*)b.take(nrec * 4);
-        uint32_t* dn = (uint32_t*)b.take((size_t)nq * 4);
-        if (const int r = bm25_queue(ctx, ix.post_doc, ix.post_tf, ix.post_off, ix.npost, ix.nids, ix.norm, ix.ndocs,
-                                     ix.weight, ix.nids, ix.k1, c.ids, c.tcap, c.doc_tok, nq, topk, c.st, ddoc, dscore, dn,
-                                     work))
-            return r;
-        HIPCHK(hipMemcpyAsync(res_doc, ddoc, nrec * 4, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipMemcpyAsync(res_score, dscore, nrec * 8, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipMemcpyAsync(res_n, dn, (size_t)nq * 4, hipMemcpyDeviceToHost, c.st));
-        return JB_OK;
-    });
 }

@@ -1,5 +1,5 @@
-// jb_charspans.h — what jb_charspans (jb_charspans.cpp), jb_charspans_device and jb_cut_batch_charspans
-// (jb_capi.cpp) share.  Library-internal, host only.
+// jb_charspans.h — what jb_charspans (jb_charspans.cpp), jb_charspans_device (jb_capi.cpp) and
+// jb_cut_batch_charspans (jb_batch.cpp) share.  Library-internal, host only.
 #pragma once
 #include <cstdint>
 

@@ -25,6 +25,17 @@ int colloc_slots(const char* who, uint64_t nslots) {
     return JB_OK;
 }
 
+int colloc_table_args(const char* who, const void* d_table, size_t ntable, const void* d_uni, uint32_t nuni) {
+    if (!d_table) return fail(JB_EINVAL, "%s: null table", who);
+    if (((uintptr_t)d_table & 31u) != 0) return fail(JB_EINVAL, "%s: d_table must be 32-byte aligned", who);
+    if (ntable < jb_cl_bytes(JB_CL_MIN_SLOTS))
+        return fail(JB_EINVAL, "%s: a table buffer of %llu bytes, the smallest table has %llu", who,
+                    (unsigned long long)ntable, (unsigned long long)jb_cl_bytes(JB_CL_MIN_SLOTS));
+    if (nuni && !d_uni) return fail(JB_EINVAL, "%s: null d_uni", who);
+    if (((uintptr_t)d_uni & 7u) != 0) return fail(JB_EINVAL, "%s: d_uni must be 8-byte aligned", who);
+    return JB_OK;
+}
+
 int colloc_add_args(const char* who, const void* ids, uint64_t ids_cap, const void* doc_tok, const void* keep,
                     uint32_t nkeep, uint32_t flags, const void* start, const void* end, const void* uni, uint32_t nuni) {
     if (flags & ~JB_COLLOC_CONTIG) return fail(JB_EINVAL, "%s: flags %#x (JB_COLLOC_CONTIG)", who, flags);

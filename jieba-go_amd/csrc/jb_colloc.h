@@ -153,6 +153,8 @@ namespace jb {
 
 // The checks the host rule and the device calls share: JB_OK, or JB_EINVAL / JB_ELIMIT with the thread's message set.
 int colloc_slots(const char* who, uint64_t nslots);
+// What every call that is handed a table checks: JB_OK, or JB_EINVAL with the thread's message set.
+int colloc_table_args(const char* who, const void* d_table, size_t ntable, const void* d_uni, uint32_t nuni);
 int colloc_add_args(const char* who, const void* ids, uint64_t ids_cap, const void* doc_tok, const void* keep,
                     uint32_t nkeep, uint32_t flags, const void* start, const void* end, const void* uni, uint32_t nuni);
 int colloc_score_args(const char* who, const void* uni, uint32_t nuni, int scorer, uint64_t min_count);

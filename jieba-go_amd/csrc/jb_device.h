@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/jiebahip.h"
+#include "jb_batch.h"
 #include "jb_err.h"
 #include "jb_image.h"
 #include "jb_kernels.h"
@@ -339,21 +340,12 @@ struct jb_ctx {
     uint32_t* d_sslots = nullptr;
     uint8_t* d_spool = nullptr;
     DevVocab dstop{};
-    // jb_keywords_batch's and jb_df_batch's device buffers on the first device, kept for the next call
-    // (they only grow; calls take kw_mu in turn): [0] sized by the batch's bytes, [1] by its token count,
-    // [2] jb_df_batch's ndf counters, [3] jb_textrank_batch's keep mask, records and work buffer,
-    // [4] jb_cut_batch_join's output, [5] its work buffer and output offsets,
-    // [6] jb_cut_batch_charspans' work buffer and doc_units, [7] jb_wc_batch's work buffer,
-    // [8] jb_minhash_batch's work buffer, signatures and shingle counts,
-    // [9] the batch filter's work buffer and filtered span list (jb_cut_batch_filter, jb_batch_filter_set),
-    // [10] jb_postings_batch's work buffer and postings, [11] jb_search_batch's work buffer and records,
-    // [12] jb_neardup_sig's signatures, keys, work buffer and pairs,
-    // [13] jb_colloc_batch's ids, keep mask and work buffer
+    // the host-text calls' device buffers on the first device (jb_batch.h: KwBuf names them) and the lock they
+    // are used under
     std::mutex kw_mu;
-    void* kw_buf[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t kw_cap[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    // the rule jb_cut_batch_join, jb_wc_batch, jb_minhash_batch and jb_colloc_batch filter by (jb_batch_filter_set; under kw_mu)
+    void* kw_buf[kArCount] = {};
+    size_t kw_cap[kArCount] = {};
+    // the rule of jb_batch_filter_set (under kw_mu); jb_batch.cpp lists the calls that filter by it
     bool bfilter_on = false;
     jb_filter_rule bfilter{0, 0, 0, 0};
     // the caller's index (jb_index_set) on the first device, one allocation: search calls read it under the

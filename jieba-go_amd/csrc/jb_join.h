@@ -1,4 +1,4 @@
-// jb_join.h — what jb_join (jb_join.cpp), jb_join_device and jb_cut_batch_join (jb_capi.cpp) share.
+// jb_join.h — what jb_join (jb_join.cpp), jb_join_device (jb_capi.cpp) and jb_cut_batch_join (jb_batch.cpp) share.
 // Library-internal, host only.
 #pragma once
 #include <cstdint>

@@ -1,4 +1,5 @@
-// jb_textrank.h — what jb_textrank (jb_textrank.cpp) and jb_textrank_device (jb_capi.cpp) share.
+// jb_textrank.h — what jb_textrank (jb_textrank.cpp), jb_textrank_device (jb_capi.cpp) and jb_textrank_batch
+// (jb_batch.cpp) share.
 // Library-internal, host only.
 #pragma once
 #include <cstdint>

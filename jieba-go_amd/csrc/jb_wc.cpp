@@ -31,6 +31,15 @@ int wc_sizes(const char* who, uint64_t nslots, uint64_t pool_bytes) {
     return JB_OK;
 }
 
+int wc_table_args(const char* who, const void* d_table, size_t ntable) {
+    if (!d_table) return fail(JB_EINVAL, "%s: null table", who);
+    if (((uintptr_t)d_table & 31u) != 0) return fail(JB_EINVAL, "%s: d_table must be 32-byte aligned", who);
+    if (ntable < jb_wc_bytes(JB_WC_MIN_SLOTS, 0))
+        return fail(JB_EINVAL, "%s: a table buffer of %llu bytes, the smallest table has %llu", who,
+                    (unsigned long long)ntable, (unsigned long long)jb_wc_bytes(JB_WC_MIN_SLOTS, 0));
+    return JB_OK;
+}
+
 void wc_host_add(const JbWcView& v, const uint8_t* key, uint32_t len, uint32_t k, uint32_t bits) {
     v.hdr->ctr[JB_WC_TOKENS]++;
     uint32_t kw[6];

@@ -138,6 +138,8 @@ namespace jb {
 
 // The limits of a table's sizes: JB_OK, or JB_EINVAL / JB_ELIMIT with the thread's message set.
 int wc_sizes(const char* who, uint64_t nslots, uint64_t pool_bytes);
+// What every call that is handed a table checks: JB_OK, or JB_EINVAL with the thread's message set.
+int wc_table_args(const char* who, const void* d_table, size_t ntable);
 // One token of key[0..len) (1 <= len <= 255, the key already formed) added to a table in host memory: what
 // the three kernels do to it, one token at a time and in order, through the code above (the sanitizer
 // program builds tables with it).  k is the token's index in its batch, bits the fingerprint's width.

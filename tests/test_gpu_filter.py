@@ -558,6 +558,55 @@ def test_batch_filter(mini_paths, stop, real, mode, hmm):
         t.close()
 
 
+def test_batch_filter_after_full_mode_regrow(mini_paths):
+    """A batch whose full-mode list is longer than the text has bytes (F.chain_dict(5) over the mini dictionary,
+    test_ctx_model.py::test_the_regrow_case_is_the_smallest; 77 spans in 76 bytes): the cut's regrow, then the batch filter,
+    then jb_cut_batch_join, jb_wc_batch and jb_minhash_batch's own step equal the host rules over the filtered
+    full-mode spans; with the filter cleared, over all of them."""
+    import torch
+    with open(mini_paths[0], encoding="utf-8") as f:
+        d = f.read()
+    t = J.Tokenizer(J.make_config(dict_bytes=(F.chain_dict(5) + d).encode(), emit_path=mini_paths[1]))
+    try:
+        buf, off = R.batch_of([("甲" * 12).encode(), ("𠀀" + "甲" * 12).encode()])
+        text = bytes(buf[:int(off[-1])])
+        s, e, dt = t.cut_batch_full(buf, off)
+        assert len(s) > int(off[-1])
+        nslots, pool = 1 << 10, 1 << 12
+        ntable = J.wc_table_bytes(nslots, pool)
+        tab = torch.zeros(ntable + 32, dtype=torch.uint8, device="cuda")
+        p_tab = (tab.data_ptr() + 31) & ~31
+
+        def run():
+            out, ooff = t.cut_batch_join(buf, off, False, "full", b" ", b"\n")
+            t.wc_init_device(p_tab, ntable, nslots, pool)
+            t.wc_batch(buf, off, False, p_tab, ntable, "full")
+            wc = t.wc_read(p_tab, ntable)
+            sig, dn = t.minhash_batch(buf, off, False, 2, 16, 5, "full")
+            return (out.tobytes(), ooff.tobytes(), wc.keys, wc.counts.tobytes(), wc.tokens, sig.tobytes(), dn.tobytes())
+
+        def want(fs, fe, fdt):
+            out, ooff, _ = J.join(text, fs, fe, fdt, b" ", b"\n")
+            wc = J.wc_count(text, fs, fe)
+            sig, dn = J.minhash(text, fs, fe, fdt, 2, 16, 5)
+            return (out.tobytes(), ooff.tobytes(), wc.keys, wc.counts.tobytes(), wc.tokens, sig.tobytes(), dn.tobytes())
+
+        # (every token here is Han, so the first rule keeps none of the longer list; the second keeps the words of
+        # two runes and more)
+        seen = []
+        for rule, some in (((("han",), 2, 0), False), (((), 2, 0), True)):
+            t.set_batch_filter(*rule)
+            hs, he, _, hdt, hn, _ = J.filter_spans(text, s, e, dt, J.filter_rule(*rule))
+            assert hn < len(s) and (hn > 0) == some
+            seen.append(run())
+            assert seen[-1] == want(hs[:hn], he[:hn], hdt)
+        t.clear_batch_filter()
+        plain = run()
+        assert plain == want(s, e, dt) and plain not in seen and seen[0] != seen[1]
+    finally:
+        t.close()
+
+
 def test_c_and_cpp_consumers(mini_paths, tmp_path):
     lib = os.path.join(ROOT, "jieba-go_amd", "lib")
     exe = str(tmp_path / "c_abi_filter")

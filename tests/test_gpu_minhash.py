@@ -406,6 +406,39 @@ def test_add_word_changes_the_signature(mini_paths):
         tk.close()
 
 
+def regrow_tokenizer(mini_paths):
+    """A tokenizer over F.chain_dict(5) plus the mini dictionary, the smallest chain with a full-mode list longer than
+    its text (test_ctx_model.py::test_the_regrow_case_is_the_smallest), and a batch of two such documents:
+    (tk, buf, off, text).  A run of n >= 5 甲 has 4n - 10 spans in 3n bytes; with the second document's 𠀀 (one span,
+    four bytes) runs of 11 give 69 spans in 70 bytes, runs of 12 give 77 in 76."""
+    with open(mini_paths[0], encoding="utf-8") as f:
+        d = f.read()
+    tk = J.Tokenizer(J.make_config(dict_bytes=(F.chain_dict(5) + d).encode(), emit_path=mini_paths[1]))
+    buf, off = R.batch_of([("甲" * 12).encode(), ("𠀀" + "甲" * 12).encode()])
+    return tk, buf, off, bytes(buf[:int(off[-1])])
+
+
+def test_minhash_batch_full_mode_regrow(mini_paths):
+    """Full mode with more spans than bytes: jb_minhash_batch grows the span arrays and repeats the cut, twice over,
+    and a plain-mode call that follows on the same context is not disturbed by it."""
+    tf, buf, off, text = regrow_tokenizer(mini_paths)
+    try:
+        s, e, d = tf.cut_batch_full(buf, off)
+        assert len(s) > int(off[-1])
+        want_sig, want_dn = J.minhash(text, s, e, d, 2, 16, 5)
+        assert int(want_dn.sum()) > 0
+        for rep in range(2):
+            sig, dn = tf.minhash_batch(buf, off, False, 2, 16, 5, "full")
+            assert (dn == want_dn).all() and (sig == want_sig).all(), rep
+        ps, pe, pd = tf.cut_batch(buf, off, False)
+        assert len(ps) < len(s)
+        plain_sig, plain_dn = J.minhash(text, ps, pe, pd, 2, 16, 5)
+        sig, dn = tf.minhash_batch(buf, off, False, 2, 16, 5, "cut")
+        assert (dn == plain_dn).all() and (sig == plain_sig).all()
+    finally:
+        tf.close()
+
+
 def test_c_and_cpp_consumers(mini_paths, tmp_path):
     lib = os.path.join(ROOT, "jieba-go_amd", "lib")
     exe = str(tmp_path / "c_abi_minhash")
