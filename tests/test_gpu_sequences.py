@@ -8,12 +8,17 @@ the vocabulary, the four arenas of the *_batch calls, and the flags behind jb_la
 counts: their batch calls carve the same arenas in another layout (and four more), move the span arrays into
 the ids/terms arena when a full-mode list outgrows its batch, overwrite span arrays in place, hand out a
 pinned block that one process-wide cache recycles, and add to a table the caller keeps; join_ref,
-charspans_ref and wc_ref over the model's spans answer them, byte for byte."""
+charspans_ref and wc_ref over the model's spans answer them, byte for byte.  The last part follows the calls
+that came after those (MinHash, the caller's filter, postings, BM25 search, near-duplicate pairs, collocations)
+through the same arenas and their own six, which only grow and are never cleared, with the stop set, the batch
+filter and the index changing under them and JB_ELIMIT / JB_EINVAL returned half-way through a call."""
+import ctypes as C
 import gc
 
 import numpy as np
 import pytest
 
+import bm25_ref as BR
 import charspans_ref as CR
 import ctx_model as M
 import full_ref as F
@@ -110,6 +115,9 @@ class Driver:
         self.cs_out, self.cs_cap = None, None  # the arrays of the last charspans_batch, and their size
         self.calls = []  # (kind, bytes of the batch) of every *_batch call
         self.too_small = self.restored = 0  # charspans_batch retries; cuts repeated after an in-place charspans
+        self.sig = None  # the last minhash_batch: the model's (sig, doc_n, whether the batch has duplicates)
+        self.ctable = None  # one collocation table and d_uni per vocabulary
+        self.log = []  # ("refused", kind), ("search", spec, hits, misses), ("neardup", dups, pairs, over the window)
 
     def st(self):
         """A stream of the driver's own, for every device call: the library captures a graph only for a
@@ -274,10 +282,13 @@ class Driver:
         b = self.batch(b)
         self.lastdev = None
         self.calls.append(("join_batch", b.nbytes))
-        want, woff = self.m.join(b, mode, hmm, sep, term)
+        label = f"{label} join_batch {mode} hmm={hmm} {b.spec} sep={sep!r} term={term!r}"
+        try:
+            want, woff = self.m.join(b, mode, hmm, sep, term)
+        except M.ModelError:  # (a batch filter that asks for a stop set that is gone)
+            return self.refused(lambda: self.tk.cut_batch_join(b.buf, b.off, hmm, M.LIB_MODE[mode], sep, term), label)
         if self.tk is None:
             return None
-        label = f"{label} join_batch {mode} hmm={hmm} {b.spec} sep={sep!r} term={term!r}"
         got, off = self.tk.cut_batch_join(b.buf if buf is None else buf, b.off, hmm, M.LIB_MODE[mode], sep, term)
         assert off.tolist() == woff, f"{label}: out_doc_off"
         assert got.tobytes() == want, f"{label}: {len(got)} bytes, want {len(want)}"
@@ -335,7 +346,13 @@ class Driver:
         b = self.batch(b)
         self.lastdev = None
         self.calls.append(("wc_batch", b.nbytes))
-        self.m.wc_batch(b, mode, hmm)
+        try:
+            self.m.wc_batch(b, mode, hmm)
+        except M.ModelError:  # (raised before the model's table is touched; the library's must stay as it is too)
+            if self.tk is not None:
+                ptr, n = self.wc_table()
+                self.refused(lambda: self.tk.wc_batch(b.buf, b.off, hmm, ptr, n, M.LIB_MODE[mode]), f"{label} wc_batch")
+            return
         if self.tk is None:
             return
         ptr, n = self.wc_table()
@@ -469,6 +486,260 @@ class Driver:
         torch.cuda.synchronize()
         inner_bytes(work, nwork)
 
+    # -- MinHash, the caller's filter, postings, search, near-duplicates and collocations; the stop set, the batch
+    # filter and the index.  Without a library (DryDriver) each makes the model's call alone.
+    def _both(self, kind, b, want_fn, lib_fn, label):
+        """One *_batch call of `kind` on batch b: (the model's answer, the library's).  Where the model refuses the
+        call (ModelError) the library must return JB_EINVAL: (None, None)."""
+        self.lastdev = None
+        self.calls.append((kind, b.nbytes))
+        try:
+            want = want_fn()
+        except M.ModelError:
+            want = None
+            self.log.append(("refused", kind))
+        if self.tk is None:
+            return want, None
+        if want is None:
+            self.refused(lib_fn, label)
+            return None, None
+        return want, lib_fn()
+
+    def refused(self, lib_fn, label):
+        """A call the model refuses: the library's JB_EINVAL."""
+        if self.tk is not None:
+            with pytest.raises(J.JbError) as ei:
+                lib_fn()
+            assert ei.value.code == J.JB_EINVAL, f"{label}: {ei.value}"
+
+    def minhash_batch(self, mode, hmm, b, n=5, K=128, seed=1, label="", dups=False):
+        """jb_minhash_batch; the model's signatures are kept for neardup (sig, doc_n, whether b has duplicates)."""
+        b = self.batch(b)
+        label = f"{label} minhash_batch {mode} hmm={hmm} {b.spec} n={n} K={K} seed={seed}"
+        want, got = self._both("minhash_batch", b, lambda: self.m.minhash(b, mode, hmm, n, K, seed),
+                               lambda: self.tk.minhash_batch(b.buf, b.off, hmm, n, K, seed, M.LIB_MODE[mode]), label)
+        if want is not None:
+            self.sig = (want[0], want[1], dups)
+        if got is not None:
+            assert np.array_equal(got[1], want[1]), f"{label}: doc_n"
+            assert got[0].shape == want[0].shape and np.array_equal(got[0], want[0]), f"{label}: signatures"
+        return want
+
+    def filter_batch(self, mode, hmm, b, rule, short=0, label=""):
+        """jb_cut_batch_filter with a caller's rule into arrays of the exact count less `short`: too small, it is
+        JB_ELIMIT with the count and the statistics right and nothing else written."""
+        b = self.batch(b)
+        label = f"{label} filter_batch {mode} hmm={hmm} {b.spec} {rule} short={short}"
+        nd = b.ndocs
+
+        def call():
+            n = len(self.m.filter_batch(b, mode, hmm, rule)[0])
+            cap = max(n - short, 0)
+            s, e = np.full(max(cap, 1), JUNK, np.uint32), np.full(max(cap, 1), JUNK, np.uint32)
+            tok, cnt, stats = np.full(nd + 1, JUNK, np.uint64), C.c_uint64(JUNK), np.full(5, JUNK, np.uint64)
+            r = J.jb_filter_rule(J.JB_FILTER_STOP if rule.stop else 0, rule.drop, rule.min_runes, rule.max_runes)
+            rc = J.lib().jb_cut_batch_filter(self.tk.h, b.buf.ctypes.data, b.off.ctypes.data, nd, int(hmm),
+                                             J._MODES[M.LIB_MODE[mode]], C.byref(r), s.ctypes.data, e.ctypes.data, cap,
+                                             tok.ctypes.data, C.byref(cnt), stats.ctypes.data)
+            if rc == J.JB_EINVAL:
+                J._check(rc)
+            return rc, s, e, tok, cnt.value, stats, cap
+
+        want, got = self._both("filter_batch", b, lambda: self.m.filter_batch(b, mode, hmm, rule), call, label)
+        if got is not None:
+            rc, s, e, tok, cnt, stats, cap = got
+            ws, we, wd, wst = want
+            assert cnt == len(ws) and np.array_equal(stats, wst), f"{label}: count {cnt}, statistics {stats.tolist()}"
+            if len(ws) > cap:
+                assert rc == J.JB_ELIMIT, f"{label}: {rc}"
+                assert (s == JUNK).all() and (e == JUNK).all() and (tok == JUNK).all(), f"{label}: written after JB_ELIMIT"
+            else:
+                assert rc == J.JB_OK, f"{label}: {rc}"
+                assert np.array_equal(s[:cnt], ws) and np.array_equal(e[:cnt], we), f"{label}: spans"
+                assert (s[cnt:] == JUNK).all() and (e[cnt:] == JUNK).all(), f"{label}: written past the count"
+                assert np.array_equal(tok, wd), f"{label}: doc_tok"
+        return want
+
+    def postings_batch(self, hmm, b, doc_base=0, short=0, label=""):
+        """jb_postings_batch into arrays of the exact count less `short`: too small, it is JB_ELIMIT with the count
+        and post_off right and no list written."""
+        b = self.batch(b)
+        label = f"{label} postings_batch hmm={hmm} {b.spec} doc_base={doc_base} short={short}"
+        nd = b.ndocs
+
+        def call():
+            nids = len(self.m.keys)
+            pcap = max(len(self.m.postings(b, hmm, doc_base)[1]) - short, 0)
+            po, dl = np.full(nids + 1, JUNK, np.uint64), np.full(max(nd, 1), JUNK, np.uint32)
+            pd, pt = np.full(max(pcap, 1), JUNK, np.uint32), np.full(max(pcap, 1), JUNK, np.uint32)
+            n = C.c_uint64(JUNK)
+            rc = J.lib().jb_postings_batch(self.tk.h, b.buf.ctypes.data, b.off.ctypes.data, nd, int(hmm), doc_base, pcap,
+                                           po.ctypes.data, nids, pd.ctypes.data, pt.ctypes.data, C.byref(n), dl.ctypes.data)
+            if rc == J.JB_EINVAL:
+                J._check(rc)
+            return rc, po, pd, pt, n.value, dl[:nd], pcap
+
+        want, got = self._both("postings_batch", b, lambda: self.m.postings(b, hmm, doc_base), call, label)
+        if got is not None:
+            rc, po, pd, pt, n, dl, pcap = got
+            wo, wd, wt, wl = want
+            assert n == len(wd) and np.array_equal(po, wo), f"{label}: count {n} (want {len(wd)}) or post_off"
+            if len(wd) > pcap:
+                assert rc == J.JB_ELIMIT, f"{label}: {rc}"
+                assert (pd == JUNK).all() and (pt == JUNK).all(), f"{label}: lists written after JB_ELIMIT"
+            else:
+                assert rc == J.JB_OK, f"{label}: {rc}"
+                assert np.array_equal(pd[:n], wd) and np.array_equal(pt[:n], wt), f"{label}: the lists"
+                assert (pd[n:] == JUNK).all() and (pt[n:] == JUNK).all(), f"{label}: written past the count"
+                assert np.array_equal(dl, wl), f"{label}: doc_len"
+        return want
+
+    def search_batch(self, hmm, b, topk, label=""):
+        """jb_search_batch: the records of every query, every slot; JB_EINVAL where the model has no answer."""
+        b = self.batch(b)
+        label = f"{label} search_batch hmm={hmm} {b.spec} topk={topk}"
+
+        def call():
+            rows = max(b.ndocs, 1) * topk
+            rd, rs, rn = np.full(rows, JUNK, np.uint32), np.full(rows, JUNK, np.uint64), np.full(max(b.ndocs, 1), JUNK, np.uint32)
+            J._check(J.lib().jb_search_batch(self.tk.h, b.buf.ctypes.data, b.off.ctypes.data, b.ndocs, int(hmm), topk,
+                                             rd.ctypes.data, rs.ctypes.data, rn.ctypes.data))
+            return rd.reshape(-1, topk)[:b.ndocs], rs.reshape(-1, topk)[:b.ndocs], rn[:b.ndocs]
+
+        want, got = self._both("search_batch", b, lambda: self.m.search(b, hmm, topk), call, label)
+        if want is not None:
+            self.log.append(("search", b.spec, int((want[2] > 0).sum()), int((want[2] == 0).sum())))
+        if got is not None:
+            for g, w, name in zip(got, want, ("res_doc", "res_score", "res_n")):
+                assert g.shape == w.shape and np.array_equal(g, w), f"{label}: {name}"
+        return want
+
+    def neardup(self, B, R, W=64, min_agree=None, short=None, label=""):
+        """jb_neardup_sig on the signatures of the last minhash_batch, into arrays of the exact count less `short`
+        (None: arrays of no entry at all, which gives the counts only)."""
+        if self.sig is None:
+            return None
+        sig, doc_n, _ = self.sig
+        nd, K = sig.shape
+        min_agree = J._default_agree(K) if min_agree is None else min_agree
+        label = f"{label} neardup B={B} R={R} W={W} min_agree={min_agree} short={short}"
+        wo, wd, wa, wst = want = self.m.neardup(sig, doc_n, B, R, W, min_agree)
+        self.log.append(("neardup", self.sig[2], len(wd), int(wst[2])))
+        if self.tk is None:
+            return want
+        pcap = 0 if short is None else max(len(wd) - short, 0)
+        po, st, n = np.full(nd + 1, JUNK, np.uint64), np.full(J.JB_ND_NSTAT, JUNK, np.uint64), C.c_uint64(JUNK)
+        pd, pa = np.full(max(pcap, 1), JUNK, np.uint32), np.full(max(pcap, 1), JUNK, np.uint32)
+        rc = J.lib().jb_neardup_sig(self.tk.h, sig.ctypes.data, doc_n.ctypes.data, nd, K, B, R, W, min_agree,
+                                    pd.ctypes.data if pcap else None, pa.ctypes.data if pcap else None, pcap,
+                                    po.ctypes.data, C.byref(n), st.ctypes.data)
+        assert n.value == len(wd) and np.array_equal(po, wo) and np.array_equal(st, wst), \
+            f"{label}: count {n.value} (want {len(wd)}), pair_off or the counters {st.tolist()} (want {wst.tolist()})"
+        if len(wd) > pcap:
+            assert rc == J.JB_ELIMIT, f"{label}: {rc}"
+            assert (pd == JUNK).all() and (pa == JUNK).all(), f"{label}: pairs written after JB_ELIMIT"
+        else:
+            assert rc == J.JB_OK, f"{label}: {rc}"
+            k = n.value
+            if pcap:
+                assert np.array_equal(pd[:k], wd) and np.array_equal(pa[:k], wa), f"{label}: the pairs"
+                assert (pd[k:] == JUNK).all() and (pa[k:] == JUNK).all(), f"{label}: written past the count"
+        return want
+
+    def colloc_table(self):
+        """The driver's collocation table and d_uni between canaries, for the vocabulary as it is: (table pointer,
+        bytes, d_uni pointer, nuni).  set_vocab drops both; the next call makes and initialises new ones."""
+        import torch
+        if self.m.cl is None:
+            self.m.colloc_init()
+        if self.tk is None:
+            return None
+        if self.ctable is None:
+            nuni = len(self.m.keys)
+            n = J.colloc_table_bytes(M.COLLOC_NSLOTS)
+            t, u = guarded_bytes(n), guarded(nuni, torch.int64)
+            assert (t.data_ptr() + NG) % 32 == 0
+            self.tk.colloc_init_device(t.data_ptr() + NG, n, M.COLLOC_NSLOTS, u.data_ptr() + 8 * NG, nuni, self.st())
+            torch.cuda.synchronize()
+            self.ctable = (t, n, u, nuni)
+        t, n, u, nuni = self.ctable
+        return t.data_ptr() + NG, n, u.data_ptr() + 8 * NG, nuni
+
+    def colloc_raw(self):
+        """The table's and d_uni's bytes, the canaries checked."""
+        t, n, u, nuni = self.ctable
+        return inner_bytes(t, n).tobytes(), inner(u, nuni, np.uint64).tobytes()
+
+    def colloc_batch(self, hmm, b, keep=None, contig=False, label=""):
+        """jb_colloc_batch into the driver's table; keep: None, or a u8 mask over the vocabulary's ids."""
+        b = self.batch(b)
+        label = f"{label} colloc_batch hmm={hmm} {b.spec} contig={contig}"
+        p = self.colloc_table() if self.m.vocab is not None else (0, 0, 0, 0)
+
+        def call():
+            self.tk.colloc_batch(b.buf, b.off, hmm, p[0], p[1], p[2], p[3], keep, J.JB_COLLOC_CONTIG if contig else 0)
+            return True
+
+        # (a refused call adds nothing: the model raises before it counts)
+        self._both("colloc_batch", b, lambda: self.m.colloc_batch(b, hmm, keep, contig) or True, call, label)
+
+    def colloc_read(self, scorer="count", min_count=1, threshold=float("-inf"), topn=0, label=""):
+        """jb_colloc_read against the model's table: the candidates in the rule's order with their f32 score bits,
+        and the five totals; nothing dropped."""
+        import torch
+        if self.m.cl is None:
+            return None
+        rows, totals = self.m.colloc_result(scorer, min_count, threshold, topn)
+        if self.tk is None:
+            return rows
+        p = self.colloc_table()
+        label = f"{label} colloc_read {scorer} min_count={min_count} threshold={threshold} topn={topn}"
+        r = self.tk.colloc_read(p[0], p[1], p[2], p[3], scorer, min_count, threshold, topn, self.st())
+        torch.cuda.synchronize()
+        self.colloc_raw()
+        assert r.totals() == totals, f"{label}: totals {r.totals()}, want {totals}"
+        assert (r.a.tolist(), r.b.tolist(), r.count.tolist()) == (
+            [x[0] for x in rows], [x[1] for x in rows], [x[2] for x in rows]), f"{label}: the candidates"
+        want = np.array([x[3] for x in rows], np.float32)
+        assert np.array_equal(r.score.view(np.uint32), want.view(np.uint32)), f"{label}: the scores' bits"
+        return rows
+
+    def set_stop(self, keys):
+        self.m.set_stop(keys)
+        if self.tk is not None:
+            self.tk.set_stop_words(keys)
+            assert self.tk.stop_words_size == (-1 if keys is None else len(set(keys)))
+
+    def set_filter(self, rule):
+        """jb_batch_filter_set; None clears."""
+        self.m.set_filter(rule)
+        if self.tk is None:
+            return
+        if rule is None:
+            self.tk.clear_batch_filter()
+        else:
+            self.tk.set_batch_filter(rule.drop, rule.min_runes, rule.max_runes, rule.stop)
+
+    def build_index(self, batches, hmm=True, k1=1.2, b=0.75, label=""):
+        """postings_batch of each batch with doc_base advancing (each checked), the model's merge of them, and
+        jb_index_set of that: jb_index_info must describe it."""
+        batches = [self.batch(x) for x in batches]
+        base = 0
+        for x in batches:
+            self.postings_batch(hmm, x, base, label=f"{label} build_index")
+            base += x.ndocs
+        ix = self.m.build_index(batches, hmm)
+        self.m.set_index(ix, k1, b)
+        if self.tk is not None:
+            self.tk.set_index(ix.post_off, ix.post_doc, ix.post_tf, ix.doc_len, k1=k1, b=b)
+            assert self.tk.index_info() == (len(ix.doc_len), ix.nids, len(ix.post_doc), BR.avgdl(ix.doc_len)), label
+        return ix
+
+    def clear_index(self):
+        self.m.set_index(None)
+        if self.tk is not None:
+            self.tk.clear_index()
+
     # -- the rest
     def add_word(self, word, freq):
         assert self.m.reachable(word), word  # (every word these tests add becomes an edge of buildDag)
@@ -482,6 +753,7 @@ class Driver:
         self.tk.set_vocab(keys)
         self.m.set_vocab(keys)
         assert self.tk.vocab_size == len(keys)
+        self.ctable = self.m.cl = None  # (the table's ids were the old vocabulary's: colloc_table starts anew)
 
     def stats(self, label=""):
         """jb_last_stats describes the ctx's last cut, whichever call made it."""
@@ -519,6 +791,30 @@ class Driver:
             self.wc_batch(op[1], op[2], op[3])
         elif k == "wc_read":
             self.wc_read()
+        elif k == "minhash_batch":
+            self.minhash_batch(op[1], op[2], op[3], op[4], op[5], dups=op[3][0] == "dups")
+        elif k == "filter_batch":
+            self.filter_batch(op[1], op[2], op[3], M.RULES[op[4]])
+        elif k == "postings_batch":
+            self.postings_batch(op[1], op[2])
+        elif k == "search_batch":
+            self.search_batch(op[1], op[2], op[3])
+        elif k == "colloc_batch":
+            self.colloc_batch(op[1], op[2], self.m.keep if op[3] else None, op[4])
+        elif k == "colloc_read":
+            self.colloc_read(op[1], 2 if op[1] != "count" else 1, 0.1 if op[1] != "count" else float("-inf"))
+        elif k == "neardup":
+            self.neardup(op[1], op[2], 64, op[3], short=0)
+        elif k == "set_stop":
+            self.set_stop(self.m.stop_keys(op[1]))
+        elif k == "set_filter":
+            self.set_filter(M.RULES[op[1]])
+        elif k == "clear_filter":
+            self.set_filter(None)
+        elif k == "build_index":
+            self.build_index([x for x in op[1:3] if x is not None], True, op[3], op[4])
+        elif k == "clear_index":
+            self.clear_index()
         else:
             raise ValueError(op)
 
@@ -562,6 +858,7 @@ class DryDriver(Driver):
 
     def set_vocab(self, keys):
         self.m.set_vocab(keys)
+        self.m.cl = None
 
     def stats(self, label=""):
         pass
@@ -951,12 +1248,13 @@ def test_random_sequences(syn, seed):
 # Each script takes a Driver and makes the calls; the test opens a tokenizer for it.  test_ctx_model.py runs the
 # scripts that fill a word-count table through a DryDriver first: the table must never be what limits a test.
 def arena_order(first, second):
-    """19 kinds, alternately of `first` and of `second` (three kinds each): every ordered pair of one of
-    `first` followed by one of `second`, and every pair the other way round, is a neighbouring pair."""
+    """Kinds alternately of `first` and of `second`: every pair of one of `first` directly followed by one of
+    `second`, and every pair the other way round, is a neighbouring pair (2 * len(first) * len(second) + 1 kinds:
+    19 for three kinds each)."""
     seq = []
-    for shift in range(3):
-        for i in range(3):
-            seq += [first[i], second[(i + shift) % 3]]
+    for shift in range(len(second)):
+        for i in range(len(first)):
+            seq += [first[i], second[(i + shift) % len(second)]]
     return seq + [first[0]]
 
 
@@ -1282,5 +1580,586 @@ def test_random_sequences2(syn, seed):
                 raise AssertionError(f"seed {seed}, step {i}: {op!r}\nops = {ops[:i + 1]!r}\n{e}") from e
         dr.wc_read("at the end")
         assert dr.too_small >= 1 and dr.restored >= 1  # (what covered2 promises did happen)
+    finally:
+        dr.tk.close()
+
+
+# ---- MinHash, the caller's filter, postings, search, near-duplicates and collocations on a long-lived context ----
+# These calls came after the ones above and share their front (batch_front / batch_chain, jb_batch.cpp): kArText and
+# kArTokens with every older call, and a grow-only buffer each that is never cleared.  The scripts take a Driver (or a
+# DryDriver: test_ctx_model.py checks their inputs on the CPU).
+NEWEST_BATCH_OPS = M.NEWEST_BATCH_OPS
+LARGE3 = 48 << 10  # the large batch of these scripts: the thresholds are 4,096 bytes / documents and 256-byte pieces
+
+
+def newest_call(dr, kind, b, i, label, modes=None):
+    """Call number i of a script: one *_batch call of `kind` on b, its parameters turned by i."""
+    mode = (modes or {}).get((kind, b.spec), M.MODES[i % 3])
+    hmm = mode != "full" and (b.nbytes > M.SMALL_MAX or i % 2 == 0)
+    if kind == "keywords_batch":
+        dr.keywords(True, b, 20, label)
+    elif kind == "df_batch":
+        dr.df(True, b, label)
+    elif kind == "textrank_batch":
+        dr.textrank(True, b, label=label)
+    elif kind == "join_batch":
+        dr.join_batch(mode, hmm, b, JR.SEPS[i % 4], JR.SEPS[(i + 1) % 4], label)
+    elif kind == "charspans_batch":
+        dr.charspans_batch(mode, hmm, b, ("rune", "utf16")[i % 2], b.nbytes > M.SMALL_MAX, label)
+    elif kind == "wc_batch":
+        dr.wc_batch(mode, hmm, b, label)
+    elif kind == "minhash_batch":
+        dr.minhash_batch(mode, hmm, b, (1, 3, 5)[i % 3], (16, 128, 64)[i % 3], 1 + i % 2, label)
+    elif kind == "filter_batch":
+        dr.filter_batch(mode, hmm, b, M.RULES[i % 2], label=label)
+    elif kind == "postings_batch":
+        dr.postings_batch(i % 2 == 0, b, (0, 7)[i % 2], label=label)
+    elif kind == "search_batch":
+        dr.search_batch(i % 2 == 0, b, (1, 10, 64)[i % 3], label)
+    elif kind == "colloc_batch":
+        dr.colloc_batch(i % 2 == 0, b, (None, dr.m.keep)[(i // 2) % 2], i % 3 == 0, label)
+    else:
+        raise ValueError(kind)
+    dr.stats(label)
+
+
+def script_arenas3(dr):
+    m = dr.m
+    big = dr.batch(("large", 1700, LARGE3))
+    one, none = M.from_texts(("one",), ["中"]), dr.batch(("empty", 0, 5))
+    tail = M.Batch(("tail",), big.buf, big.off[1:])  # (48 KiB are few documents: from document 1 on)
+    assert 32 << 10 < big.nbytes <= LARGE3 and one.nbytes == 3 and none.nbytes == 0 and none.ndocs == 5
+    assert int(tail.off[0]) > 0 and tail.nbytes > M.SMALL_MAX
+    v1, v2 = m.vocab_keys(0), m.vocab_keys(1)
+    assert len(v2) < len(v1)
+    modes = {("join_batch", big.spec): "plain", ("join_batch", tail.spec): "search",
+             ("charspans_batch", big.spec): "search", ("charspans_batch", tail.spec): "full",
+             ("wc_batch", big.spec): "full", ("wc_batch", tail.spec): "plain",
+             ("minhash_batch", big.spec): "full", ("minhash_batch", tail.spec): "plain",
+             ("filter_batch", big.spec): "search", ("filter_batch", tail.spec): "full"}
+    step = [0]
+
+    def call(kind, b):
+        i = step[0]
+        step[0] += 1
+        newest_call(dr, kind, b, i, f"call {i}", modes)
+
+    dr.set_vocab(v1)
+    dr.build_index([m.source])
+    # an older kind on each large batch and one of the newest on each tiny one, ...
+    for k, kind in enumerate(arena_order(M.ALL_BATCH_OPS, NEWEST_BATCH_OPS)):
+        call(kind, ((big, tail)[(k // 2) % 2], (one, none)[(k // 2) % 2])[k % 2])
+    dr.colloc_read("npmi", 2, 0.1, label="half way")
+    dr.wc_read("half way")
+    dr.set_vocab(v2)
+    dr.build_index([m.source], k1=1.6, b=0.5)
+    # ... and the other way round
+    for k, kind in enumerate(arena_order(NEWEST_BATCH_OPS, M.ALL_BATCH_OPS)):
+        if k == 30:
+            dr.add_word(m.pick_word(0, big), 10_000_000)
+            dr.stats("after AddWord")
+        call(kind, ((big, tail)[(k // 2) % 2], (one, none)[(k // 2) % 2])[k % 2])
+    dr.colloc_read("count", label="at the end")
+    dr.wc_read("at the end")
+    want = {(a, b, up) for a in M.ALL_BATCH_OPS for b in NEWEST_BATCH_OPS for up in (False, True)}
+    want |= {(b, a, up) for a, b, up in want}
+    assert len(want) == 120 and want <= arena_pairs(dr.calls), sorted(want - arena_pairs(dr.calls))
+
+
+def test_newest_batch_calls_share_the_arenas(syn):
+    """The five newest *_batch kinds and the six older ones on one ctx with a vocabulary and an index, over a 48 KiB
+    batch, one 3-byte document, five empty documents and the large buffer from its document 1 on, a smaller
+    vocabulary and an AddWord in between, jb_last_stats after every call: every ordered pair of a newest kind and
+    an older one, both ways round, lies on a large-then-tiny and on a tiny-then-large transition (asserted from the
+    driver's call list)."""
+    dr = open_20k(syn)
+    try:
+        script_arenas3(dr)
+    finally:
+        dr.tk.close()
+
+
+def script_same_shape3(dr):
+    m = dr.m
+    a = dr.batch(("offset", 787, 30 << 10))  # (sentences: many documents)
+    t = dr.batch(twin(a))
+
+    def other(x, y):
+        """Whether two of the model's answers differ in some array."""
+        return any(np.shape(i) != np.shape(j) or not np.array_equal(i, j) for i, j in zip(x, y))
+
+    qa = dr.batch(("queries", 797, 6))
+    qt = dr.batch(twin(qa))
+    d = dr.batch(("dups", 807, 64))
+    few = M.Batch(("few",), d.buf, d.off[:4])
+    assert np.array_equal(a.off, t.off) and np.array_equal(qa.off, qt.off) and qa.ndocs == 8 and few.ndocs == 3
+    v0, v1 = m.vocab_keys(0), m.vocab_keys(1)
+    dr.set_vocab(v0)
+    dr.build_index([m.source])
+    for mode, hmm in COMBOS[1:]:
+        got = [dr.minhash_batch(mode, hmm, x, 5, 64, label=f"same shape {k}") for k, x in enumerate((a, t, a))]
+        assert got[0] is got[2] and other(got[0], got[1])  # (the model's answers differ)
+        got = [dr.filter_batch(mode, hmm, x, M.RULES[0], label=f"same shape {k}") for k, x in enumerate((a, t, a))]
+        assert other(got[0], got[1])
+        dr.stats(mode)
+    for hmm in (True, False):
+        got = [dr.postings_batch(hmm, x, label=f"same shape {k}") for k, x in enumerate((a, t, a))]
+        assert other(got[0], got[1])
+        got = [dr.search_batch(hmm, x, 10, label=f"same shape {k}") for k, x in enumerate((qa, qt, qa))]
+        assert other(got[0], got[1])
+        for k, x in enumerate((a, t, a)):
+            dr.colloc_batch(hmm, x, label=f"same shape {k}")
+            dr.colloc_read("count", label=f"same shape {k}")
+        dr.stats(f"hmm={hmm}")
+    # shrinking calls: the larger call's tail lies right behind the live data of the smaller one
+    dr.minhash_batch("plain", True, d, 5, 128, label="K 128, 64 documents", dups=True)
+    big = dr.neardup(32, 4, 64, 64, short=0, label="B 32")
+    dr.minhash_batch("plain", True, few, 5, 16, label="K 16, 3 documents")
+    dr.neardup(4, 4, 64, 8, short=0, label="3 documents")
+    dr.minhash_batch("plain", True, d, 5, 128, label="K 128 again", dups=True)
+    small = dr.neardup(4, 2, 64, 120, short=0, label="B 4, fewer pairs")
+    assert 0 < len(small[1]) < len(big[1])  # (pcap shrinks with the count)
+    dr.neardup(4, 2, 64, 120, short=None, label="B 4, no arrays")
+    many = dr.postings_batch(True, a, label="many keys")
+    wide = dr.search_batch(True, qa, 64, label="topk 64, 8 queries")
+    one = M.Batch(("oneq",), qa.buf, qa.off[:2])
+    dr.search_batch(True, one, 1, label="topk 1, 1 query")
+    assert int(wide[2].max()) > 1
+    dr.colloc_batch(True, a, np.ones(len(v0), np.uint8), label="keep: every id")
+    dr.colloc_batch(True, a, None, label="keep: none")
+    dr.colloc_read("npmi", 2, 0.1, label="after the keep masks")
+    dr.set_vocab(v1)
+    fewer = dr.postings_batch(True, a, label="few keys")
+    assert len(fewer[0]) < len(many[0]) and len(fewer[1]) < len(many[1])
+    dr.colloc_batch(True, a, label="few keys")
+    dr.colloc_read("count", label="few keys")
+    dr.stats("at the end")
+
+
+def test_newest_calls_same_shape_other_text(syn):
+    """Per newest kind: a batch, its twin of identical document lengths and other runes, the batch again, each answer
+    its own; then per kind a large call followed by a small one (K 128 then 16 and 64 documents then 3; many keys
+    then few; topk 64 then 1 and 8 queries then 1; B and pcap shrinking; a keep mask of every id, then none)."""
+    dr = open_20k(syn)
+    try:
+        script_same_shape3(dr)
+    finally:
+        dr.tk.close()
+
+
+def every_newest(dr, big, tiny, q, label, skip=(), filtered=True):
+    """One call of every newest kind (but `skip`; the filtered ones only with `filtered`) and of one older kind."""
+    if "minhash_batch" not in skip and filtered:
+        dr.minhash_batch("search", True, tiny, 3, 32, label=label)
+        dr.neardup(8, 4, 64, 16, short=0, label=label)
+    if "filter_batch" not in skip:
+        dr.filter_batch("plain", True, tiny, M.RULES[1], label=label)
+    if "postings_batch" not in skip:
+        dr.postings_batch(True, tiny, 3, label=label)
+    if "search_batch" not in skip:
+        dr.search_batch(True, q, 5, label)
+    if "colloc_batch" not in skip and filtered:
+        dr.colloc_batch(True, tiny, label=label)
+        dr.colloc_read("count", label=label)
+    dr.keywords(True, big, 5, label)
+    dr.stats(label)
+
+
+def script_errors(dr):
+    m = dr.m
+    big, tiny = dr.batch(("small", 2100, 30 << 10)), dr.batch(("tiny", 2110, 5))
+    q, d = dr.batch(("queries", 2120, 6)), dr.batch(("dups", 2130, 24))
+    dr.set_vocab(m.vocab_keys(0))
+    dr.build_index([big])
+    dr.set_stop(m.stop_keys(0))
+    # jb_postings_batch: one entry short, then with room
+    dr.postings_batch(True, big, short=1, label="one short")
+    dr.stats("postings one short")
+    every_newest(dr, big, tiny, q, "after postings' JB_ELIMIT", skip=("postings_batch",))
+    dr.postings_batch(True, big, label="with room")
+    # jb_cut_batch_filter
+    dr.filter_batch("search", True, big, M.RULES[2], short=1, label="one short")
+    dr.stats("filter one short")
+    every_newest(dr, big, tiny, q, "after the filter's JB_ELIMIT", skip=("filter_batch",))
+    dr.filter_batch("search", True, big, M.RULES[2], label="with room")
+    # jb_neardup_sig: counts only, one short, an exact fit
+    dr.minhash_batch("plain", True, d, 5, 128, label="dups", dups=True)
+    want = dr.neardup(32, 4, 64, 64, short=None, label="counts only")
+    assert len(want[1]) >= 3
+    dr.neardup(32, 4, 64, 64, short=1, label="one short")
+    every_newest(dr, big, tiny, q, "after neardup's JB_ELIMIT", skip=("minhash_batch",))
+    dr.minhash_batch("plain", True, d, 5, 128, label="dups", dups=True)
+    dr.neardup(32, 4, 64, 64, short=0, label="an exact fit")
+    # a batch filter that asks for a stop set that is gone: JB_EINVAL after the cut, both tables untouched
+    dr.wc_batch("plain", True, tiny, "before")
+    dr.colloc_batch(True, big, label="before")
+    dr.set_stop(None)
+    dr.set_filter(M.RULES[2])
+    before = None
+    if dr.tk is not None:
+        import torch
+        torch.cuda.synchronize()
+        before = (inner_bytes(dr.table[0], dr.table[1]).tobytes(), dr.colloc_raw())
+    for k, x in enumerate((big, tiny)):
+        dr.join_batch("search", True, x, b" ", b"\n", f"no stop set {k}")
+        dr.stats("after join's JB_EINVAL")  # (the cut ran: its count)
+        dr.wc_batch("full", False, x, f"no stop set {k}")
+        dr.minhash_batch("plain", False, x, label=f"no stop set {k}")
+        dr.colloc_batch(True, x, label=f"no stop set {k}")
+        dr.stats("after colloc's JB_EINVAL")
+    if dr.tk is not None:
+        torch.cuda.synchronize()
+        assert before == (inner_bytes(dr.table[0], dr.table[1]).tobytes(), dr.colloc_raw()), "a refused call changed a table"
+    every_newest(dr, big, tiny, q, "the unfiltered kinds under the broken filter", filtered=False)
+    dr.wc_read("after the refusals")
+    dr.colloc_read("npmi", 2, 0.1, label="after the refusals")
+    dr.set_filter(None)
+    every_newest(dr, big, tiny, q, "after the filter's JB_EINVAL")
+    dr.set_stop(m.stop_keys(1))
+    dr.set_filter(M.RULES[2])
+    every_newest(dr, big, tiny, q, "a stop set again")
+    dr.wc_batch("plain", True, tiny, "a stop set again")
+    dr.wc_read("at the end")
+
+
+def test_error_returns_leave_the_context_whole(syn):
+    """JB_ELIMIT from jb_postings_batch, jb_cut_batch_filter and jb_neardup_sig (arrays one entry short; none at all)
+    with the counts, post_off / pair_off and the statistics right and nothing else written, and JB_EINVAL from join,
+    wc, MinHash and colloc under a batch filter whose stop set is gone, with the word-count and collocation tables
+    bit-identical before and after: after each, a call of every other newest kind and of an older one equals the
+    model, and so does the refused call once it has room."""
+    dr = open_20k(syn)
+    try:
+        script_errors(dr)
+    finally:
+        dr.tk.close()
+
+
+MINI_PARTS = ("今天", "天氣", "很好", "我", "昨天", "去", "上海", "交通", "大學", "這", "的", "一刹那", "量子力學", "，", "。", " ",
+              "abc ", "2024 ", "甲甲甲", "\x80")
+
+
+def mini_docs(seed, ndocs, most):
+    rng = np.random.default_rng(seed)
+    return ["".join(MINI_PARTS[int(rng.integers(0, len(MINI_PARTS)))] for _ in range(int(rng.integers(0, most))))
+            .encode("utf-8", "surrogateescape").replace(b"\xc2\x80", b"\x80") for _ in range(ndocs)]
+
+
+def script_filter_life(dr):
+    m = dr.m
+    b = dr.batch(M.from_texts(("mini", 41), mini_docs(41, 300, 40)))
+    t = dr.batch(M.from_texts(("mini", 43), mini_docs(43, 6, 12)))
+    q = dr.batch(M.from_texts(("miniq",), ["今天天氣很好", "上海交通大學", "", "zzz 未知", "昨天去上海 abc"]))
+    regrow = dr.batch(M.from_texts(("regrow12",), ["甲" * 12, X4 + "甲" * 12]))
+    assert 24 << 10 <= b.nbytes <= LARGE3 and t.nbytes <= M.SMALL_MAX
+    assert len(m.cut(regrow, "full", False, count=False)[0]) > regrow.nbytes  # (the front cuts twice)
+    keys = set()
+    for x in (b, t, q, regrow):
+        s, e, _ = m.cut(x, "plain", True, count=False)
+        keys |= {bytes(x.buf[int(i):int(j)]) for i, j in zip(s, e) if j - i > 1 or x.buf[int(i)] < 0x80}
+    dr.set_vocab(sorted(keys))
+    dr.build_index([b, t])
+    stop1 = ["今天".encode(), "的".encode(), b"abc", ("甲" * 3).encode()]
+    stop2 = ["上海".encode(), ("甲" * 2).encode(), ("甲" * 4).encode(), b"2024", "。".encode()]
+    dr.set_stop(stop1)
+    own = M.RULES[1]
+
+    def lap(label, x=b, unfiltered=True):
+        out = []
+        for mode, hmm in (("plain", True), ("search", True), ("full", False)):
+            dr.join_batch(mode, hmm, x, b" ", b"\n", label)
+            out.append(m.join(x, mode, hmm, b" ", b"\n"))
+            dr.wc_batch(mode, hmm, x, label)
+            out.append(dr.minhash_batch(mode, hmm, x, 2, 32, label=label))
+            if unfiltered:
+                dr.charspans_batch(mode, hmm, x, "rune", False, label)
+                dr.filter_batch(mode, hmm, x, own, label=label)
+            dr.stats(f"{label} {mode}")
+        dr.colloc_batch(True, x, label=label)
+        out.append({k: v for k, v in m.cl["table"].items()})
+        if unfiltered:
+            dr.keywords(True, x, 5, label)
+            dr.df(True, x, label)
+            dr.textrank(True, x, label=label)
+            dr.postings_batch(True, x, label=label)
+            dr.search_batch(True, q, 10, label)
+            dr.stats(label)
+        dr.colloc_read("count", label=label)
+        dr.wc_read(label)
+        return out
+
+    def differ(x, y):
+        """Whether every filtered answer of two laps differs (joined bytes, signatures); the tables only grow."""
+        return all(not np.array_equal(np.asarray(i[0]), np.asarray(j[0])) for i, j in zip(x[:-1], y[:-1]))
+
+    before = lap("before")
+    before_t = lap("before, tiny", t)
+    dr.set_filter(M.RULES[0])
+    first = lap("the first rule")
+    assert differ(before, first)
+    lap("the first rule, tiny", t)
+    dr.set_filter(M.RULES[1])  # (replaces the first)
+    second = lap("the second rule")
+    assert differ(first, second) and differ(before, second)
+    dr.set_filter(M.RULES[2])
+    s1 = lap("a stop-using rule", unfiltered=False)
+    dr.set_stop(stop2)
+    s2 = lap("the stop set replaced", unfiltered=False)
+    assert differ(s1, s2) and differ(before, s2)
+    # (a word of b that t does not hold: t's answers stay, as the model confirms at the end)
+    ttext = bytes(t.buf[:int(t.off[-1])]).decode("utf-8", "replace")
+    word = next(w for w in (m.pick_word(k, b) for k in range(8)) if w not in ttext)
+    dr.add_word(word, 10_000_000)
+    s3 = lap("after AddWord")
+    assert differ(s2, s3)  # (the filtered results follow the new dictionary)
+    # full mode's regrow with the filter on, then the calls that cut kArTokens up as ids, terms and work
+    for k, (hand, after) in enumerate((("join", "postings"), ("wc", "search"), ("minhash", "colloc"), ("join", "colloc"),
+                                       ("minhash", "postings"), ("wc", "search"))):
+        label = f"regrow {k}"
+        if hand == "join":
+            dr.join_batch("full", False, regrow, b" ", b"\n", label)
+        elif hand == "wc":
+            dr.wc_batch("full", False, regrow, label)
+        else:
+            dr.minhash_batch("full", False, regrow, 2, 16, label=label)
+        dr.stats(label)
+        if after == "postings":
+            dr.postings_batch(True, (b, regrow)[k % 2], label=label)
+        elif after == "search":
+            dr.search_batch(True, q, 10, label)
+        else:
+            dr.colloc_batch(True, (b, regrow)[k % 2], label=label)
+            dr.colloc_read("count", label=label)
+        dr.stats(label)
+    dr.set_filter(None)
+    # cleared: every kind answers as with no filter.  For b that is the unfiltered answer under the dictionary with
+    # the added word; for t, which does not hold the word, it is what it was before the first set, to the byte
+    after = lap("cleared")
+    assert differ(s3, after) and m.bfilter is None
+    after_t = lap("cleared, tiny", t)
+    for x, y in zip(before_t[:-1], after_t[:-1]):
+        assert np.array_equal(np.asarray(x[0]), np.asarray(y[0])) and np.array_equal(np.asarray(x[1]), np.asarray(y[1]))
+
+
+def test_batch_filter_over_a_contexts_life(mini):
+    """One ctx (the mini dictionary with the regrow chain): every filtered and every unfiltered kind in plain, search
+    and full mode with no filter, a rule, a rule that replaces it, a stop-using rule under two stop sets, after
+    AddWord, around a full-mode regrow batch (followed by postings, search and colloc, which cut kArTokens up
+    differently), and cleared; the model says where the answers must differ."""
+    mini_text, emit = mini
+    dr = open_text(regrow_dict(mini_text), emit)
+    try:
+        script_filter_life(dr)
+    finally:
+        dr.tk.close()
+
+
+def rune_pairs(m, b, hmm, keys):
+    """{word: count} of the pairs of neighbouring one-rune Han tokens of b's plain cut (inside one document) whose
+    runes are both among `keys` and whose concatenation is reachable and no dictionary key: a word AddWord can make
+    one token of."""
+    s, e, d = m.cut(b, "plain", hmm, count=False)
+    firsts, pairs, keys = set(d.tolist()), {}, set(keys)
+    for k in range(len(s) - 1):
+        if e[k] - s[k] == 3 and e[k + 1] - s[k + 1] == 3 and e[k] == s[k + 1] and k + 1 not in firsts:
+            w = bytes(b.buf[int(s[k]):int(e[k + 1])]).decode("utf-8", "replace")
+            if all(HAN[0] <= c <= HAN[1] for c in w) and m.o.get(w) is None and m.reachable(w) and \
+                    w[0] != w[1] and w[0].encode() in keys and w[1].encode() in keys:
+                pairs[w] = pairs.get(w, 0) + 1
+    return pairs
+
+
+def script_index_life(dr):
+    m = dr.m
+    b1, b2 = dr.batch(("offset", 2300, 28 << 10)), dr.batch(("small", 2310, 24 << 10))
+    large, q = dr.batch(("large", 2320, LARGE3)), dr.batch(("queries", 2330, 6))
+    tiny = dr.batch(("tiny", 2340, 4))
+    v0, v1 = m.vocab_keys(0), m.vocab_keys(1)
+    assert len(v0) != len(v1) and b1.ndocs + b2.ndocs > 10 * tiny.ndocs
+
+    def hits(r):
+        return int((r[2] > 0).sum()), int((r[2] == 0).sum())
+
+    dr.set_vocab(v0)
+    dr.search_batch(True, q, 10, "no index yet")  # JB_EINVAL
+    dr.build_index([b1, b2])
+    first = [dr.search_batch(True, q, k, "the first index") for k in (10, 1, 64)]
+    dr.stats("the first index")
+    assert min(hits(first[0])) > 0  # (queries with documents and queries without)
+    dr.postings_batch(True, large, label="between two searches")
+    dr.minhash_batch("full", False, large, 5, 128, label="between two searches")
+    again = [dr.search_batch(True, q, k, "again") for k in (10, 1, 64)]
+    assert all(x is y for x, y in zip(first, again))
+    # a word of a query: the index stays, the query's cut moves
+    pairs = rune_pairs(m, q, True, v0)
+    word = min(pairs, key=lambda w: (-pairs[w], w))
+    dr.add_word(word, 10_000_000)
+    moved = dr.search_batch(True, q, 10, "after AddWord")
+    assert m.index.vversion == m.vversion and not all(np.array_equal(x, y) for x, y in zip(first[0], moved))
+    dr.stats("after AddWord")
+    # a vocabulary of another key count: search is refused, every other kind answers
+    dr.set_vocab(v1)
+    stats = m.last_tokens
+    dr.search_batch(True, q, 10, "the vocabulary replaced")
+    assert m.last_tokens == stats  # (refused before the cut)
+    dr.stats("after the refusal")
+    dr.minhash_batch("plain", True, tiny, label="the vocabulary replaced")
+    dr.filter_batch("search", True, b2, M.RULES[0], label="the vocabulary replaced")
+    dr.postings_batch(True, b2, label="the vocabulary replaced")
+    dr.colloc_batch(True, b2, label="the vocabulary replaced")
+    dr.colloc_read("npmi", 2, 0.1, label="the vocabulary replaced")
+    dr.keywords(True, tiny, 5, "the vocabulary replaced")
+    dr.join_batch("plain", True, tiny, b" ", b"\n", "the vocabulary replaced")
+    dr.search_batch(True, q, 10, "still refused")
+    dr.build_index([b1, b2])
+    rebuilt = dr.search_batch(True, q, 64, "rebuilt")
+    assert min(hits(rebuilt)) > 0
+    # an index over far fewer documents, other parameters: kArSearch keeps the larger size
+    dr.build_index([tiny], k1=2.0, b=0.0)
+    small = dr.search_batch(True, q, 64, "few documents")
+    assert int(small[2].max()) <= tiny.ndocs < int(rebuilt[2].max())
+    dr.search_batch(False, q, 1, "few documents")
+    dr.stats("few documents")
+    dr.clear_index()
+    dr.search_batch(True, q, 10, "no index")
+    dr.postings_batch(True, tiny, label="no index")
+    dr.stats("at the end")
+
+
+def test_index_over_a_contexts_life(syn):
+    """An index built from two batches, attached and searched; a large postings_batch and a full-mode minhash_batch
+    between two searches that agree; AddWord of a word of a query (the old index, the new cut: other answers, from
+    the model); a vocabulary of another key count (JB_EINVAL from search alone); rebuilt; replaced by a much
+    smaller one with other k1 / b; cleared (JB_EINVAL).  The fixtures offer one setting of JB_BM25_FORM, the
+    default; test_gpu_bm25.py compares the two forms."""
+    dr = open_20k(syn)
+    try:
+        script_index_life(dr)
+    finally:
+        dr.tk.close()
+
+
+def noisy_copies(d):
+    """The documents of a batch, each followed by a copy with ASCII words behind some of its punctuation: tokens a
+    filter of alnum, num and other removes, and with them every difference."""
+    o = [int(x) for x in d.off]
+    docs = []
+    for k in range(d.ndocs):
+        text = bytes(d.buf[o[k]:o[k + 1]]).decode("utf-8")
+        out, n = [], 0
+        for c in text:
+            out.append(c)
+            if c in "，。！？；：、" :
+                n += 1
+                if n % 3 == 0:
+                    out.append(f" memo{n} 20{n:02d} ")
+        docs += [text, "".join(out)]
+    return M.from_texts(("noisy",) + tuple(d.spec), docs)
+
+
+def script_colloc_dedup(dr):
+    m = dr.m
+    b1, b2, b3 = dr.batch(m.source), dr.batch(("offset", 2420, 28 << 10)), dr.batch(("tiny", 2430, 6))
+    none, large, b6 = dr.batch(("empty", 0, 3)), dr.batch(("large", 2440, LARGE3)), dr.batch(("tiny", 2450, 2))
+    # The word to add: as script_wc_life picks it, the most frequent pair of neighbouring one-rune tokens of b1 that
+    # is reachable and no key, here with both runes keys of the vocabulary (so the table counts the pair); the
+    # vocabulary holds the word itself too, so that it has a unigram counter once the dictionary cuts it.
+    v0 = m.vocab_keys(0)
+    pairs = rune_pairs(m, b1, False, v0)
+    word = min(pairs, key=lambda w: (-pairs[w], w))
+    keys = v0 + [word.encode()]
+    dr.set_vocab(keys)
+    pair, wid = (keys.index(word[0].encode()), keys.index(word[1].encode())), len(keys) - 1
+
+    def read(label):
+        dr.colloc_read("npmi", 2, 0.1, label=label)
+        dr.colloc_read("count", label=label)
+        dr.stats(label)
+
+    for k, (x, hmm, keep, contig) in enumerate(((b1, False, None, False), (b3, True, None, True), (b2, True, m.keep, False),
+                                                (none, True, None, False), (large, False, None, True),
+                                                (b6, False, m.keep, True))):
+        dr.colloc_batch(hmm, x, keep, contig, label=f"batch {k}")
+        read(f"batch {k}")
+    counted, uni = m.cl["table"][pair], m.cl["uni"][wid]
+    assert counted >= pairs[word] > 1 and uni == 0
+    dr.add_word(word, 10_000_000)
+    dr.colloc_batch(False, b1, label="after AddWord")
+    read("after AddWord")
+    assert m.cl["table"][pair] == counted and m.cl["uni"][wid] > 0  # (the pair is one token now)
+    distinct = len(m.cl["table"])
+    dr.set_vocab(m.vocab_keys(1))
+    assert m.cl is None
+    dr.colloc_batch(True, b2, label="a new table")
+    read("a new table")
+    assert 0 < len(m.cl["table"]) < distinct
+    # near-duplicates: a dups batch, then copies that differ in tokens a batch filter removes
+    dd = dr.batch(("dups", 2460, 32))
+    dr.minhash_batch("plain", True, dd, 5, 128, label="dups", dups=True)
+    po, pd, pa, _ = dr.neardup(32, 4, 64, 64, short=0, label="dups")
+    plan = M.dup_plan(2460, 32)
+    got = {(int(pd[k]), j) for j in range(dd.ndocs) for k in range(int(po[j]), int(po[j + 1]))}
+    assert {(src, j) for j, (kind, src, _) in enumerate(plan) if kind == "copy"} <= got and len(pd) >= 3
+    assert all(int(pa[k]) == 128 for j, (kind, _, _) in enumerate(plan) if kind == "copy" for k in range(int(po[j]), int(po[j + 1]))
+               if plan[int(pd[k])][0] == "new")
+    noisy = dr.batch(noisy_copies(M.Batch(("dd16",), dd.buf, dd.off[:17])))
+    sig, _ = dr.minhash_batch("plain", True, noisy, 5, 128, label="noisy copies")
+    po, pd, pa, _ = dr.neardup(32, 4, 64, 64, short=0, label="noisy copies")
+    assert all(not np.array_equal(sig[2 * k], sig[2 * k + 1]) for k in range(16))
+    dr.set_filter(M.rule(("alnum", "num", "other")))
+    sig, _ = dr.minhash_batch("plain", True, noisy, 5, 128, label="noisy copies, filtered")
+    assert all(np.array_equal(sig[2 * k], sig[2 * k + 1]) for k in range(16))  # (exact duplicates now)
+    po, pd, pa, _ = dr.neardup(32, 4, 64, 64, short=0, label="noisy copies, filtered")
+    for k in range(16):
+        row = {int(pd[i]): int(pa[i]) for i in range(int(po[2 * k + 1]), int(po[2 * k + 2]))}
+        assert row.get(2 * k) == 128, (k, row)
+    dr.set_filter(None)
+    dr.stats("at the end")
+
+
+def test_collocations_and_dedup_over_a_contexts_life(syn):
+    """One caller-owned collocation table and d_uni (between canaries) over six colloc_batch calls of different sizes,
+    keep masks and flags, read with two scorers after each; AddWord of an adjacent pair the table counts (the pair
+    stops growing, the new word's unigram starts); a new vocabulary, a new table.  Then MinHash and the pairs of a
+    batch with planted copies, and of copies that differ only in tokens a batch filter removes: exact duplicates
+    once it is set."""
+    dr = open_20k(syn)
+    try:
+        script_colloc_dedup(dr)
+    finally:
+        dr.tk.close()
+
+
+@pytest.fixture(scope="module", params=M.SEEDS3)
+def seq3(request, syn):
+    """(seed, ops, the references of gen_ops3(seed, NSTEPS3)): the sequence through the model alone, once, so that
+    the test below spends its time on the library.  The references are the model's cache, whose keys hold the
+    batch, the call's parameters and the versions of the dictionary, the vocabulary, the filter, the stop set and
+    the index, which the same ops reach in the same order."""
+    seed = request.param
+    ops = M.gen_ops3(seed, M.NSTEPS3)
+    dry = dry_20k(syn)
+    dry.set_vocab(dry.m.vocab_keys(0))
+    for op in ops:
+        dry.run(op)
+    return seed, ops, dry.m._cache, dry.batches
+
+
+def test_random_sequences3(syn, seq3):
+    """gen_ops3(seed, NSTEPS3): test_random_sequences2 with the newest kinds of call, the stop set, the batch filter
+    and the index in the sequence, jb_last_stats after every step."""
+    seed, ops, refs, batches = seq3
+    dr = open_20k(syn)
+    dr.m._cache, dr.batches = refs, dict(batches)
+    try:
+        dr.set_vocab(dr.m.vocab_keys(0))
+        for i, op in enumerate(ops):
+            try:
+                dr.run(op)
+                dr.stats()
+            except (AssertionError, J.JbError) as e:
+                raise AssertionError(f"seed {seed}, step {i}: {op!r}\nops = {ops[:i + 1]!r}\n{e}") from e
+        dr.wc_read("at the end")
+        dr.colloc_read("count", label="at the end")
     finally:
         dr.tk.close()
